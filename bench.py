@@ -42,6 +42,13 @@ aux     : end_to_end (fill + grp_finalize + the timed region: the whole goldrush
           reads), probe_accounting (executed against useful probes, the excess attributed), stream_keep
           (what the streaming windows kept across their in-launch inserts), phases.steady.fit (seconds
           per read and per insert over the steady-state slices), pipeline_shaped, oracle_check.
+
+--dump-outputs DIR: after the timed steps, what the last step handed its caller goes to DIR/<name>.npy
+(float64, every value exact): the decisions of the step's reads (commit_<field>.npy, one row per read in
+commit order; a seeded sample of 2^18 reads when the step has more) and the miBF those decisions left
+behind — the classifier's counters (counters.npy, names in the line's aux.dump_outputs) and a seeded
+sample of the ID / count arrays (mibf_pos / mibf_ids / mibf_counts.npy).  The reads come from fixed
+seeds: the same arguments give the same inputs, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -139,6 +146,43 @@ def _newest_profile(pattern: str):
 
 
 WITNESS = 1024  # reads at either end of the stream whose GPU decisions are kept for the oracle's check
+
+# --dump-outputs: at most 2^18 reads' decisions x 10 fields + 2^20 ID / count slots x 3 arrays, all float64: 46 MB
+COMMIT_FIELDS = ("read", "kind", "num_tiles", "num_assigned", "trim_start", "trim_end", "first_id", "path", "hits", "misses")  # Classifier.kept_commits()
+COUNTER_NAMES = ("valid_reads", "total_tiles", "assigned_tiles", "unassigned_tiles", "queries", "hits", "misses", "inserted_bases", "ids_inserted", "reads_committed", "inserts")
+DUMP_READS = 1 << 18
+DUMP_MIBF_RUNS, DUMP_MIBF_RUN = 256, 4096  # runs of consecutive ID / count slots at seeded offsets
+
+
+def dump_outputs(out_dir: str, eng, commits, first: int, count: int, st, pop: int) -> dict:
+    """Write what the last timed step computed (see the module docstring) and describe it for the line."""
+    rows = np.array(commits, dtype=np.float64).reshape(-1, len(COMMIT_FIELDS))
+    rows = rows[(rows[:, 0] >= first) & (rows[:, 0] < first + count)]
+    if count > DUMP_READS:  # the sample is drawn from the step's read numbers: the same reads whatever a build decided
+        pick = np.random.default_rng(0).choice(count, DUMP_READS, replace=False) + first
+        rows = rows[np.isin(rows[:, 0], pick)]
+    arrays = {"commit_" + f: rows[:, i] for i, f in enumerate(COMMIT_FIELDS)}
+    arrays["counters"] = np.array([st[k_] for k_ in COUNTER_NAMES] + [pop], dtype=np.float64)
+    if pop <= DUMP_MIBF_RUNS * DUMP_MIBF_RUN:
+        starts = np.array([0], dtype=np.int64)
+        run = pop
+    else:
+        starts = np.sort(np.random.default_rng(1).integers(0, pop - DUMP_MIBF_RUN + 1, size=DUMP_MIBF_RUNS))
+        run = DUMP_MIBF_RUN
+    pos, ids, counts = [], [], []
+    for s in starts:
+        i_, c_ = eng.export_ids(int(s), int(run))
+        pos.append(np.arange(s, s + run, dtype=np.float64))
+        ids.append(i_)
+        counts.append(c_)
+    arrays["mibf_pos"] = np.concatenate(pos)
+    arrays["mibf_ids"] = np.concatenate(ids).astype(np.float64)
+    arrays["mibf_counts"] = np.concatenate(counts).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "reads_of_last_step": [first, first + count], "commits": int(rows.shape[0]), "sampled": count > DUMP_READS,
+            "counters": list(COUNTER_NAMES) + ["pop"], "arrays": {name: list(arr.shape) for name, arr in arrays.items()}}
 
 
 def cpu_baseline(dr, eng, cls, phases, silver, n_reads: int, m: int, pop: int, seeds, k: int, tile: int, genome: int, budget_s: float = 10.0, kept=None):
@@ -349,10 +393,13 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for single-GPU plumbing tests)")
     ap.add_argument("--verify-ranks", action="store_true", help="developer: N > 1, compare the classifier state of all ranks after the run")
     ap.add_argument("--share-gpu", action="store_true", help="developer: all ranks use GPU 0 (plumbing test on a 1-GPU box, use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; see the module docstring)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ:
         if a.gpus > 1:
             # no launcher around us: start the N ranks ourselves (the single command that uses the whole
@@ -581,8 +628,14 @@ def main():
     # the oracle's witness (cpu_baseline leg): what the GPU path decided for the first and the last WITNESS reads of
     # the stream stays inside the classifier (no callback per read) and is compared with the oracle's serial loop
     witness = world == 1 and rs.n_batches == 1 and not a.no_cpu_baseline and n_reads >= 2 * WITNESS
+    # --dump-outputs: the last step's commits are kept the same way (read numbers are the stream's while it is one batch)
+    dump = a.dump_outputs if rank == 0 else None
+    last_first = (a.steps - 1) * per_step
     if witness:
-        cls.keep_commits(0, WITNESS, n_reads - WITNESS, WITNESS)
+        tail = min(n_reads - WITNESS, last_first) if dump else n_reads - WITNESS
+        cls.keep_commits(0, WITNESS, tail, n_reads - tail)
+    elif dump and rs.n_batches == 1:
+        cls.keep_commits(last_first, per_step)
     slices = []  # (reads, seconds, inserts) per timing slice, rank 0's clock
     finished = [False]  # silver mode: the last path is complete (the reference exits there)
     synth_before = rs.synth_s
@@ -592,6 +645,8 @@ def main():
         # so that the head of the path and the steady state can be told apart
         first = i * per_step
         done = 0
+        if dump and rs.n_batches > 1 and i == a.steps - 1:
+            cls.keep_commits(0, 0xFFFFFFFF)  # read numbers are a batch's own here: keep every commit from the last step on
         while done < per_step and not finished[0]:
             n = min(PHASE_SLICE, per_step - done)
             s0 = cls.state()
@@ -647,6 +702,18 @@ def main():
         assert all(x == allst[0] for x in allst), "ranks disagree: %r" % (allst,)
         if rank == 0:
             sys.stderr.write("verify-ranks: %d ranks agree on %s\n" % (world, dict(zip(keys, mine))))
+    kept = cls.kept_commits() if (witness or dump) else None
+    dumped = None
+    if dump:  # before anything below touches the filter (the silver pass resets its IDs)
+        commits = kept
+        if rs.n_batches > 1:  # batch-local read numbers, in commit order -> the stream's
+            b, prev, commits = last_first // rs.batch, -1, []
+            for c in kept:
+                if c[0] <= prev:
+                    b += 1
+                prev = c[0]
+                commits.append((c[0] + b * rs.batch,) + tuple(c[1:]))
+        dumped = dump_outputs(dump, eng, commits, last_first, per_step, st1, pop)
 
     if rank == 0:
         kq = ks["query"]
@@ -795,6 +862,8 @@ def main():
                     "batch_verify": eng.verify_stats(),  # tiles of the batches' second decisions: patched from records / queried again / redone / calls that fell back
                     "wall_s": dt},
         }
+        if dumped:
+            out["aux"]["dump_outputs"] = dumped
         # where the probes beyond the useful ones went: every frame of every read is useful once (h x queries);
         # the rest is speculation that was thrown away or confirmation that exactness asks for
         vs_, sk_ = out["aux"]["batch_verify"], out["aux"]["stream_keep"]
@@ -811,7 +880,7 @@ def main():
                                           "share_of_useful": {k_: v_ / useful for k_, v_ in acc.items()} if useful else None,
                                           "note": "tile counts x tile x h (a read's clipped last tile counted whole); streaming: grp_debug_stream_stats — tiles finished in front of an in-launch insert whose probes met a changed slot or whose fingerprints were gone"}
         if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(rs, eng, cls, out["phases"], silver, n_reads, m, pop, seeds, k, tile, G, kept=cls.kept_commits() if witness else None)
+            out["cpu_baseline"] = cpu_baseline(rs, eng, cls, out["phases"], silver, n_reads, m, pop, seeds, k, tile, G, kept=kept if witness else None)
             check = out["cpu_baseline"].pop("oracle_check", None)
             out["aux"]["oracle_check"] = check
             if check and not check["identical"]:

@@ -4,7 +4,8 @@ first-party translation units of /root/reference that build from their own sourc
 (oracle/Makefile, target `ref` -> oracle/_ref/): spaced_seeds.cpp (make_seed_pattern),
 calc_phred_average.cpp (calc_phred_average, sum_phred) and opt.cpp (process_options).
 Run in the build container (the GPU box has no /root/reference); the JSON holds inputs
-and the reference's outputs only.  Round 3: reference_funcs.json too (make_funcs below)."""
+and the reference's outputs only.  Round 3: reference_funcs.json too (make_funcs below); reference_live.npz holds the
+reference's answers to the live comparisons of tests/test_reference_funcs.py (make_live)."""
 import ctypes as C
 import json
 import os
@@ -174,6 +175,26 @@ def make_mini():
         json.dump(out, f, indent=1)
 
 
+def make_live():
+    """tests/golden/reference_live.npz: the reference's answers (oracle/_ref/libref_funcs.so) to the seeded calls of the
+    live comparisons in tests/test_reference_funcs.py, recorded by running them (tests/ref_funcs.py, Recorded)."""
+    import sys
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as d:
+        env = dict(os.environ, GRP_RECORD_REFERENCE_LIVE=d)
+        tests = ["tests/test_reference_funcs.py::test_fixture_is_what_the_reference_computes_now",
+                 "tests/test_reference_funcs.py::test_strand_states_host_core_against_the_reference_live"]
+        subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider"] + tests, cwd=ROOT, env=env, check=True)
+        out = {}
+        for f in sorted(os.listdir(d)):
+            z = np.load(os.path.join(d, f))
+            out[f[:-4] + ".flat"], out[f[:-4] + ".off"] = z["flat"], z["off"]
+    np.savez_compressed(os.path.join(HERE, "reference_live.npz"), **out)
+    print("recorded", sorted(out))
+
+
 if __name__ == "__main__":
     main()
     make_mini()
+    make_live()

@@ -72,6 +72,80 @@ class RefFuncs:
         return int(self.lib.ref_hash_universe(weight, genome_size, hash_num))
 
 
+# The reference's answers to the live tests' seeded calls, stored so that those tests run where oracle/_ref cannot be
+# built (no reference sources there): tests/golden/make_reference_fixtures.py `live` records them.
+LIVE = os.path.join(ROOT, "tests", "golden", "reference_live.npz")
+RECORD_ENV = "GRP_RECORD_REFERENCE_LIVE"  # set by the fixture generator: a directory the recorded answers go to
+
+
+def _flat(name, r):
+    if name == "vote_tile":
+        return [r[0], r[1], len(r[2])] + [x for e in r[2] for x in e]
+    if name == "smooth_tiles":
+        return [len(r[0])] + [int(v) for v in r[0]] + [int(v) for v in r[1]] + [r[2]]
+    if name == "find_longest_stretch":
+        return [r[0], r[1]]
+    if name == "eval_flanks":
+        return [int(r[0]), r[1], r[2]]
+    return [r]
+
+
+def _unflat(name, v):
+    if name == "vote_tile":
+        return v[0], v[1], [(v[3 + 2 * i], v[4 + 2 * i]) for i in range(v[2])]
+    if name == "smooth_tiles":
+        n = v[0]
+        return np.array(v[1:1 + n], dtype=np.uint32), np.array(v[1 + n:1 + 2 * n], dtype=np.uint8), v[1 + 2 * n]
+    if name == "find_longest_stretch":
+        return v[0], v[1]
+    if name == "eval_flanks":
+        return bool(v[0]), v[1], v[2]
+    return v[0]
+
+
+class Recorded:
+    """RefFuncs for one test's seeded calls, in call order.  Where oracle/_ref is built the calls go to the reference's
+    lines and every answer must equal the stored one; elsewhere the stored answers (tests/golden/reference_live.npz)
+    stand in.  done() checks that the test made exactly the stored calls."""
+
+    def __init__(self, key):
+        self.key = key
+        self.rf = RefFuncs() if os.path.exists(LIB) else None
+        self.record = os.environ.get(RECORD_ENV)
+        if self.record and self.rf is None:
+            raise RuntimeError("recording the reference's answers needs oracle/_ref (make -C oracle ref)")
+        self.got = []
+        self.stored = None
+        if not self.record:
+            z = np.load(LIVE)
+            flat, off = z[key + ".flat"], z[key + ".off"]
+            self.stored = [flat[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
+
+    def _call(self, name, *args):
+        i = len(self.got)
+        if self.rf is None:
+            assert i < len(self.stored), (self.key, "more calls than tests/golden/reference_live.npz holds")
+            self.got.append(self.stored[i])
+            return _unflat(name, self.stored[i])
+        r = getattr(self.rf, name)(*args)
+        v = [int(x) for x in _flat(name, r)]
+        assert self.stored is None or (i < len(self.stored) and v == self.stored[i]), (self.key, i, "the reference's answer differs from the stored one")
+        self.got.append(v)
+        return r
+
+    def __getattr__(self, name):
+        if name in ("vote_tile", "smooth_tiles", "find_longest_stretch", "eval_flanks", "calc_optimal_size", "hash_universe"):
+            return lambda *args: self._call(name, *args)
+        raise AttributeError(name)
+
+    def done(self):
+        if self.record:
+            off = np.cumsum([0] + [len(v) for v in self.got])
+            np.savez(os.path.join(self.record, self.key + ".npz"), flat=np.array([x for v in self.got for x in v], dtype=np.int64), off=off)
+        else:
+            assert len(self.got) == len(self.stored), (self.key, len(self.got), len(self.stored))
+
+
 def random_tiles(rng, n, wrap=False):
     """Random per-tile query results shaped like real ones: a few IDs close to each other (so the
     +-1 rules fire), lists of (id, count > 2); wrap: IDs around 0 / 2^32 - 1 (uint32 wrap-around

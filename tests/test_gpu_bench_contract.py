@@ -35,6 +35,30 @@ def test_bench_line_has_the_contract_fields():
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == "reads/s" and cb["sample"]
 
 
+def test_dump_outputs_hold_the_last_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the decisions of the last timed step's reads and a sample of the filter behind them, float64,
+    the same files from two runs with the same arguments (the inputs come from fixed seeds, the path is order-exact)."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--config", "C1", "--steps", "3", "--warmup", "1", "--reads", "60000", "--batch", "4096", "--no-cpu-baseline", "--no-pipeline-shaped"]
+    runs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        arr = {f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)}
+        assert d["steps"] == 3 and d["aux"]["dump_outputs"]["reads_of_last_step"] == [2 * 4096, 3 * 4096]
+        assert all(a.dtype == np.float64 for a in arr.values())
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)) <= 64 << 20
+        assert np.array_equal(arr["commit_read"], np.arange(2 * 4096, 3 * 4096))
+        assert set(np.unique(arr["commit_kind"]).tolist()) <= {2, 3, 4, 5}
+        assert arr["counters"][-1] == d["aux"]["pop"] and arr["counters"][:-1].tolist() == [d["aux"]["counters"][k] for k in d["aux"]["dump_outputs"]["counters"][:-1]]
+        assert arr["mibf_ids"].size == arr["mibf_counts"].size == arr["mibf_pos"].size > 0
+        runs.append(arr)
+    a, b = runs
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_two_ranks_on_the_one_gpu_end_where_one_rank_ends():
     """The N > 1 path end to end on the one available GPU (two processes share it): sharded fill
     merged by reduce-scatter + all-gather, batches with striped queries, striped streaming
