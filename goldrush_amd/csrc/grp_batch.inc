@@ -882,7 +882,9 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
     const uint64_t gunits = units * c->params.h;
     for (uint64_t u0 = 0; u0 < gunits; u0 += MAX_GRID_WGS) {
       const uint32_t nb = (uint32_t)std::min<uint64_t>(gunits - u0, MAX_GRID_WGS);
-      if (c->uniform_weight == 16) {
+      if (long_span(c)) {
+        DISPATCH_H(c->params.h, (k_batch_collect<HH, GRP_WT_LONG><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
+      } else if (c->uniform_weight == 16) {
         DISPATCH_H(c->params.h, (k_batch_collect<HH, 16><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
       } else {
         DISPATCH_H(c->params.h, (k_batch_collect<HH, 0><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
@@ -950,7 +952,9 @@ grp_window_overlap(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   for (uint64_t b0 = 0; b0 < nt; b0 += MAX_GRID_WGS) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(nt - b0, MAX_GRID_WGS);
-    if (c->uniform_weight == 16) {
+    if (long_span(c)) {
+      k_ovl_sample<GRP_WT_LONG><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);
+    } else if (c->uniform_weight == 16) {
       k_ovl_sample<16><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);
     } else {
       k_ovl_sample<0><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);

@@ -22,7 +22,9 @@ window_lo(const uint32_t* sBases, uint32_t b)
 
 // The window a hash is taken from: its first 32 bases, and where it lies — seeds whose span exceeds 32 bases
 // (k + h - 1 up to 64; round 4, DevSeeds::wide) fetch the 32 bases behind them from there.  The default geometries
-// (span <= 26) never do: the wide path costs them one wave-uniform branch per hash.
+// (span <= 26) never do: the wide path costs them one wave-uniform branch per hash.  Spans beyond 64 (up to 256,
+// DevSeeds::wide == 2) read every care position from the staged words themselves (seed_hash_long) and run in
+// instantiations of their own (WT == GRP_WT_LONG), which nothing else launches.
 struct Win
 {
   uint64_t lo;
@@ -64,6 +66,58 @@ seed_hash(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t s, c
   return fwd + rev;
 }
 
+// The long-span class of the kernels' WT parameter: seeds whose span exceeds 64 bases (k + h - 1 up to GRP_MAX_SPAN =
+// 256).  The host launches these instantiations instead of the WT == 0 ones when DevSeeds::wide == 2; the forms of
+// spans up to 64 keep their code.
+constexpr int GRP_WT_LONG = -1;
+
+// seed_hash for spans beyond 64 bases: each care position's 2-bit base is read from the staged words
+// (one LDS dword per care position; a base never straddles two words).  No window is built — a per-lane array
+// of the span would live in scratch — and every position read lies inside the seed's span, so inside the bases
+// a kernel stages for its frames (a frame's seeds end at or before the last staged base).
+__device__ inline uint64_t
+seed_hash_long(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t s, const Win& w)
+{
+  uint64_t fwd = 0, rev = 0;
+  const uint32_t wt = sd->weight[s];
+  const ulonglong2* t = sTab + (size_t)s * sd->wmax * 4u;
+  const uint32_t bit0 = w.b * 2u;
+  for (uint32_t i = 0; i < wt; ++i) {
+    const uint32_t bit = bit0 + sd->shift[s][i];
+    const uint32_t b = (w.src[bit >> 5] >> (bit & 31u)) & 3u;
+    const ulonglong2 e = t[i * 4u + b];
+    fwd ^= e.x;
+    rev ^= e.y;
+  }
+  return fwd + rev;
+}
+
+// WT > 0: every seed has weight WT (make_seed_pattern's seeds do) and the care
+// loop is fully unrolled; WT == 0: run-time weights; WT == GRP_WT_LONG: run-time
+// weights, spans beyond 64 bases
+template<int WT>
+__device__ inline uint64_t
+seed_hash_t(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t s, const Win& win)
+{
+  const uint64_t w = win.lo; // (WT > 0 is only dispatched for seeds of span <= 32: the engine clears uniform_weight otherwise)
+  if constexpr (WT == 0) {
+    return seed_hash(sTab, sd, s, win);
+  } else if constexpr (WT == GRP_WT_LONG) {
+    return seed_hash_long(sTab, sd, s, win);
+  } else {
+    uint64_t fwd = 0, rev = 0;
+    const ulonglong2* t = sTab + (size_t)s * WT * 4u;
+#pragma unroll
+    for (uint32_t i = 0; i < (uint32_t)WT; ++i) {
+      const uint32_t b = (uint32_t)(w >> sd->shift[s][i]) & 3u;
+      const ulonglong2 e = t[i * 4u + b];
+      fwd ^= e.x;
+      rev ^= e.y;
+    }
+    return fwd + rev;
+  }
+}
+
 __device__ inline void
 load_tab(ulonglong2* sTab, const DevSeeds* __restrict__ sd)
 {
@@ -83,7 +137,8 @@ stage_bases(uint32_t* sBases, const uint32_t* __restrict__ packed, uint64_t word
   const uint32_t w0 = b0 >> 4;
   const uint32_t w_last = (b0 + nb + 15u) >> 4; // exclusive
   const uint32_t w_read = (len + 15u) >> 4;     // words the read owns
-  const uint32_t nw = w_last - w0 + 4u; // + pad: a window reads up to 3 words from its first one, a wide one (span > 32) 5
+  const uint32_t nw = w_last - w0 + 4u; // + pad: a window reads up to 3 words from its first one, a wide one (span > 32) 5;
+                                        // a long one (span > 64) reads its care positions only, all before b0 + nb
   for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) {
     uint32_t w = w0 + i;
     sBases[i] = (w < w_read) ? packed[word_off + w] : 0u;
@@ -145,6 +200,76 @@ k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk
         widx[j][s] = 0;
         if (ok) {
           uint64_t hv = seed_hash(sTab, sd, s, window_at(sBases, boff + i));
+          uint64_t pos = grp_mod_m(hv, f.m, f.m_inv);
+          widx[j][s] = pos >> 5;
+          mask[j][s] = 1u << (uint32_t)(pos & 31u);
+        }
+      }
+    }
+    // test first (plain load), set only where needed: the filter saturates and
+    // most probes find their bit already set
+#pragma unroll
+    for (int j = 0; j < FR; ++j) {
+#pragma unroll
+      for (int s = 0; s < H; ++s) {
+        val[j][s] = mask[j][s] ? words[widx[j][s]] : 0xFFFFFFFFu;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < FR; ++j) {
+#pragma unroll
+      for (int s = 0; s < H; ++s) {
+        if (mask[j][s] & ~val[j][s]) {
+          atomicOr(&words[widx[j][s]], mask[j][s]);
+        }
+      }
+    }
+  }
+}
+
+// k_fill for seeds of spans beyond 64 bases (DevSeeds::wide == 2): the same body with seed_hash_long.  A copy, not a
+// shared inline body: sharing one moved k_fill<5..8>'s scalar registers (+4 SGPRs), and the forms of spans up to 64
+// keep their code.
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_fill_long(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk_begin)
+{
+  extern __shared__ uint4 smem4[];
+  ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+
+  const uint64_t chunk = chunk_begin + blockIdx.x;
+  const uint32_t r = rd.chunk_read[chunk];
+  const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
+  const uint32_t len = rd.len[r];
+  const uint32_t k = sd->k;
+  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + H - 1
+  const uint32_t p0 = ci * FILL_CHUNK;
+  const uint32_t np = min(FILL_CHUNK, npos - p0);
+
+  load_tab(sTab, sd);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  __syncthreads();
+
+  uint32_t* words = f.bv;
+  constexpr int FR = 4;
+  for (uint32_t i0 = threadIdx.x; i0 < np; i0 += THREADS * FR) {
+    uint64_t widx[FR][H];
+    uint32_t mask[FR][H];
+    uint32_t val[FR][H];
+#pragma unroll
+    for (int j = 0; j < FR; ++j) {
+      const uint32_t i = i0 + j * THREADS;
+      const uint32_t p = p0 + i;
+#pragma unroll
+      for (int s = 0; s < H; ++s) {
+        // seed s is valid at read position p iff p + span_s <= len
+        // (stale re-inserts of the iterator set the same bit again)
+        const bool ok = (i < np) && (p + sd->span[s] <= len);
+        mask[j][s] = 0;
+        widx[j][s] = 0;
+        if (ok) {
+          uint64_t hv = seed_hash_long(sTab, sd, s, window_at(sBases, boff + i));
           uint64_t pos = grp_mod_m(hv, f.m, f.m_inv);
           widx[j][s] = pos >> 5;
           mask[j][s] = 1u << (uint32_t)(pos & 31u);
@@ -502,29 +627,6 @@ better(uint32_t c, uint32_t id, uint32_t bc, uint32_t bid)
   return (c > bc) || (c == bc && c != 0u && id < bid);
 }
 
-// WT > 0: every seed has weight WT (make_seed_pattern's seeds do) and the care
-// loop is fully unrolled; WT == 0: run-time weights
-template<int WT>
-__device__ inline uint64_t
-seed_hash_t(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t s, const Win& win)
-{
-  const uint64_t w = win.lo; // (WT > 0 is only dispatched for seeds of span <= 32: the engine clears uniform_weight otherwise)
-  if constexpr (WT == 0) {
-    return seed_hash(sTab, sd, s, win);
-  } else {
-    uint64_t fwd = 0, rev = 0;
-    const ulonglong2* t = sTab + (size_t)s * WT * 4u;
-#pragma unroll
-    for (uint32_t i = 0; i < (uint32_t)WT; ++i) {
-      const uint32_t b = (uint32_t)(w >> sd->shift[s][i]) & 3u;
-      const ulonglong2 e = t[i * 4u + b];
-      fwd ^= e.x;
-      rev ^= e.y;
-    }
-    return fwd + rev;
-  }
-}
-
 // ---- the seeds of one make_seed_pattern family share their halves ---------------------------
 // seed i = left || 0^i || right (DevSeeds::n_left).  With seed 0's table entries
 //   T[q][b] = { srol(SEED[b], K0-1-q), srol(SEED[comp b], q) }
@@ -541,7 +643,7 @@ seed_halves(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t n_
 {
   const uint64_t w = win.lo; // (n_left is 0 for wide seeds: the shared halves are a 32-base form)
   L = RL = R = RR = 0;
-  const uint32_t wt = WT ? (uint32_t)WT : sd->weight[0];
+  const uint32_t wt = WT > 0 ? (uint32_t)WT : sd->weight[0];
   if (n_left == 8u && wt == 16u) { // the pipeline's seeds (weight 16, palindromic): straight-line code
     if constexpr (LEFT) {
 #pragma unroll
@@ -2520,7 +2622,7 @@ k_query(DevFilter f,
   // Where the helper lanes would cost a pass (h = 5: 244 frames per block, a 1000-frame tile
   // would need 5 passes instead of 4) every wave's last lanes evaluate their neighbours' right
   // halves themselves instead (256 frames per block, H - 1 extra half evaluations per wave).
-  const uint32_t n_left = (H >= 2) ? sd->n_left : 0u;
+  const uint32_t n_left = (H >= 2 && WT != GRP_WT_LONG) ? sd->n_left : 0u; // (0 for long spans: the halves are a 32-base form)
   constexpr uint32_t OV = (uint32_t)H - 1u, USE = 64u - OV;
   static_assert(THREADS == 256, "the helper-lane layout below is written for four waves per workgroup (my_wave == 3 is the last one, FBH = 3 * USE + 64)");
   constexpr uint32_t FBH = 3u * USE + 64u;
@@ -3052,18 +3154,18 @@ dedup_claim(unsigned long long* table, uint64_t cap_mask, unsigned long long key
   }
 }
 
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_insert(DevFilter f,
-         DevReads rd,
-         const DevSeeds* __restrict__ sd,
-         uint32_t tile_len,
-         uint32_t read_idx,
-         uint32_t tile_start,
-         uint32_t id,
-         unsigned long long* __restrict__ dedup,
-         uint64_t dedup_mask,
-         unsigned long long epoch_tag)
+template<int H, int WT>
+__device__ __forceinline__ void
+insert_tiles(const DevFilter& f,
+             const DevReads& rd,
+             const DevSeeds* __restrict__ sd,
+             uint32_t tile_len,
+             uint32_t read_idx,
+             uint32_t tile_start,
+             uint32_t id,
+             unsigned long long* __restrict__ dedup,
+             uint64_t dedup_mask,
+             unsigned long long epoch_tag)
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
@@ -3090,7 +3192,7 @@ k_insert(DevFilter f,
 #pragma unroll
     for (int s = 0; s < H; ++s) {
       const uint32_t fs = min(fr, Lp - sd->span[s]);
-      pr[s] = grp_locate(f, seed_hash(sTab, sd, s, window_at(sBases, boff + fs)));
+      pr[s] = grp_locate(f, seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs)));
     }
 #pragma unroll
     for (int s = 0; s < H; ++s) {
@@ -3127,6 +3229,39 @@ k_insert(DevFilter f,
       }
     }
   }
+}
+
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_insert(DevFilter f,
+         DevReads rd,
+         const DevSeeds* __restrict__ sd,
+         uint32_t tile_len,
+         uint32_t read_idx,
+         uint32_t tile_start,
+         uint32_t id,
+         unsigned long long* __restrict__ dedup,
+         uint64_t dedup_mask,
+         unsigned long long epoch_tag)
+{
+  insert_tiles<H, 0>(f, rd, sd, tile_len, read_idx, tile_start, id, dedup, dedup_mask, epoch_tag);
+}
+
+// seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_insert_long(DevFilter f,
+              DevReads rd,
+              const DevSeeds* __restrict__ sd,
+              uint32_t tile_len,
+              uint32_t read_idx,
+              uint32_t tile_start,
+              uint32_t id,
+              unsigned long long* __restrict__ dedup,
+              uint64_t dedup_mask,
+              unsigned long long epoch_tag)
+{
+  insert_tiles<H, GRP_WT_LONG>(f, rd, sd, tile_len, read_idx, tile_start, id, dedup, dedup_mask, epoch_tag);
 }
 
 // ---- whole-read insert (all ID blocks of a read in two launches) ------------------
@@ -3266,9 +3401,9 @@ k_debug_locate(const uint64_t* __restrict__ x, uint64_t n, uint64_t m, uint64_t 
   }
 }
 
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_debug_tile_hashes(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
+template<int H, int WT>
+__device__ __forceinline__ void
+debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
@@ -3285,12 +3420,27 @@ k_debug_tile_hashes(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_
 #pragma unroll
     for (int s = 0; s < H; ++s) {
       const uint32_t fs = min(fr, Lp - sd->span[s]);
-      uint64_t hv = seed_hash(sTab, sd, s, window_at(sBases, boff + fs));
+      uint64_t hv = seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs));
       uint64_t o = (uint64_t)fr * H + s;
       if (o < cap) {
         out[o] = hv;
       }
     }
   }
+}
+
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_debug_tile_hashes(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
+{
+  debug_tile_hashes<H, 0>(rd, sd, tile_len, read_idx, tile_idx, out, cap);
+}
+
+// seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_debug_tile_hashes_long(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
+{
+  debug_tile_hashes<H, GRP_WT_LONG>(rd, sd, tile_len, read_idx, tile_idx, out, cap);
 }
 

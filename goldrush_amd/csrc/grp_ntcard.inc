@@ -75,6 +75,67 @@ k_ntcard(DevReads rd,
   }
 }
 
+// k_ntcard for seeds of spans beyond 64 bases (DevSeeds::wide == 2): the same body with seed_hash_long (a copy, as
+// k_fill_long: a shared inline body moved k_ntcard<5..8>'s scalar registers)
+template<int H>
+__global__ void __launch_bounds__(THREADS)
+k_ntcard_long(DevReads rd,
+              const DevSeeds* __restrict__ sd,
+              const uint2* __restrict__ chunks, // (read, chunk index inside the read)
+              const uint32_t* __restrict__ extra, // [read - first][H] stale repeats of the last window, or nullptr
+              uint32_t first,
+              uint32_t* __restrict__ counters,
+              uint32_t sbits)
+{
+  extern __shared__ uint4 smem4[];
+  ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+
+  const uint2 ck = chunks[blockIdx.x];
+  const uint32_t r = ck.x;
+  const uint32_t len = rd.len[r];
+  const uint32_t k = sd->k;
+  const uint32_t npos = len - k + 1u; // listed => len >= k
+  const uint32_t p0 = ck.y * FILL_CHUNK;
+  const uint32_t np = min(FILL_CHUNK, npos - p0);
+
+  load_tab(sTab, sd);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  __syncthreads();
+
+  const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
+  for (uint32_t i = threadIdx.x; i < np; i += THREADS) {
+    const uint32_t p = p0 + i;
+    const Win w = window_at(sBases, boff + i);
+#pragma unroll
+    for (int s = 0; s < H; ++s) {
+      const uint32_t span = sd->span[s];
+      if (p + span > len) {
+        continue; // no window of seed s starts here
+      }
+      const uint64_t hv = seed_hash_long(sTab, sd, s, w);
+      // ntComp (:81-94)
+      uint32_t ind = NTC_NSAMP;
+      if ((hv >> (63u - sbits)) == 1ull) {
+        ind = 0;
+      }
+      if ((hv >> (64u - sbits)) == smask) {
+        ind = 1;
+      }
+      if (ind < NTC_NSAMP) {
+        // the seed's last window is counted again for every frame it stays stale:
+        // span_s - k frames for a plain read, or what the host computed
+        uint32_t times = 1u;
+        if (p + span == len) {
+          times += extra ? extra[(size_t)(r - first) * H + s] : (span - k);
+        }
+        const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
+        atomicAdd(&counters[slot], times);
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(THREADS)
 k_ntcard_zeros(const uint32_t* __restrict__ counters, unsigned long long* __restrict__ zeros)
 {
@@ -160,9 +221,15 @@ grp_ntcard_add(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, c
   const size_t lds = tab_bytes(c) + bases_bytes(FILL_CHUNK + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_NTCARD, hashes);
-    DISPATCH_H(c->params.h,
-               (k_ntcard<HH><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
-                 r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
+    if (long_span(c)) {
+      DISPATCH_H(c->params.h,
+                 (k_ntcard_long<HH><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
+                   r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
+    } else {
+      DISPATCH_H(c->params.h,
+                 (k_ntcard<HH><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
+                   r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
+    }
     HIP_TRY(c, hipGetLastError());
   }
   // `chunks` (and the caller's array) must outlive the copies

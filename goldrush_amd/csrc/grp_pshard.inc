@@ -376,6 +376,9 @@ grp_debug_touch_filter(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t 
   if (!c->finalized) {
     return set_err(c, GRP_ERR_STATE, "grp_debug_touch_filter before grp_finalize");
   }
+  if (long_span(c)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t H = c->params.h, tile = c->params.tile;
   const uint64_t t0 = r->tile0[first];
@@ -441,6 +444,9 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   }
   if (!c->finalized) {
     return set_err(c, GRP_ERR_STATE, "grp_pshard_query before grp_finalize");
+  }
+  if (long_span(c)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
   }
   const uint32_t H = c->params.h, tile = c->params.tile;
   if ((uint64_t)tile * H > 65535u) {

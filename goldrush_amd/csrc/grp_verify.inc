@@ -504,7 +504,10 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       vf.read_ins = d_read_ins;
       vf.n_reads = count;
       Timer t(c, GRP_K_VERIFY, r_records);
-      if (c->uniform_weight == 16) {
+      if (long_span(c)) {
+        DISPATCH_H(c->params.h, (k_batch_delta<HH, GRP_WT_LONG><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
+                                                                                                                              reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
+      } else if (c->uniform_weight == 16) {
         DISPATCH_H(c->params.h, (k_batch_delta<HH, 16><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
                                                                                                                      reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
       } else {

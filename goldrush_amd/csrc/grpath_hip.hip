@@ -14,6 +14,9 @@
 //                 (read_hashing.cpp:29-54, goldrush_path.cpp:544-626)
 //   k_insert      hash -> rank -> exact per-call rank dedup -> reservoir rule
 //                 (MIBFConstructSupport.hpp:247-283)
+// Seeds of spans 65 .. 256 bases (DevSeeds::wide == 2, long_span) run their own
+// instantiations of every hashing kernel (WT == GRP_WT_LONG, k_fill_long, k_ntcard_long,
+// k_insert_long, k_debug_tile_hashes_long); the forms of spans up to 64 are untouched.
 #include "grp_device.h"
 #include "host/gr_tiles_core.hpp"
 
@@ -502,12 +505,20 @@ tab_bytes(const grp_ctx* c)
   return (size_t)c->h_seeds.h * c->h_seeds.wmax * 4u * sizeof(ulonglong2);
 }
 
-size_t
+constexpr size_t
 bases_bytes(uint32_t nbases)
 {
   // words covering nbases at any 16-base phase + 2 pad words, rounded to 16 B
   size_t words = (nbases + 15u) / 16u + 1u + 4u;
   return ((words * 4u + 15u) / 16u) * 16u;
+}
+
+// seeds of spans beyond 64 bases (DevSeeds::wide == 2): every hashing kernel runs its long-span form (WT ==
+// GRP_WT_LONG, or the *_long kernels), the only code that reads bases past the 64th of a frame
+inline bool
+long_span(const grp_ctx* c)
+{
+  return c->h_seeds.wide > 1u;
 }
 
 template<typename K>
@@ -576,6 +587,10 @@ template<typename T>
 int ensure_dev(grp_ctx* c, T*& p, uint64_t& cap, uint64_t want);
 
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024 - 512; // gfx950, less the kernels' static shared variables
+// The kernels that stage a fill chunk or one tile beside the seed tables (fill, ntCard, insert, batch records, overlap
+// samples, tile-hash inspection): their LDS grows with the span, and fits at the longest span and tile there are
+static_assert(GRP_DEV_MAX_H * GRP_DEV_MAX_W * 4u * sizeof(ulonglong2) + bases_bytes(GRP_MAX_TILE + GRP_MAX_SPAN + GRP_DEV_MAX_H) <= LDS_PER_WORKGROUP,
+              "a tile of the longest span does not fit the LDS beside the seed tables");
 constexpr uint32_t GT_SLICE = 256;                     // workgroups of one launch with global count tables
 
 struct QueryGeom
@@ -625,12 +640,10 @@ query_geom(const grp_ctx* c, bool full)
   return g;
 }
 
-template<int HH>
+template<int HH, int QWT>
 int
-launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles = nullptr, grp_id_count* out_lists = nullptr, uint32_t direct_stride = 0, const DevStreamCtl* stream_ctl = nullptr,
-             uint32_t blk0 = 0,          // no tile list: the launch covers tiles [blk0, blk0 + n_launch) of the window
-             bool list_flags = false,    // a tile list that is NOT the redo of flagged tiles: flagged tiles are collected as without a list
-             bool plain = false)         // the plain query even while a batch view is set (the reads behind the batch)
+launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles, grp_id_count* out_lists, uint32_t direct_stride, const DevStreamCtl* stream_ctl,
+                uint32_t blk0, bool list_flags, bool plain)
 {
   if (!out_tiles) {
     out_tiles = c->q->d_tiles;
@@ -702,13 +715,13 @@ launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, con
         if (v.redo_count && off) {
           break; // (a launch sized before its list was known covers one slice: longer lists take the host's way)
         }
-        auto kern = k_query<HH, 1, 0, false, true, true>;
+        auto kern = k_query<HH, 1, QWT, false, true, true>;
         if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
           return rc;
         }
         kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr), flag_out, (uint32_t)c->q->d_flag_cap, 0u, b0, DevStreamCtl{}, v, c->d_gtab);
       } else {
-        auto kern = k_query<HH, 1, 0, false, false, true>;
+        auto kern = k_query<HH, 1, QWT, false, false, true>;
         if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
           return rc;
         }
@@ -718,13 +731,13 @@ launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, con
     return GRP_OK;
   }
   if (c->view && !stream_ctl && !plain) { // grp_batch_classify: every read sees the state in front of its own insert
-    return go(k_query<HH, SFR, 0, false, true>);
+    return go(k_query<HH, SFR, QWT, false, true>);
   }
   if (stream_ctl) {
     // persistent workgroups: exactly what is resident at once
     // one frame per lane and pass: fewer registers, more resident workgroups — measured
     // better than two for the persistent form (h = 3: +3 %, h = 5: +19 %)
-    auto kern = k_query<HH, 1, 0, true>;
+    auto kern = k_query<HH, 1, QWT, true>;
     int per_cu = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, THREADS, g.lds));
     // Round 6: a window that applies inserts itself keeps the probes' fingerprints of the tile in progress and of the
@@ -788,7 +801,21 @@ launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, con
   // seeds: 346 VGPRs + 14 spilled at h = 3.  With the shared halves the hash is a third of the
   // instructions it was and the batches took the insert-heavy phases over: the form is gone — the
   // CLI's silver run takes the same time with and without it, tools/dev/r3_latform.sh.)
-  return go(k_query<HH, SFR, 0, false>);
+  return go(k_query<HH, SFR, QWT, false>);
+}
+
+// QWT: the hash form of every k_query the launch may take — 0, or GRP_WT_LONG for seeds of spans beyond 64 bases
+template<int HH>
+int
+launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles = nullptr, grp_id_count* out_lists = nullptr, uint32_t direct_stride = 0, const DevStreamCtl* stream_ctl = nullptr,
+             uint32_t blk0 = 0,          // no tile list: the launch covers tiles [blk0, blk0 + n_launch) of the window
+             bool list_flags = false,    // a tile list that is NOT the redo of flagged tiles: flagged tiles are collected as without a list
+             bool plain = false)         // the plain query even while a batch view is set (the reads behind the batch)
+{
+  if (long_span(c)) {
+    return launch_query_wt<HH, GRP_WT_LONG>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain);
+  }
+  return launch_query_wt<HH, 0>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain);
 }
 
 int
@@ -834,8 +861,10 @@ build_seed_tables(grp_ctx* c)
     }
   }
   // spans beyond 32 bases (round 4): the generic hash reads a second 64-bit window; the unrolled weight-16 form and
-  // the shared halves are 32-base forms and stay off
-  sd.wide = (c->params.k + sd.h - 1 > 32) ? 1u : 0u;
+  // the shared halves are 32-base forms and stay off.  Beyond 64 bases (up to GRP_MAX_SPAN): the long-span
+  // instantiations, which read each care position from the staged bases (long_span, grp_kernels.inc seed_hash_long).
+  const uint32_t span = c->params.k + sd.h - 1;
+  sd.wide = (span > 64) ? 2u : (span > 32) ? 1u : 0u;
   if (sd.wide) {
     c->uniform_weight = 0;
   }
@@ -882,8 +911,8 @@ grp_create(const grp_params* p, grp_ctx** out)
   if (p->h < 1 || p->h > GRP_MAX_SEEDS) {
     return set_err(nullptr, GRP_ERR_INVALID, "h=%u outside [1,%d]", p->h, GRP_MAX_SEEDS);
   }
-  if (p->k < 1 || p->k + p->h - 1 > GRP_MAX_SPAN) {
-    return set_err(nullptr, GRP_ERR_INVALID, "k+h-1=%u exceeds the %d-base window of this implementation", p->k + p->h - 1, GRP_MAX_SPAN);
+  if (p->k < 1 || p->k > GRP_MAX_SPAN || p->k + p->h - 1 > GRP_MAX_SPAN) {
+    return set_err(nullptr, GRP_ERR_INVALID, "k=%u h=%u: the longest seed spans k+h-1=%u bases, this implementation supports spans of 1 to %d bases", p->k, p->h, p->k + p->h - 1, GRP_MAX_SPAN);
   }
   if (p->tile < p->k + p->h - 1) {
     return set_err(nullptr, GRP_ERR_INVALID, "tile length %u shorter than the longest seed span %u", p->tile, p->k + p->h - 1);
@@ -1556,7 +1585,11 @@ grp_bv_insert(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
   for (uint64_t b = ch0; b < ch1;) {
     uint32_t nb = (uint32_t)std::min<uint64_t>(ch1 - b, MAX_GRID_WGS);
     Timer t(c, GRP_K_FILL, b == ch0 ? probes : 0);
-    DISPATCH_H(c->params.h, (k_fill<HH><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
+    if (long_span(c)) {
+      DISPATCH_H(c->params.h, (k_fill_long<HH><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
+    } else {
+      DISPATCH_H(c->params.h, (k_fill<HH><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
+    }
     HIP_TRY(c, hipGetLastError());
     b += nb;
   }
@@ -2997,7 +3030,11 @@ grp_insert_tiles(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t til
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
-    DISPATCH_H(c->params.h, (k_insert<HH><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+    if (long_span(c)) {
+      DISPATCH_H(c->params.h, (k_insert_long<HH><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+    } else {
+      DISPATCH_H(c->params.h, (k_insert<HH><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+    }
   }
   HIP_TRY(c, hipGetLastError());
   return GRP_OK;
@@ -3048,7 +3085,9 @@ grp_insert_read(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t tile
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
-    if (c->uniform_weight == 16) { // make_seed_pattern's default weight: care loop unrolled (the launch is latency-bound)
+    if (long_span(c)) {
+      DISPATCH_H(c->params.h, (k_insert_collect<HH, GRP_WT_LONG><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
+    } else if (c->uniform_weight == 16) { // make_seed_pattern's default weight: care loop unrolled (the launch is latency-bound)
       DISPATCH_H(c->params.h, (k_insert_collect<HH, 16><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
     } else {
       DISPATCH_H(c->params.h, (k_insert_collect<HH, 0><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
@@ -3235,7 +3274,11 @@ grp_debug_tile_hashes(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_
   uint64_t* d = nullptr;
   HIP_TRY(c, hipMalloc(&d, nv * 8));
   const size_t lds = tab_bytes(c) + bases_bytes(tile + k + c->params.h);
-  DISPATCH_H(c->params.h, (k_debug_tile_hashes<HH><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
+  if (long_span(c)) {
+    DISPATCH_H(c->params.h, (k_debug_tile_hashes_long<HH><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
+  } else {
+    DISPATCH_H(c->params.h, (k_debug_tile_hashes<HH><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
+  }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, d, nv * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

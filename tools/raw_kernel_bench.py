@@ -20,11 +20,23 @@ def main():
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--populate", type=int, default=4000, help="reads inserted as IDs before querying")
     ap.add_argument("--qbatches", type=int, default=8)
+    ap.add_argument("--k", type=int, default=22, help="span of the base seed (k + h - 1 up to 256)")
+    ap.add_argument("--w", type=int, default=16, help="weight of the seed (with --k other than 22 and no --preset: a preset is drawn)")
+    ap.add_argument("--preset", default=None, help="seed preset of span k (default: the pipeline's 22-base preset at k = 22)")
     a = ap.parse_args()
     G = int(a.genome)
-    k, w, tile = 22, 16, 1000
-    preset = "1011011110110111101101"
-    seeds = [preset[:11] + "0" * i + preset[11:] for i in range(a.h)]
+    k, w, tile = a.k, a.w, 1000
+    preset = a.preset
+    if preset is None:
+        if k == 22 and w == 16:
+            preset = "1011011110110111101101"
+        else:  # care positions at both ends, the rest drawn
+            care = np.zeros(k, dtype=bool)
+            care[0] = care[-1] = True
+            care[np.random.default_rng(k).choice(np.arange(1, k - 1), size=w - 2, replace=False)] = True
+            preset = "".join("1" if c else "0" for c in care)
+    assert len(preset) == k and preset.count("1") == w
+    seeds = [preset[:k // 2] + "0" * i + preset[k // 2:] for i in range(a.h)]
     U = int(np.float32(min(4 ** w, 2 * G)) * np.float32(0.5) * np.float32(a.h))
     n = int(-float(U) / np.log(1.0 - 0.1))
     m = n + (64 - n % 64)
@@ -37,6 +49,7 @@ def main():
     eng.bv_insert(rb)
     eng.sync()
     t_fill = time.time() - t
+    ks_fill = eng.kernel_stats()["fill"]
     t = time.time()
     pop = eng.finalize()
     t_fin = time.time() - t
@@ -66,7 +79,9 @@ def main():
     gbps = q["units"] * 128 / (q["ms"] * 1e-3) / 1e9
     out = {"reads_per_s_wall": nq / wall, "reads_per_s_kernel": nq / (q["ms"] * 1e-3), "query_ms_per_launch": q["ms"] / q["launches"],
            "probes_per_launch": q["units"] / q["launches"], "GBps_128B_per_probe": gbps, "frac_of_8TBps": gbps / 8000,
-           "hit_frac": hits / max(q["units"], 1), "fill_s": t_fill, "fill_Gprobes_per_s": ks["fill"]["units"] / max(t_fill, 1e-9) / 1e9 if ks["fill"]["units"] else None}
+           "hit_frac": hits / max(q["units"], 1), "fill_s": t_fill, "fill_Gprobes_per_s": ks_fill["units"] / max(t_fill, 1e-9) / 1e9 if ks_fill["units"] else None,
+           "fill_Gprobes_per_s_kernel": ks_fill["units"] / (ks_fill["ms"] * 1e-3) / 1e9 if ks_fill["units"] and ks_fill["ms"] else None,
+           "query_Gprobes_per_s_kernel": q["units"] / (q["ms"] * 1e-3) / 1e9, "k": k, "w": w, "h": a.h, "span": k + a.h - 1}
     ks_all = eng.kernel_stats()
     print(json.dumps(out))
     print(json.dumps(ks_all))
