@@ -125,11 +125,12 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd); // (one seed per workgroup: the many-seed form differs in its strides only)
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint32_t gunit = gunit0 + blockIdx.x;
-  const uint32_t unit = gunit / (uint32_t)H;
-  const uint32_t s = gunit - unit * (uint32_t)H;
+  const uint32_t unit = gunit / hn;
+  const uint32_t s = gunit - unit * hn;
   const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
   const uint32_t jb = batch_unit_jb(b, unit, parts);
   const uint32_t* e = b.ins + (size_t)(jb >> 8) * 6;
@@ -200,7 +201,7 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
     for (;;) {
       if (grp_claim_epoch(cur) == b.epoch) { // a rank of this batch already: whose
         const uint32_t owner = grp_claim_record(cur);
-        const uint32_t owner_unit = owner / ((uint32_t)H * THREADS);
+        const uint32_t owner_unit = owner / (hn * THREADS);
         why = owner + 2u;
         // the same unit is the same (read, block): one dedup scope, one touch
         if (owner_unit < blk_unit0 || owner_unit >= blk_unit1) {

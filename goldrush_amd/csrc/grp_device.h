@@ -36,7 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define GRP_DEV_MAX_H 8
+#define GRP_DEV_MAX_H 16
 #define GRP_DEV_MAX_W 32
 #define GRP_BUCKET_IDS 13u
 #define GRP_NEAR_CW 8u           /* count words in the unit's insert line */
@@ -54,7 +54,8 @@ struct DevSeeds
   // Seeds built by make_seed_pattern (spaced_seeds.cpp:58-66) are seed 0 with i don't-care
   // positions inserted at the centre: seed i = left || 0^i || right.  n_left > 0 says so (the
   // number of care positions of the left part): the H hashes of a frame then share their halves
-  // (grp_kernels.inc, seed_halves), 16 table look-ups per frame instead of 16 per seed.
+  // (grp_kernels.inc, seed_halves), 16 table look-ups per frame instead of 16 per seed.  Only the query forms of h <= 8
+  // use it: the many-seed form (h = 9 .. 16, grp_kernels.inc frame_seeds) hashes every seed on its own.
   uint32_t n_left;
   uint32_t wide; // 1: the longest span exceeds 32 bases (k + h - 1 <= 64): hashes read a 128-bit window (grp_kernels.inc, seed_hash);
                  // 2: it exceeds 64 (k + h - 1 <= 256): only the long-span kernels run, which read each care position on its own (seed_hash_long)

@@ -71,6 +71,34 @@ seed_hash(const ulonglong2* sTab, const DevSeeds* __restrict__ sd, uint32_t s, c
 // spans up to 64 keep their code.
 constexpr int GRP_WT_LONG = -1;
 
+// The seeds of a frame.  Every kernel that hashes a frame's seeds is compiled once per h up to GRP_H_GROUP (H = h: the
+// seed loops unroll to exactly h); h = 9 .. 16 share ONE many-seed form (H = GRP_H_MANY), whose loops run over 16 seeds
+// and drop the seeds >= sd->h at run time (a wave-uniform test).  Its per-lane arrays are sized for 16 seeds: where
+// that would not fit the registers (the query's bucket lines, the fill's frames in flight) the form walks a frame's
+// seeds in groups of GRP_H_GROUP, or keeps fewer frames in flight.
+constexpr int GRP_H_GROUP = 8;
+constexpr int GRP_H_MANY = 16;
+static_assert(GRP_H_MANY == GRP_DEV_MAX_H && GRP_H_MANY <= 2 * GRP_H_GROUP, "the many-seed form covers the device tables in two groups");
+
+template<int H>
+__device__ __forceinline__ uint32_t
+frame_seeds(const DevSeeds* __restrict__ sd)
+{
+  if constexpr (H <= GRP_H_GROUP) {
+    return (uint32_t)H;
+  } else {
+    return sd->h;
+  }
+}
+
+// seed s takes part in a frame of this form (always true, and folded away, in the forms of h <= GRP_H_GROUP)
+template<int H>
+__device__ __forceinline__ bool
+seed_on(int s, uint32_t hn)
+{
+  return H <= GRP_H_GROUP || (uint32_t)s < hn;
+}
+
 // seed_hash for spans beyond 64 bases: each care position's 2-bit base is read from the staged words
 // (one LDS dword per care position; a base never straddles two words).  No window is built — a per-lane array
 // of the span would live in scratch — and every position read lies inside the seed's span, so inside the bases
@@ -166,23 +194,24 @@ k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint64_t chunk = chunk_begin + blockIdx.x;
   const uint32_t r = rd.chunk_read[chunk];
   const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
   const uint32_t len = rd.len[r];
   const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + H - 1
+  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + h - 1
   const uint32_t p0 = ci * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
   __syncthreads();
 
   uint32_t* words = f.bv;
-  constexpr int FR = 4;
+  constexpr int FR = (H <= GRP_H_GROUP) ? 4 : 2; // the many-seed form: 2 x 16 probes in flight per lane (4 x 16 spill)
   for (uint32_t i0 = threadIdx.x; i0 < np; i0 += THREADS * FR) {
     uint64_t widx[FR][H];
     uint32_t mask[FR][H];
@@ -195,7 +224,7 @@ k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk
       for (int s = 0; s < H; ++s) {
         // seed s is valid at read position p iff p + span_s <= len
         // (stale re-inserts of the iterator set the same bit again)
-        const bool ok = (i < np) && (p + sd->span[s] <= len);
+        const bool ok = seed_on<H>(s, hn) && (i < np) && (p + sd->span[s] <= len);
         mask[j][s] = 0;
         widx[j][s] = 0;
         if (ok) {
@@ -236,23 +265,24 @@ k_fill_long(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t 
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint64_t chunk = chunk_begin + blockIdx.x;
   const uint32_t r = rd.chunk_read[chunk];
   const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
   const uint32_t len = rd.len[r];
   const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + H - 1
+  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + h - 1
   const uint32_t p0 = ci * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
   __syncthreads();
 
   uint32_t* words = f.bv;
-  constexpr int FR = 4;
+  constexpr int FR = (H <= GRP_H_GROUP) ? 4 : 2; // the many-seed form: 2 x 16 probes in flight per lane (4 x 16 spill)
   for (uint32_t i0 = threadIdx.x; i0 < np; i0 += THREADS * FR) {
     uint64_t widx[FR][H];
     uint32_t mask[FR][H];
@@ -265,7 +295,7 @@ k_fill_long(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t 
       for (int s = 0; s < H; ++s) {
         // seed s is valid at read position p iff p + span_s <= len
         // (stale re-inserts of the iterator set the same bit again)
-        const bool ok = (i < np) && (p + sd->span[s] <= len);
+        const bool ok = seed_on<H>(s, hn) && (i < np) && (p + sd->span[s] <= len);
         mask[j][s] = 0;
         widx[j][s] = 0;
         if (ok) {
@@ -1542,6 +1572,7 @@ insert_collect_unit(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
 
   const uint32_t fr = part * THREADS + threadIdx.x;
   const bool live = fr < frames;
+  const uint32_t hn = frame_seeds<H>(sd);
   uint32_t my_slot[H];
   bool my_claim[H];
   uint32_t n_claimed = 0;
@@ -1553,6 +1584,10 @@ insert_collect_unit(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
     // profiles/r03_collect3_hunt.txt.  This kernel never showed it, but it had the same shape.)
 #pragma unroll
     for (int s = 0; s < H; ++s) {
+      if (!seed_on<H>(s, hn)) {
+        my_claim[s] = false;
+        continue;
+      }
       Probe pr[H];
       uint4 hd[H];
       {
@@ -2275,15 +2310,16 @@ k_query(DevFilter f,
   // GT (round 5): the worst-case table of a geometry whose tile x h IDs do not fit the LDS (tiles beyond ~9 000 frames at h = 3)
   // lives in a slice of a global scratch area — only the redo of the tiles the first step's LDS-sized table could not hold
   // runs this form: same arithmetic, atomics at the L2 instead of the LDS
+  const uint32_t hn = frame_seeds<H>(sd);
   uint32_t* sKeys;
   uint32_t* sCnts;
   uint32_t* sBases;
   if constexpr (GT) {
     sKeys = gtab + (size_t)blockIdx.x * (hist_cap + hist_cap / 2u);
     sCnts = sKeys + hist_cap;
-    sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+    sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
   } else {
-    sKeys = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+    sKeys = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
     sCnts = sKeys + hist_cap; // 16-bit counts, two per word
     sBases = sCnts + hist_cap / 2u;
   }
@@ -2592,7 +2628,7 @@ k_query(DevFilter f,
   __syncthreads();
   if constexpr (ST) {
     if (threadIdx.x == 0) {
-      atomicAdd(sc.executed, (unsigned long long)frames * H);
+      atomicAdd(sc.executed, (unsigned long long)frames * hn);
     }
   }
   uint32_t* const fp_cur = (ST && sFp != nullptr) ? sFp + sBuf * sc.fp_words : nullptr; // (sBuf is final behind the barrier above)
@@ -2622,7 +2658,8 @@ k_query(DevFilter f,
   // Where the helper lanes would cost a pass (h = 5: 244 frames per block, a 1000-frame tile
   // would need 5 passes instead of 4) every wave's last lanes evaluate their neighbours' right
   // halves themselves instead (256 frames per block, H - 1 extra half evaluations per wave).
-  const uint32_t n_left = (H >= 2 && WT != GRP_WT_LONG) ? sd->n_left : 0u; // (0 for long spans: the halves are a 32-base form)
+  const uint32_t n_left = (H >= 2 && H <= GRP_H_GROUP && WT != GRP_WT_LONG) ? sd->n_left : 0u; // (0 for long spans: the halves are a 32-base form;
+                                                                                                 // 0 in the many-seed form: every seed hashed on its own)
   constexpr uint32_t OV = (uint32_t)H - 1u, USE = 64u - OV;
   static_assert(THREADS == 256, "the helper-lane layout below is written for four waves per workgroup (my_wave == 3 is the last one, FBH = 3 * USE + 64)");
   constexpr uint32_t FBH = 3u * USE + 64u;
@@ -2689,6 +2726,16 @@ k_query(DevFilter f,
       lv[j] = fr_raw < frames;
 #pragma unroll
       for (int s = 0; s < H; ++s) {
+        if (!seed_on<H>(s, frame_seeds<H>(sd))) {
+          bk_[j][s] = 0;
+          off_[j][s] = 0;
+          if constexpr (ST) {
+            if (fp_cur != nullptr) {
+              fp_cur[((pp * FR + (uint32_t)j) * (uint32_t)THREADS + threadIdx.x) * (uint32_t)H + (uint32_t)s] = 0u;
+            }
+          }
+          continue;
+        }
         const uint64_t hv = seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + min(fr, last[s])));
         const Probe p = grp_locate(f, hv);
         bk_[j][s] = p.b;
@@ -2704,7 +2751,9 @@ k_query(DevFilter f,
   };
   // (only the persistent form: with two frames per lane the second set of positions costs the
   // synchronous forms a wave of occupancy — 169 VGPRs — and their rate, measured)
-  constexpr bool PIPE = ST || FR == 1;
+  // (the many-seed form computes a pass's positions in front of its loads: 16 probes per lane are latency enough, and the
+  // persistent form has no registers left for a second set — measured: 512 VGPRs and 24 spilled with it)
+  constexpr bool PIPE = (ST || FR == 1) && H <= GRP_H_GROUP;
   if constexpr (PIPE) {
     if (passes > 0u) {
       positions(0u, bk, off, live_j);
@@ -2727,98 +2776,192 @@ k_query(DevFilter f,
         }
       }
     }
-    uint4 piece[FR][H][4];
-    if constexpr (!PIPE) {
+    if constexpr (H <= GRP_H_GROUP) {
+      uint4 piece[FR][H][4];
+      if constexpr (!PIPE) {
+        positions(pass, bk, off, live_j);
+      }
+      // 2) round g: the quad reads the bucket of its lane g's probe
+#pragma unroll
+      for (int j = 0; j < FR; ++j) {
+#pragma unroll
+        for (int s = 0; s < H; ++s) {
+          piece[j][s][0] = f.buckets[quad_bcast64<0>(bk[j][s]) * GRP_UNIT_U4 + sub];
+          piece[j][s][1] = f.buckets[quad_bcast64<1>(bk[j][s]) * GRP_UNIT_U4 + sub];
+          piece[j][s][2] = f.buckets[quad_bcast64<2>(bk[j][s]) * GRP_UNIT_U4 + sub];
+          piece[j][s][3] = f.buckets[quad_bcast64<3>(bk[j][s]) * GRP_UNIT_U4 + sub];
+        }
+      }
+      uint64_t bk_next[PIPE ? FR : 1][PIPE ? H : 1];
+      uint32_t off_next[PIPE ? FR : 1][PIPE ? H : 1];
+      bool live_next[PIPE ? FR : 1];
+      if constexpr (PIPE) {
+        if (pass + 1u < passes) {
+          positions(pass + 1u, bk_next, off_next, live_next);
+        }
+      }
+      // 3) bit test + ID slot, exchanged inside the quad; per-frame ID set -> tile count table
+#pragma unroll
+      for (int j = 0; j < FR; ++j) {
+        const bool live = live_j[j];
+        bool all = live;
+        uint32_t idv[H];
+        uint64_t vrank[VER ? H : 1], vbl[VER ? H : 1];
+        bool vneed[VER ? H : 1], vamb[VER ? H : 1];
+#pragma unroll
+        for (int s = 0; s < H; ++s) {
+          QuadAnswer a0 = quad_answer<0>(piece[j][s][0], off[j][s], quad_base);
+          QuadAnswer a1 = quad_answer<1>(piece[j][s][1], off[j][s], quad_base);
+          QuadAnswer a2 = quad_answer<2>(piece[j][s][2], off[j][s], quad_base);
+          QuadAnswer a3 = quad_answer<3>(piece[j][s][3], off[j][s], quad_base);
+          const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+          all = all && mine.bit; // atRank (MIBloomFilter.hpp:465-476)
+          uint32_t d = mine.id;  // getData (:614-621)
+
+          if (mine.lr >= GRP_BUCKET_IDS && live) { // 14th.. set bit of its bucket: rare side table
+            d = grp_ovf_get(f, f.super[bk[j][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr);
+          }
+          if constexpr (VER) {
+            const uint32_t fl = bv.floor[r - bv.floor_first]; // bit 31: an ID equal to the floor may have been written in front of this read
+            const uint32_t floor_id = fl & 0x7FFFFFFFu;
+            vrank[s] = f.super[bk[j][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr;
+            vbl[s] = bk[j][s] * 64ull + mine.lr;
+            vneed[s] = live && mine.bit && (d & 0x7FFFFFFFu) >= floor_id; // written by this or a later read of the batch
+            vamb[s] = (fl >> 31) != 0u && (d & 0x7FFFFFFFu) == floor_id;
+          }
+          idv[s] = d;
+        }
+        if (!all) {
+          continue; // (a frame with a clear bit counts nothing: its IDs need not be looked up)
+        }
+        if constexpr (VER) {
+          // every read sees the state in front of its own insert: the IDs this batch wrote are looked up
+          batch_view_multi<H>(bv, vrank, vbl, vneed, vamb, r - bv.first, idv);
+        }
+        uint32_t ids[H];
+#pragma unroll
+        for (int s = 0; s < H; ++s) {
+          const uint32_t d = idv[s];
+          // saturation bit stripped exactly as goldrush_path.cpp:573-594
+          const uint32_t id = (d > 0x80000000u) ? (d & 0x7FFFFFFFu) : d;
+          if (id == 0u) {
+            ++n_miss;
+          } else {
+            ++n_hit;
+          }
+          bool dup = false;
+#pragma unroll
+          for (int u = 0; u < s; ++u) {
+            dup = dup || (ids[u] == id);
+          }
+          ids[s] = id;
+          if (id != 0u && !dup) {
+            hist_add16(sKeys, sCnts, hist_cap, id, &sDistinct, distinct_limit, &sOverflow);
+          }
+        }
+      }
+      if constexpr (PIPE) {
+        if (pass + 1u < passes) {
+#pragma unroll
+          for (int j = 0; j < FR; ++j) {
+            live_j[j] = live_next[j];
+#pragma unroll
+            for (int s = 0; s < H; ++s) {
+              bk[j][s] = bk_next[j][s];
+              off[j][s] = off_next[j][s];
+            }
+          }
+        }
+      }
+    } else {
+      // The many-seed form (h = 9 .. 16; one frame per lane): the bucket lines of 16 probes x 4 quad pieces would take
+      // 256 VGPRs, so the frame's seeds go in two groups of GRP_H_GROUP — a group's lines are read, answered and
+      // dropped before the next group's are read.  The FRAME stays one unit across the groups: its hit flag (all h
+      // bits set, MIBloomFilter::atRank) and its IDs are collected over both, then counted and de-duplicated over all
+      // h probes at once, as below for h <= 8.
+      static_assert(FR == 1 && !PIPE, "the many-seed form runs one frame per lane and pass");
+      constexpr int NG = (H + GRP_H_GROUP - 1) / GRP_H_GROUP;
       positions(pass, bk, off, live_j);
-    }
-    // 2) round g: the quad reads the bucket of its lane g's probe
-#pragma unroll
-    for (int j = 0; j < FR; ++j) {
-#pragma unroll
-      for (int s = 0; s < H; ++s) {
-        piece[j][s][0] = f.buckets[quad_bcast64<0>(bk[j][s]) * GRP_UNIT_U4 + sub];
-        piece[j][s][1] = f.buckets[quad_bcast64<1>(bk[j][s]) * GRP_UNIT_U4 + sub];
-        piece[j][s][2] = f.buckets[quad_bcast64<2>(bk[j][s]) * GRP_UNIT_U4 + sub];
-        piece[j][s][3] = f.buckets[quad_bcast64<3>(bk[j][s]) * GRP_UNIT_U4 + sub];
-      }
-    }
-    uint64_t bk_next[PIPE ? FR : 1][PIPE ? H : 1];
-    uint32_t off_next[PIPE ? FR : 1][PIPE ? H : 1];
-    bool live_next[PIPE ? FR : 1];
-    if constexpr (PIPE) {
-      if (pass + 1u < passes) {
-        positions(pass + 1u, bk_next, off_next, live_next);
-      }
-    }
-    // 3) bit test + ID slot, exchanged inside the quad; per-frame ID set -> tile count table
-#pragma unroll
-    for (int j = 0; j < FR; ++j) {
-      const bool live = live_j[j];
+      const bool live = live_j[0];
       bool all = live;
       uint32_t idv[H];
       uint64_t vrank[VER ? H : 1], vbl[VER ? H : 1];
       bool vneed[VER ? H : 1], vamb[VER ? H : 1];
 #pragma unroll
       for (int s = 0; s < H; ++s) {
-        QuadAnswer a0 = quad_answer<0>(piece[j][s][0], off[j][s], quad_base);
-        QuadAnswer a1 = quad_answer<1>(piece[j][s][1], off[j][s], quad_base);
-        QuadAnswer a2 = quad_answer<2>(piece[j][s][2], off[j][s], quad_base);
-        QuadAnswer a3 = quad_answer<3>(piece[j][s][3], off[j][s], quad_base);
-        const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
-        all = all && mine.bit; // atRank (MIBloomFilter.hpp:465-476)
-        uint32_t d = mine.id;  // getData (:614-621)
-
-        if (mine.lr >= GRP_BUCKET_IDS && live) { // 14th.. set bit of its bucket: rare side table
-          d = grp_ovf_get(f, f.super[bk[j][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr);
-        }
+        idv[s] = 0u;
         if constexpr (VER) {
-          const uint32_t fl = bv.floor[r - bv.floor_first]; // bit 31: an ID equal to the floor may have been written in front of this read
-          const uint32_t floor_id = fl & 0x7FFFFFFFu;
-          vrank[s] = f.super[bk[j][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr;
-          vbl[s] = bk[j][s] * 64ull + mine.lr;
-          vneed[s] = live && mine.bit && (d & 0x7FFFFFFFu) >= floor_id; // written by this or a later read of the batch
-          vamb[s] = (fl >> 31) != 0u && (d & 0x7FFFFFFFu) == floor_id;
-        }
-        idv[s] = d;
-      }
-      if (!all) {
-        continue; // (a frame with a clear bit counts nothing: its IDs need not be looked up)
-      }
-      if constexpr (VER) {
-        // every read sees the state in front of its own insert: the IDs this batch wrote are looked up
-        batch_view_multi<H>(bv, vrank, vbl, vneed, vamb, r - bv.first, idv);
-      }
-      uint32_t ids[H];
-#pragma unroll
-      for (int s = 0; s < H; ++s) {
-        const uint32_t d = idv[s];
-        // saturation bit stripped exactly as goldrush_path.cpp:573-594
-        const uint32_t id = (d > 0x80000000u) ? (d & 0x7FFFFFFFu) : d;
-        if (id == 0u) {
-          ++n_miss;
-        } else {
-          ++n_hit;
-        }
-        bool dup = false;
-#pragma unroll
-        for (int u = 0; u < s; ++u) {
-          dup = dup || (ids[u] == id);
-        }
-        ids[s] = id;
-        if (id != 0u && !dup) {
-          hist_add16(sKeys, sCnts, hist_cap, id, &sDistinct, distinct_limit, &sOverflow);
+          vrank[s] = 0;
+          vbl[s] = 0;
+          vneed[s] = false;
+          vamb[s] = false;
         }
       }
-    }
-    if constexpr (PIPE) {
-      if (pass + 1u < passes) {
 #pragma unroll
-        for (int j = 0; j < FR; ++j) {
-          live_j[j] = live_next[j];
+      for (int gi = 0; gi < NG; ++gi) {
+        uint4 piece[GRP_H_GROUP][4];
 #pragma unroll
-          for (int s = 0; s < H; ++s) {
-            bk[j][s] = bk_next[j][s];
-            off[j][s] = off_next[j][s];
+        for (int q = 0; q < GRP_H_GROUP; ++q) {
+          const int s = gi * GRP_H_GROUP + q;
+          if (seed_on<H>(s, hn)) {
+            piece[q][0] = f.buckets[quad_bcast64<0>(bk[0][s]) * GRP_UNIT_U4 + sub];
+            piece[q][1] = f.buckets[quad_bcast64<1>(bk[0][s]) * GRP_UNIT_U4 + sub];
+            piece[q][2] = f.buckets[quad_bcast64<2>(bk[0][s]) * GRP_UNIT_U4 + sub];
+            piece[q][3] = f.buckets[quad_bcast64<3>(bk[0][s]) * GRP_UNIT_U4 + sub];
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < GRP_H_GROUP; ++q) {
+          const int s = gi * GRP_H_GROUP + q;
+          if (!seed_on<H>(s, hn)) {
+            continue;
+          }
+          QuadAnswer a0 = quad_answer<0>(piece[q][0], off[0][s], quad_base);
+          QuadAnswer a1 = quad_answer<1>(piece[q][1], off[0][s], quad_base);
+          QuadAnswer a2 = quad_answer<2>(piece[q][2], off[0][s], quad_base);
+          QuadAnswer a3 = quad_answer<3>(piece[q][3], off[0][s], quad_base);
+          const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+          all = all && mine.bit; // atRank (MIBloomFilter.hpp:465-476): over all h seeds of the frame
+          uint32_t d = mine.id;  // getData (:614-621)
+          if (mine.lr >= GRP_BUCKET_IDS && live) {
+            d = grp_ovf_get(f, f.super[bk[0][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr);
+          }
+          if constexpr (VER) {
+            const uint32_t fl = bv.floor[r - bv.floor_first];
+            const uint32_t floor_id = fl & 0x7FFFFFFFu;
+            vrank[s] = f.super[bk[0][s] >> GRP_SUPER_SHIFT] + mine.rel + mine.lr;
+            vbl[s] = bk[0][s] * 64ull + mine.lr;
+            vneed[s] = live && mine.bit && (d & 0x7FFFFFFFu) >= floor_id;
+            vamb[s] = (fl >> 31) != 0u && (d & 0x7FFFFFFFu) == floor_id;
+          }
+          idv[s] = d;
+        }
+      }
+      if (all) {
+        if constexpr (VER) {
+          batch_view_multi<H>(bv, vrank, vbl, vneed, vamb, r - bv.first, idv);
+        }
+        uint32_t ids[H];
+#pragma unroll
+        for (int s = 0; s < H; ++s) {
+          if (!seed_on<H>(s, hn)) {
+            continue;
+          }
+          const uint32_t d = idv[s];
+          const uint32_t id = (d > 0x80000000u) ? (d & 0x7FFFFFFFu) : d; // goldrush_path.cpp:573-594
+          if (id == 0u) {
+            ++n_miss;
+          } else {
+            ++n_hit;
+          }
+          bool dup = false; // the frame's IDs de-duplicated over all h probes, both groups
+#pragma unroll
+          for (int u = 0; u < s; ++u) {
+            dup = dup || (ids[u] == id);
+          }
+          ids[s] = id;
+          if (id != 0u && !dup) {
+            hist_add16(sKeys, sCnts, hist_cap, id, &sDistinct, distinct_limit, &sOverflow);
           }
         }
       }
@@ -3169,7 +3312,8 @@ insert_tiles(const DevFilter& f,
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint32_t r = read_idx;
   // one frame per thread: `parts` workgroups share a tile
@@ -3191,15 +3335,22 @@ insert_tiles(const DevFilter& f,
     uint4 hd[H];
 #pragma unroll
     for (int s = 0; s < H; ++s) {
-      const uint32_t fs = min(fr, Lp - sd->span[s]);
-      pr[s] = grp_locate(f, seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs)));
+      if (seed_on<H>(s, hn)) {
+        const uint32_t fs = min(fr, Lp - sd->span[s]);
+        pr[s] = grp_locate(f, seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs)));
+      }
     }
 #pragma unroll
     for (int s = 0; s < H; ++s) {
-      hd[s] = f.buckets[pr[s].b * GRP_UNIT_U4];
+      if (seed_on<H>(s, hn)) {
+        hd[s] = f.buckets[pr[s].b * GRP_UNIT_U4];
+      }
     }
 #pragma unroll
     for (int s = 0; s < H; ++s) {
+      if (!seed_on<H>(s, hn)) {
+        continue;
+      }
       // getRankPos (MIBloomFilter.hpp:488-491): rank only, the bit is not tested
       const uint32_t lr = grp_local_rank(grp_bitmap(hd[s]), pr[s].off);
       const uint64_t rank = f.super[pr[s].b >> GRP_SUPER_SHIFT] + hd[s].x + lr;
@@ -3280,7 +3431,7 @@ k_insert_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + frame_seeds<H>(sd) * sd->wmax * 4u);
   __shared__ uint32_t sWave[THREADS / 64 + 1];
   load_tab(sTab, sd);
   insert_collect_unit<H, WT, false>(f, rd, sd, sTab, sBases, sWave, tile_len, read_idx, tile_start, block_tiles, tb, &tb.counter[parity], blockIdx.x);
@@ -3407,7 +3558,8 @@ debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t 
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
   const uint32_t len = rd.len[read_idx];
   const uint32_t k = sd->k;
   const uint32_t start = tile_idx * tile_len;
@@ -3419,9 +3571,12 @@ debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t 
   for (uint32_t fr = threadIdx.x; fr < frames; fr += THREADS) {
 #pragma unroll
     for (int s = 0; s < H; ++s) {
+      if (!seed_on<H>(s, hn)) {
+        continue;
+      }
       const uint32_t fs = min(fr, Lp - sd->span[s]);
       uint64_t hv = seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs));
-      uint64_t o = (uint64_t)fr * H + s;
+      uint64_t o = (uint64_t)fr * hn + s;
       if (o < cap) {
         out[o] = hv;
       }

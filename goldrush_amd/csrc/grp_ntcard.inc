@@ -21,14 +21,15 @@ __global__ void __launch_bounds__(THREADS)
 k_ntcard(DevReads rd,
          const DevSeeds* __restrict__ sd,
          const uint2* __restrict__ chunks, // (read, chunk index inside the read)
-         const uint32_t* __restrict__ extra, // [read - first][H] stale repeats of the last window, or nullptr
+         const uint32_t* __restrict__ extra, // [read - first][h] stale repeats of the last window, or nullptr
          uint32_t first,
          uint32_t* __restrict__ counters,
          uint32_t sbits)
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint2 ck = chunks[blockIdx.x];
   const uint32_t r = ck.x;
@@ -39,7 +40,7 @@ k_ntcard(DevReads rd,
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
   __syncthreads();
 
   const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
@@ -48,6 +49,9 @@ k_ntcard(DevReads rd,
     const Win w = window_at(sBases, boff + i);
 #pragma unroll
     for (int s = 0; s < H; ++s) {
+      if (!seed_on<H>(s, hn)) {
+        continue;
+      }
       const uint32_t span = sd->span[s];
       if (p + span > len) {
         continue; // no window of seed s starts here
@@ -66,7 +70,7 @@ k_ntcard(DevReads rd,
         // span_s - k frames for a plain read, or what the host computed
         uint32_t times = 1u;
         if (p + span == len) {
-          times += extra ? extra[(size_t)(r - first) * H + s] : (span - k);
+          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - k);
         }
         const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
         atomicAdd(&counters[slot], times);
@@ -82,14 +86,15 @@ __global__ void __launch_bounds__(THREADS)
 k_ntcard_long(DevReads rd,
               const DevSeeds* __restrict__ sd,
               const uint2* __restrict__ chunks, // (read, chunk index inside the read)
-              const uint32_t* __restrict__ extra, // [read - first][H] stale repeats of the last window, or nullptr
+              const uint32_t* __restrict__ extra, // [read - first][h] stale repeats of the last window, or nullptr
               uint32_t first,
               uint32_t* __restrict__ counters,
               uint32_t sbits)
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
 
   const uint2 ck = chunks[blockIdx.x];
   const uint32_t r = ck.x;
@@ -100,7 +105,7 @@ k_ntcard_long(DevReads rd,
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + H - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
   __syncthreads();
 
   const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
@@ -109,6 +114,9 @@ k_ntcard_long(DevReads rd,
     const Win w = window_at(sBases, boff + i);
 #pragma unroll
     for (int s = 0; s < H; ++s) {
+      if (!seed_on<H>(s, hn)) {
+        continue;
+      }
       const uint32_t span = sd->span[s];
       if (p + span > len) {
         continue; // no window of seed s starts here
@@ -127,7 +135,7 @@ k_ntcard_long(DevReads rd,
         // span_s - k frames for a plain read, or what the host computed
         uint32_t times = 1u;
         if (p + span == len) {
-          times += extra ? extra[(size_t)(r - first) * H + s] : (span - k);
+          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - k);
         }
         const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
         atomicAdd(&counters[slot], times);

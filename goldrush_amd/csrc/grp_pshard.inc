@@ -379,6 +379,9 @@ grp_debug_touch_filter(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t 
   if (long_span(c)) {
     return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
   }
+  if (c->params.h > GRP_H_GROUP) {
+    return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype hashes up to %d seeds per frame only (h=%u)", GRP_H_GROUP, c->params.h);
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t H = c->params.h, tile = c->params.tile;
   const uint64_t t0 = r->tile0[first];
@@ -411,9 +414,9 @@ grp_debug_touch_filter(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t 
     HIP_TRY(c, hipMemsetAsync(d_dirty, 0, 8, c->stream));
     HIP_TRY(c, hipEventRecord(e0, c->stream));
     if (c->uniform_weight == 16) {
-      DISPATCH_H(H, (k_touch_probe<HH, 16><<<dim3((uint32_t)nt), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, d_table, (uint32_t)(n_words - 1), n_hash, d_dirty)));
+      DISPATCH_H_FEW(H, (k_touch_probe<HH, 16><<<dim3((uint32_t)nt), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, d_table, (uint32_t)(n_words - 1), n_hash, d_dirty)));
     } else {
-      DISPATCH_H(H, (k_touch_probe<HH, 0><<<dim3((uint32_t)nt), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, d_table, (uint32_t)(n_words - 1), n_hash, d_dirty)));
+      DISPATCH_H_FEW(H, (k_touch_probe<HH, 0><<<dim3((uint32_t)nt), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, d_table, (uint32_t)(n_words - 1), n_hash, d_dirty)));
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(e1, c->stream));
@@ -447,6 +450,9 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   }
   if (long_span(c)) {
     return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
+  }
+  if (c->params.h > GRP_H_GROUP) {
+    return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype hashes up to %d seeds per frame only (h=%u)", GRP_H_GROUP, c->params.h);
   }
   const uint32_t H = c->params.h, tile = c->params.tile;
   if ((uint64_t)tile * H > 65535u) {
@@ -511,9 +517,9 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   const size_t lds_vote = (size_t)g.hist_cap * 6 + (size_t)tile * H * 4 + 64;
   HIP_TRY(c, hipEventRecord(ev[0], c->stream));
   if (c->uniform_weight == 16) {
-    DISPATCH_H(H, (k_ps_partition<HH, 16><<<dim3((uint32_t)nt), dim3(THREADS), lds_part, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, ps)));
+    DISPATCH_H_FEW(H, (k_ps_partition<HH, 16><<<dim3((uint32_t)nt), dim3(THREADS), lds_part, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, ps)));
   } else {
-    DISPATCH_H(H, (k_ps_partition<HH, 0><<<dim3((uint32_t)nt), dim3(THREADS), lds_part, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, ps)));
+    DISPATCH_H_FEW(H, (k_ps_partition<HH, 0><<<dim3((uint32_t)nt), dim3(THREADS), lds_part, c->stream>>>(c->f, r->dev, c->d_seeds, tile, t0, ps)));
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(ev[1], c->stream));
@@ -533,7 +539,7 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(ev[3], c->stream));
-  DISPATCH_H(H, (k_ps_vote<HH><<<dim3((uint32_t)nt), dim3(THREADS), lds_vote, c->stream>>>(r->dev, c->d_seeds, tile, t0, ps, g.hist_cap, g.distinct_limit, d_tiles, d_lists, lcap, d_ctr)));
+  DISPATCH_H_FEW(H, (k_ps_vote<HH><<<dim3((uint32_t)nt), dim3(THREADS), lds_vote, c->stream>>>(r->dev, c->d_seeds, tile, t0, ps, g.hist_cap, g.distinct_limit, d_tiles, d_lists, lcap, d_ctr)));
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(ev[4], c->stream));
   unsigned long long used = 0;

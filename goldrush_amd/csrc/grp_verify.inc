@@ -86,11 +86,17 @@ __device__ inline bool
 verify_frame(const DevFilter& f, const DevSeeds* __restrict__ sd, const ulonglong2* sTab, const uint32_t* sBases, uint32_t boff, uint32_t fr, uint32_t Lp, const DevBatchView& bv, uint32_t reader, uint32_t fl0,
              uint32_t flj, uint32_t* dKeys, int* dVals, int& dh, int& dm)
 {
+  const uint32_t hn = frame_seeds<H>(sd);
   uint32_t cur[H];
   uint64_t rank[H], bl[H];
   bool all = true;
 #pragma unroll
   for (int s = 0; s < H; ++s) {
+    if (!seed_on<H>(s, hn)) { // (the many-seed form: no probe; its IDs below are 0, which nothing counts)
+      cur[s] = 0u;
+      rank[s] = bl[s] = 0;
+      continue;
+    }
     // a seed that can no longer roll keeps its last value (multiLensfrHashIterator.hpp:49-68)
     const uint32_t fs = min(fr, Lp - sd->span[s]);
     const Probe pr = grp_locate(f, seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs)));
@@ -112,6 +118,10 @@ verify_frame(const DevFilter& f, const DevSeeds* __restrict__ sd, const ulonglon
   uint32_t a[H], z[H]; // the frame's IDs in front of the batch / in front of the reader's insert, saturation bit stripped (:573-594)
 #pragma unroll
   for (int s = 0; s < H; ++s) {
+    if (!seed_on<H>(s, hn)) {
+      a[s] = z[s] = 0u;
+      continue;
+    }
     const uint32_t c = cur[s], ci = c & 0x7FFFFFFFu;
     const uint32_t v0 = (ci >= id0) ? batch_view(bv, rank[s], bl[s], 0u, c, (fl0 >> 31) != 0u && ci == id0) : c;
     const uint32_t vj = (ci >= idj) ? batch_view(bv, rank[s], bl[s], reader, c, (flj >> 31) != 0u && ci == idj) : c;
@@ -148,7 +158,8 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
 {
   extern __shared__ uint4 smem4[];
   ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + H * sd->wmax * 4u);
+  const uint32_t hn = frame_seeds<H>(sd);
+  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
   __shared__ uint32_t dKeys[VF_DCAP];
   __shared__ int dVals[VF_DCAP];
   __shared__ uint32_t dSeen[VF_DCAP];
@@ -197,7 +208,10 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
     bool d = false;
 #pragma unroll
     for (int s = 0; s < H; ++s) {
-      const uint32_t idx = ((unit0 + part) * (uint32_t)H + (uint32_t)s) * THREADS + threadIdx.x;
+      if (!seed_on<H>(s, hn)) {
+        continue;
+      }
+      const uint32_t idx = ((unit0 + part) * hn + (uint32_t)s) * THREADS + threadIdx.x;
       const unsigned long long key = b.rec_key[idx];
       uint32_t owner = idx;
       bool touch = (key >> 26) != 0ull;

@@ -548,8 +548,10 @@ decide_lds_bytes(uint32_t lds_tiles)
   return (size_t)lds_tiles * DECIDE_LDS_BYTES_PER_TILE;
 }
 
-#define DISPATCH_H(hval, CALL)                                                                                         \
-  switch (hval) {                                                                                                      \
+// The kernel form of h seeds per frame: one instantiation per h up to 8, the many-seed form (GRP_H_MANY, grp_kernels.inc
+// frame_seeds) for 9 .. 16.  Any other h has no kernel: an error (grp_create refuses it first).  Used inside functions
+// that return a grp_status and have the context `c` at hand.
+#define DISPATCH_H_CASES_FEW(CALL)                                                                                     \
     case 1: { constexpr int HH = 1; CALL; } break;                                                                     \
     case 2: { constexpr int HH = 2; CALL; } break;                                                                     \
     case 3: { constexpr int HH = 3; CALL; } break;                                                                     \
@@ -557,7 +559,19 @@ decide_lds_bytes(uint32_t lds_tiles)
     case 5: { constexpr int HH = 5; CALL; } break;                                                                     \
     case 6: { constexpr int HH = 6; CALL; } break;                                                                     \
     case 7: { constexpr int HH = 7; CALL; } break;                                                                     \
-    default: { constexpr int HH = 8; CALL; } break;                                                                    \
+    case 8: { constexpr int HH = 8; CALL; } break;
+#define DISPATCH_H(hval, CALL)                                                                                         \
+  switch (hval) {                                                                                                      \
+    DISPATCH_H_CASES_FEW(CALL)                                                                                         \
+    case 9: case 10: case 11: case 12: case 13: case 14: case 15:                                                      \
+    case 16: { constexpr int HH = GRP_H_MANY; CALL; } break;                                                           \
+    default: return set_err(c, GRP_ERR_INVALID, "h=%u has no kernel form", (unsigned)(hval));                         \
+  }
+// the forms of h <= 8 only (the developer prototypes of grp_pshard.inc, which refuse more seeds first)
+#define DISPATCH_H_FEW(hval, CALL)                                                                                     \
+  switch (hval) {                                                                                                      \
+    DISPATCH_H_CASES_FEW(CALL)                                                                                         \
+    default: return set_err(c, GRP_ERR_INVALID, "h=%u has no kernel form here", (unsigned)(hval));                    \
   }
 
 // decision buffers of a slot: [64 bytes of counters][cap decisions], on the device and page-locked on the host
@@ -625,6 +639,15 @@ query_geom(const grp_ctx* c, bool full)
       const size_t fixed = lds_of(0);
       const uint32_t cap = (uint32_t)((52 * 1024 - std::min<size_t>(fixed, 40 * 1024)) / 6 / 1024 * 1024);
       if (cap > (uint32_t)THREADS * h + 1024 && cap < cap_full) {
+        g.hist_cap = cap;
+      }
+    }
+    if (g.hist_cap == cap_full && lds_of(cap_full) > LDS_PER_WORKGROUP) {
+      // no room for the three-workgroups table beside large seed tables (h > 8 of heavy seeds): the largest table
+      // the LDS takes, the tiles it cannot hold redone with the worst-case one
+      const size_t fixed = lds_of(0);
+      const uint32_t cap = fixed < LDS_PER_WORKGROUP ? (uint32_t)((LDS_PER_WORKGROUP - fixed) / 6 / 1024 * 1024) : 0u;
+      if (cap > (uint32_t)THREADS * h + 64) {
         g.hist_cap = cap;
       }
     }
@@ -909,7 +932,7 @@ grp_create(const grp_params* p, grp_ctx** out)
   }
   *out = nullptr;
   if (p->h < 1 || p->h > GRP_MAX_SEEDS) {
-    return set_err(nullptr, GRP_ERR_INVALID, "h=%u outside [1,%d]", p->h, GRP_MAX_SEEDS);
+    return set_err(nullptr, GRP_ERR_INVALID, "h=%u: this implementation supports 1 to %d spaced seeds", p->h, GRP_MAX_SEEDS);
   }
   if (p->k < 1 || p->k > GRP_MAX_SPAN || p->k + p->h - 1 > GRP_MAX_SPAN) {
     return set_err(nullptr, GRP_ERR_INVALID, "k=%u h=%u: the longest seed spans k+h-1=%u bases, this implementation supports spans of 1 to %d bases", p->k, p->h, p->k + p->h - 1, GRP_MAX_SPAN);

@@ -59,7 +59,8 @@ typedef struct grp_ctx grp_ctx;     /* one miBF + its device, stream, scratch */
 typedef struct grp_reads grp_reads; /* a batch of packed reads resident in HBM */
 
 /* limits of this implementation (checked by grp_create) */
-#define GRP_MAX_SEEDS 8  /* -h */
+#define GRP_MAX_SEEDS 16 /* -h: up to 8 seeds each h has kernels of its own, 9 .. 16 share one many-seed form; the
+                            oracle that checks the engine stops at 16, so 17 and more are refused */
 #define GRP_MAX_SPAN 256 /* k + h - 1 <= 256 bases (up to 32: one 64-bit window of 2-bit bases, up to 64: two, beyond: each
                             care position read on its own — the long-span kernels) */
 #define GRP_MAX_TILE 65535 /* -t: an ID's count per tile is 16 bits (round 5: tile x h IDs need not fit the LDS any more) */
