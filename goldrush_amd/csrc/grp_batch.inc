@@ -131,7 +131,7 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
   const uint32_t gunit = gunit0 + blockIdx.x;
   const uint32_t unit = gunit / hn;
   const uint32_t s = gunit - unit * hn;
-  const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
+  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
   const uint32_t jb = batch_unit_jb(b, unit, parts);
   const uint32_t* e = b.ins + (size_t)(jb >> 8) * 6;
   const uint32_t read_idx = e[0], tile_start = e[1];
@@ -143,10 +143,10 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
   const uint32_t blk_unit0 = e[5] + (tj / b.block_tiles) * b.block_tiles * parts;
   const uint32_t blk_unit1 = min(blk_unit0 + b.block_tiles * parts, e[5] + (e[2] - e[1]) * parts);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
 
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
@@ -534,10 +534,10 @@ k_ovl_sample(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, ui
   const uint32_t r = rd.tile_read[t];
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   if (threadIdx.x == 0) {
@@ -750,7 +750,7 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
     return set_err(c, GRP_ERR_INVALID, "grp_batch_insert_reads: more than 2^38 set bits (a table word holds rank + 1 in 38 bits)");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t parts = (c->params.tile + THREADS - 1) / THREADS;
+  const uint32_t parts = tile_parts(c);
   std::vector<uint32_t>& h_ins = br.h_ins;
   h_ins.resize((size_t)n_ins * 6);
   uint64_t units = 0;

@@ -174,6 +174,15 @@ stage_bases(uint32_t* sBases, const uint32_t* __restrict__ packed, uint64_t word
   return b0 & 15u;
 }
 
+// Frames of a full tile.  The tile string is tile + k - 1 bases with the reference's -k (read_hashing.cpp:44-45), and a
+// frame exists while seed 0, the shortest, can roll (multiLensfrHashIterator.hpp:29-68): tile + k - span0 frames, one
+// more than tile at odd k, where seed 0 spans k - 1 (spaced_seeds.cpp:27-66).  A tile of Lp bases has Lp - span0 + 1.
+__device__ __forceinline__ uint32_t
+frames_per_tile(const DevSeeds* __restrict__ sd, uint32_t tile_len)
+{
+  return tile_len + sd->k - sd->span[0];
+}
+
 // ---- wave / block reductions -------------------------------------------------
 
 __device__ inline uint32_t
@@ -201,13 +210,13 @@ k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk
   const uint32_t r = rd.chunk_read[chunk];
   const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + h - 1
+  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
+  const uint32_t npos = len - s0 + 1u; // chunk exists => len >= s0 + h - 1
   const uint32_t p0 = ci * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
   __syncthreads();
 
   uint32_t* words = f.bv;
@@ -272,13 +281,13 @@ k_fill_long(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t 
   const uint32_t r = rd.chunk_read[chunk];
   const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // chunk exists => len >= k + h - 1
+  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
+  const uint32_t npos = len - s0 + 1u; // chunk exists => len >= s0 + h - 1
   const uint32_t p0 = ci * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
   __syncthreads();
 
   uint32_t* words = f.bv;
@@ -1556,16 +1565,16 @@ __device__ inline void
 insert_collect_unit(const DevFilter& f, const DevReads& rd, const DevSeeds* __restrict__ sd, const ulonglong2* sTab, uint32_t* sBases, uint32_t* sWave /* [THREADS / 64 + 1] */, uint32_t tile_len,
                     uint32_t read_idx, uint32_t tile_start, uint32_t block_tiles, const InsertTable& tb, uint32_t* counter, uint32_t unit)
 {
-  const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
+  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
   const uint32_t tj = unit / parts; // tile inside the inserted range
   const uint32_t ti = tile_start + tj;
   const uint32_t part = unit % parts;
   const unsigned long long block_bit = 1ull << (tj / block_tiles);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
 
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
   __syncthreads();
@@ -1983,7 +1992,7 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
   const uint32_t par = (ev >> 1) & 1u;
   const uint32_t members = ldc(sc.ctl + SCT_MEMBERS); // the workgroups this insert waits for (those that had begun when it was published)
   uint32_t* const bar = sc.ctl + SCT_BAR + (par * 2u) * 32u;
-  const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
+  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
   const uint32_t n_units = (tile_end - tile_start) * parts;
   const unsigned long long t_enter = wall_clock64(); // workgroup 0 leaves the phase times of the insert for the host's trace
   // collect
@@ -2597,11 +2606,11 @@ k_query(DevFilter f,
     }
   }
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
-  // tile string = seq.substr(ti*tile, tile + k - 1)   (read_hashing.cpp:44-45)
+  const uint32_t k = sd->k, s0 = sd->span[0];
+  // tile string = seq.substr(ti*tile, tile + k - 1)   (read_hashing.cpp:44-45); frames while seed 0 can roll
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
 
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   for (uint32_t i = threadIdx.x; i < hist_cap; i += THREADS) {
@@ -2663,7 +2672,8 @@ k_query(DevFilter f,
   constexpr uint32_t OV = (uint32_t)H - 1u, USE = 64u - OV;
   static_assert(THREADS == 256, "the helper-lane layout below is written for four waves per workgroup (my_wave == 3 is the last one, FBH = 3 * USE + 64)");
   constexpr uint32_t FBH = 3u * USE + 64u;
-  const bool helper = n_left != 0u && (tile_len + FBH * FR - 1u) / (FBH * FR) == (tile_len + THREADS * FR - 1u) / (THREADS * FR);
+  const uint32_t ftile = frames_per_tile(sd, tile_len);
+  const bool helper = n_left != 0u && (ftile + FBH * FR - 1u) / (FBH * FR) == (ftile + THREADS * FR - 1u) / (THREADS * FR);
   const uint32_t FB = helper ? FBH : (uint32_t)THREADS; // frames per block of THREADS lanes
   const uint32_t my_wave = threadIdx.x >> 6, my_lane = threadIdx.x & 63u;
   const uint32_t my_off = helper ? (my_wave * USE + my_lane) : threadIdx.x;          // frame of this lane inside a block
@@ -3317,14 +3327,14 @@ insert_tiles(const DevFilter& f,
 
   const uint32_t r = read_idx;
   // one frame per thread: `parts` workgroups share a tile
-  const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
+  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
   const uint32_t ti = tile_start + blockIdx.x / parts;
   const uint32_t part = blockIdx.x % parts;
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
 
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
@@ -3561,10 +3571,10 @@ debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t 
   const uint32_t hn = frame_seeds<H>(sd);
   uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = tile_idx * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
   __syncthreads();

@@ -34,13 +34,13 @@ k_ntcard(DevReads rd,
   const uint2 ck = chunks[blockIdx.x];
   const uint32_t r = ck.x;
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // listed => len >= k
+  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
+  const uint32_t npos = len - s0 + 1u; // listed => len >= s0
   const uint32_t p0 = ck.y * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
   __syncthreads();
 
   const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
@@ -67,10 +67,10 @@ k_ntcard(DevReads rd,
       }
       if (ind < NTC_NSAMP) {
         // the seed's last window is counted again for every frame it stays stale:
-        // span_s - k frames for a plain read, or what the host computed
+        // span_s - span_0 frames for a plain read, or what the host computed
         uint32_t times = 1u;
         if (p + span == len) {
-          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - k);
+          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - s0);
         }
         const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
         atomicAdd(&counters[slot], times);
@@ -99,13 +99,13 @@ k_ntcard_long(DevReads rd,
   const uint2 ck = chunks[blockIdx.x];
   const uint32_t r = ck.x;
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
-  const uint32_t npos = len - k + 1u; // listed => len >= k
+  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
+  const uint32_t npos = len - s0 + 1u; // listed => len >= s0
   const uint32_t p0 = ck.y * FILL_CHUNK;
   const uint32_t np = min(FILL_CHUNK, npos - p0);
 
   load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + k + hn - 2u);
+  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
   __syncthreads();
 
   const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
@@ -132,10 +132,10 @@ k_ntcard_long(DevReads rd,
       }
       if (ind < NTC_NSAMP) {
         // the seed's last window is counted again for every frame it stays stale:
-        // span_s - k frames for a plain read, or what the host computed
+        // span_s - span_0 frames for a plain read, or what the host computed
         uint32_t times = 1u;
         if (p + span == len) {
-          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - k);
+          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - s0);
         }
         const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
         atomicAdd(&counters[slot], times);
@@ -192,20 +192,21 @@ grp_ntcard_add(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, c
     return set_err(c, GRP_ERR_STATE, "grp_ntcard_add before grp_ntcard_begin");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t k = c->params.k, h = c->params.h;
+  const uint32_t s0 = span0(c), h = c->params.h;
   std::vector<uint2> chunks;
   uint64_t hashes = 0;
   for (uint32_t i = first; i < first + count; ++i) {
     const uint32_t len = r->len[i];
-    if (len < k) {
+    if (len < s0) {
       continue; // no window of any seed
     }
-    const uint32_t nch = (len - k + 1 + FILL_CHUNK - 1) / FILL_CHUNK;
+    const uint32_t nch = (len - s0 + 1 + FILL_CHUNK - 1) / FILL_CHUNK;
     for (uint32_t j = 0; j < nch; ++j) {
       chunks.push_back(make_uint2(i, j));
     }
     for (uint32_t s = 0; s < h; ++s) {
-      hashes += len >= k + s ? len - (k + s) + 1 : 0;
+      const uint32_t span = c->h_seeds.span[s];
+      hashes += len >= span ? len - span + 1 : 0;
     }
   }
   if (chunks.empty()) {

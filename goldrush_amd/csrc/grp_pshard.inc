@@ -379,6 +379,9 @@ grp_debug_touch_filter(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t 
   if (long_span(c)) {
     return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
   }
+  if (span0(c) != c->params.k) {
+    return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype takes tiles of `tile` frames only (seed 0 spans %u bases, k=%u)", span0(c), c->params.k);
+  }
   if (c->params.h > GRP_H_GROUP) {
     return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: the prototype hashes up to %d seeds per frame only (h=%u)", GRP_H_GROUP, c->params.h);
   }
@@ -450,6 +453,9 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   }
   if (long_span(c)) {
     return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype hashes seeds of spans up to 64 bases only (k+h-1=%u)", c->params.k + c->params.h - 1);
+  }
+  if (span0(c) != c->params.k) {
+    return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype takes tiles of `tile` frames only (seed 0 spans %u bases, k=%u)", span0(c), c->params.k);
   }
   if (c->params.h > GRP_H_GROUP) {
     return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: the prototype hashes up to %d seeds per frame only (h=%u)", GRP_H_GROUP, c->params.h);

@@ -172,7 +172,7 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
   const uint32_t r = rd.tile_read[t];
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t reader = r - bv.first;
-  const uint32_t parts = (tile_len + THREADS - 1) / THREADS;
+  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
   // only the tiles this batch inserted have records; the others are k_query<.., VER>'s
   uint32_t unit0 = 0;
   {
@@ -187,10 +187,10 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
     unit0 = e[5] + (ti - e[1]) * parts;
   }
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k;
+  const uint32_t k = sd->k, s0 = sd->span[0];
   const uint32_t start = ti * tile_len;
   const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
 
   for (uint32_t i = threadIdx.x; i < VF_DCAP; i += THREADS) {
     dKeys[i] = 0u;
@@ -437,7 +437,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   c->carry.valid = false;
   // Per read of the batch: its entry in the insert list (the kernels tell from it which tiles have records).  The
   // floors travel in the same page-locked block: one copy per call, nothing per tile on the host.
-  const uint32_t tile = c->params.tile, k = c->params.k, h = c->params.h;
+  const uint32_t tile = c->params.tile, k = c->params.k, h = c->params.h, s0 = span0(c), ftile = tile_frames(c);
   if ((uint64_t)count + total > br.vf_stage_cap) {
     if (br.h_vf_stage) {
       (void)hipHostFree(br.h_vf_stage);
@@ -466,10 +466,10 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
         rins[j] = ji;
         const uint32_t ts = br.h_ins[(size_t)ji * 6 + 1], te = br.h_ins[(size_t)ji * 6 + 2];
         const uint32_t ntile = (uint32_t)(r->tile0[rd_i + 1] - r->tile0[rd_i]);
-        uint64_t fr = (uint64_t)(te - ts) * tile; // only a read's last tile can be clipped
+        uint64_t fr = (uint64_t)(te - ts) * ftile; // only a read's last tile can be clipped
         if (te == ntile && ntile) {
           const uint32_t Lp = std::min(tile + k - 1, r->len[rd_i] - (ntile - 1) * tile);
-          fr -= tile - (Lp >= k ? Lp - k + 1 : 0);
+          fr -= ftile - (Lp >= s0 ? Lp - s0 + 1 : 0);
         }
         r_records += fr * h;
         recorded_tiles += te - ts;

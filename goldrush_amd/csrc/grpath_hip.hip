@@ -521,6 +521,28 @@ long_span(const grp_ctx* c)
   return c->h_seeds.wide > 1u;
 }
 
+// span of seed 0, the shortest seed: k, or k - 1 at odd k (make_seed_pattern, spaced_seeds.cpp:27-66).  The tile string
+// stays tile + k - 1 bases (read_hashing.cpp:44-45), so a full tile has tile + k - span0 frames (grp_kernels.inc
+// tile_frames); the longest seed spans span0 + h - 1 bases, the minimum length of a read that takes part in the fill.
+inline uint32_t
+span0(const grp_ctx* c)
+{
+  return c->h_seeds.span[0];
+}
+
+inline uint32_t
+tile_frames(const grp_ctx* c)
+{
+  return c->params.tile + c->params.k - span0(c);
+}
+
+// units of THREADS frames per tile of the kernels that walk a tile that way (k_insert, k_insert_collect, k_batch_collect)
+inline uint32_t
+tile_parts(const grp_ctx* c)
+{
+  return (tile_frames(c) + THREADS - 1) / THREADS;
+}
+
 template<typename K>
 int
 ensure_lds(grp_ctx* c, K kernel, size_t bytes)
@@ -625,7 +647,7 @@ QueryGeom
 query_geom(const grp_ctx* c, bool full)
 {
   const uint32_t h = c->params.h, tile = c->params.tile;
-  const uint64_t max_ids = (uint64_t)tile * h;
+  const uint64_t max_ids = (uint64_t)tile_frames(c) * h; // (tile + 1 frames at odd k)
   auto lds_of = [&](uint32_t cap) { return tab_bytes(c) + (size_t)cap * 6 + bases_bytes(tile + c->params.k + h); };
   const uint32_t cap_full = (uint32_t)((max_ids + (uint64_t)THREADS * h + 2 + 1023) / 1024 * 1024);
   const uint32_t forced_small = c->env_small_hist; // developer hook / tests (GRP_SMALL_HIST, read when the context is created): slots of the first-step table — forces the two-step scheme
@@ -776,7 +798,7 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
         return e ? std::max(0, std::min(2, atoi(e))) : 2;
       }();
       const uint32_t fb = 3u * (64u - ((uint32_t)HH - 1u)) + 64u; // frames per pass at least (k_query: the helper-lane layout)
-      const uint32_t passes = (c->params.tile + fb - 1u) / fb;
+      const uint32_t passes = (tile_frames(c) + fb - 1u) / fb;
       const uint32_t words = passes * (uint32_t)THREADS * (uint32_t)HH;
       const int want_cu = std::min(per_cu, 3);
       for (int nf = std::min<int>(keep_env, (int)stream_ctl->n_fp); nf >= 1; --nf) {
@@ -849,10 +871,16 @@ build_seed_tables(grp_ctx* c)
   sd.h = c->params.h;
   sd.k = c->params.k;
   sd.wmax = 0;
+  // seed s spans span0 + s bases, span0 = k or k - 1 (odd k: make_seed_pattern's halves are k/2 positions each,
+  // spaced_seeds.cpp:27-66); the tile string is tile + k - 1 bases either way
+  const size_t sp0 = c->seeds[0].size();
+  if (sp0 == 0 || (sp0 != c->params.k && sp0 + 1 != c->params.k)) {
+    return set_err(c, GRP_ERR_INVALID, "seed 0 has span %zu, expected k = %u or k-1 = %u", sp0, c->params.k, c->params.k - 1);
+  }
   for (uint32_t s = 0; s < sd.h; ++s) {
     const std::string& p = c->seeds[s];
-    if (p.size() != (size_t)c->params.k + s) {
-      return set_err(c, GRP_ERR_INVALID, "seed %u has span %zu, expected k+%u = %u", s, p.size(), s, c->params.k + s);
+    if (p.size() != sp0 + s) {
+      return set_err(c, GRP_ERR_INVALID, "seed %u has span %zu, expected k+%u = %u or k-1+%u = %u", s, p.size(), s, c->params.k + s, s, c->params.k - 1 + s);
     }
     sd.span[s] = (uint32_t)p.size();
     uint32_t w = 0;
@@ -886,7 +914,9 @@ build_seed_tables(grp_ctx* c)
   // spans beyond 32 bases (round 4): the generic hash reads a second 64-bit window; the unrolled weight-16 form and
   // the shared halves are 32-base forms and stay off.  Beyond 64 bases (up to GRP_MAX_SPAN): the long-span
   // instantiations, which read each care position from the staged bases (long_span, grp_kernels.inc seed_hash_long).
-  const uint32_t span = c->params.k + sd.h - 1;
+  // The class comes from the longest actual span, span0 + h - 1 (k + h - 2 at odd k): k = 33 with one seed of 32 bases
+  // hashes from the 32-base window, k = 65 with one seed of 64 from the 64-base one.
+  const uint32_t span = sd.span[sd.h - 1];
   sd.wide = (span > 64) ? 2u : (span > 32) ? 1u : 0u;
   if (sd.wide) {
     c->uniform_weight = 0;
@@ -989,6 +1019,10 @@ grp_create(const grp_params* p, grp_ctx** out)
   int rc = build_seed_tables(c);
   if (rc != GRP_OK) {
     return fail(rc);
+  }
+  if (tile_frames(c) > GRP_MAX_TILE) { // odd k: a full tile has tile + 1 frames
+    set_err(c, GRP_ERR_INVALID, "tile length %u with k=%u and a shortest seed of %u bases: %u frames per tile, at most 65 535 (an ID's count per tile is 16 bits)", p->tile, p->k, span0(c), tile_frames(c));
+    return fail(GRP_ERR_INVALID);
   }
   // LDS geometry of the query kernel's worst-case launch must fit one workgroup
   {
@@ -1274,8 +1308,8 @@ static int
 reads_build(grp_ctx* c, grp_reads* r, const uint64_t* word_off, const uint32_t* len, uint32_t n)
 {
   const uint32_t tile = c->params.tile;
-  const uint32_t k = c->params.k;
-  const uint32_t min_len = c->params.k + c->params.h - 1;
+  const uint32_t s0 = span0(c);
+  const uint32_t min_len = s0 + c->params.h - 1;
   r->ctx = c;
   r->n_reads = n;
   r->n_words = word_off[n];
@@ -1290,7 +1324,7 @@ reads_build(grp_ctx* c, grp_reads* r, const uint64_t* word_off, const uint32_t* 
     // reads shorter than the longest span are outside the reference's defined
     // behaviour (SeedNtHash on a too-short string); they contribute nothing
     if (len[i] >= min_len) {
-      uint64_t npos = (uint64_t)len[i] - k + 1;
+      uint64_t npos = (uint64_t)len[i] - s0 + 1;
       ch += (npos + FILL_CHUNK - 1) / FILL_CHUNK;
     }
     if ((uint64_t)(len[i] + 15u) / 16u > word_off[i + 1] - word_off[i]) {
@@ -1336,8 +1370,8 @@ int
 reads_index(grp_ctx* c, grp_reads* r, const uint64_t* word_off, const uint32_t* len, uint32_t n)
 {
   const uint32_t tile = c->params.tile;
-  const uint32_t k = c->params.k;
-  const uint32_t min_len = c->params.k + c->params.h - 1;
+  const uint32_t s0 = span0(c);
+  const uint32_t min_len = s0 + c->params.h - 1;
   r->ctx = c;
   r->n_reads = n;
   r->n_words = word_off[n];
@@ -1350,7 +1384,7 @@ reads_index(grp_ctx* c, grp_reads* r, const uint64_t* word_off, const uint32_t* 
     r->chunk0[i] = ch;
     t += len[i] / tile;
     if (len[i] >= min_len) { // (see reads_build)
-      const uint64_t npos = (uint64_t)len[i] - k + 1;
+      const uint64_t npos = (uint64_t)len[i] - s0 + 1;
       ch += (npos + FILL_CHUNK - 1) / FILL_CHUNK;
     }
   }
@@ -1598,8 +1632,8 @@ grp_bv_insert(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
   uint64_t probes = 0;
   for (uint32_t i = first; i < first + count; ++i) {
     for (uint32_t s = 0; s < c->params.h; ++s) {
-      uint32_t span = c->params.k + s;
-      if (r->len[i] >= c->params.k + c->params.h - 1) {
+      const uint32_t span = c->h_seeds.span[s];
+      if (r->len[i] >= span0(c) + c->params.h - 1) {
         probes += r->len[i] - span + 1;
       }
     }
@@ -1894,17 +1928,17 @@ ensure_dev(grp_ctx* c, T*& p, uint64_t& cap, uint64_t want)
 uint64_t
 count_probes(const grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
 {
-  const uint32_t tile = c->params.tile, k = c->params.k;
+  const uint32_t tile = c->params.tile, k = c->params.k, s0 = span0(c);
   uint64_t probes = 0;
   for (uint32_t i = first; i < first + count; ++i) {
     const uint32_t ntile = r->len[i] / tile;
     if (ntile == 0) {
       continue;
     }
-    // all tiles but the last have `tile` frames; the last may be clipped
+    // all tiles but the last have tile + k - span0 frames; the last may be clipped
     const uint32_t start = (ntile - 1) * tile;
     const uint32_t Lp = std::min(tile + k - 1, r->len[i] - start);
-    probes += ((uint64_t)(ntile - 1) * tile + (Lp - k + 1)) * c->params.h;
+    probes += ((uint64_t)(ntile - 1) * tile_frames(c) + (Lp - s0 + 1)) * c->params.h;
   }
   return probes;
 }
@@ -2667,7 +2701,7 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
   const bool resume_off = c->env_stream_resume_off; // GRP_STREAM_RESUME=off (developer switch / tests, read at grp_create): every window ends where it parks
   sl.resumable = false;
   if (want_resumable && !resume_off && n_mine != 0) {
-    const uint64_t need_ranks = max_tiles_read * c->params.tile * c->params.h;
+    const uint64_t need_ranks = max_tiles_read * tile_frames(c) * c->params.h;
     const bool other_streaming = c->slot[slot ^ 1u].busy && c->slot[slot ^ 1u].streaming;
     if (next_pow2_64(need_ranks * 2) <= c->ir_cap || !other_streaming) {
       rc = ensure_insert_table(c, need_ranks);
@@ -3004,7 +3038,7 @@ grp_classify_stream_insert(grp_ctx* c, uint32_t slot, uint32_t read_idx, uint32_
   w[9] = gen;
   __atomic_store_n(&sl.h_cmd[0], ++sl.cmd_seq, __ATOMIC_RELEASE);
   c->kstat[GRP_K_INSERT].launches += 1;
-  c->kstat[GRP_K_INSERT].units += (uint64_t)(tile_end - tile_start) * c->params.tile * c->params.h;
+  c->kstat[GRP_K_INSERT].units += (uint64_t)(tile_end - tile_start) * tile_frames(c) * c->params.h;
   *generation = gen;
   return GRP_OK;
 }
@@ -3032,7 +3066,7 @@ grp_insert_tiles(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t til
   }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t nt = tile_end - tile_start;
-  const uint64_t max_ranks = (uint64_t)nt * c->params.tile * c->params.h;
+  const uint64_t max_ranks = (uint64_t)nt * tile_frames(c) * c->params.h;
   const uint64_t want = next_pow2(max_ranks * 2);
   if (want > c->dedup_cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3054,9 +3088,9 @@ grp_insert_tiles(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t til
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
     if (long_span(c)) {
-      DISPATCH_H(c->params.h, (k_insert_long<HH><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+      DISPATCH_H(c->params.h, (k_insert_long<HH><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
     } else {
-      DISPATCH_H(c->params.h, (k_insert<HH><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+      DISPATCH_H(c->params.h, (k_insert<HH><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
     }
   }
   HIP_TRY(c, hipGetLastError());
@@ -3095,7 +3129,7 @@ grp_insert_read(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t tile
     return GRP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t max_ranks = (uint64_t)nt * c->params.tile * c->params.h;
+  const uint64_t max_ranks = (uint64_t)nt * tile_frames(c) * c->params.h;
   {
     const int trc = ensure_insert_table(c, max_ranks);
     if (trc != GRP_OK) {
@@ -3109,11 +3143,11 @@ grp_insert_read(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t tile
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
     if (long_span(c)) {
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, GRP_WT_LONG><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
+      DISPATCH_H(c->params.h, (k_insert_collect<HH, GRP_WT_LONG><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
     } else if (c->uniform_weight == 16) { // make_seed_pattern's default weight: care loop unrolled (the launch is latency-bound)
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, 16><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
+      DISPATCH_H(c->params.h, (k_insert_collect<HH, 16><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
     } else {
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, 0><<<dim3(nt * ((c->params.tile + THREADS - 1) / THREADS)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
+      DISPATCH_H(c->params.h, (k_insert_collect<HH, 0><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
     }
     k_insert_apply<<<dim3((uint32_t)((max_ranks + THREADS - 1) / THREADS)), dim3(THREADS), 0, c->stream>>>(c->f, tb, parity, block_tiles, first_id, id_offset);
   }
@@ -3289,7 +3323,7 @@ grp_debug_tile_hashes(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t start = tile_idx * tile;
   const uint32_t Lp = std::min(tile + k - 1, r->len[read_idx] - start);
-  const uint64_t nv = (uint64_t)(Lp - k + 1) * c->params.h;
+  const uint64_t nv = (uint64_t)(Lp - span0(c) + 1) * c->params.h; // (Lp >= tile >= the longest span)
   *n_values = nv;
   if (nv > cap) {
     return set_err(c, GRP_ERR_NOMEM, "grp_debug_tile_hashes: %llu values, capacity %llu", (unsigned long long)nv, (unsigned long long)cap);

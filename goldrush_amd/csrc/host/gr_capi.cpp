@@ -8,6 +8,7 @@
 #include "gr_tiles.hpp"
 #include "gr_fastq.hpp"
 
+#include <cstddef>
 #include <cstring>
 #include <new>
 
@@ -179,10 +180,15 @@ struct gr_classifier
 int
 gr_classifier_create(const gr_classifier_params* p, const grp_engine_vt* vt, void* engine_ctx, gr_classifier** out)
 {
-  if (!p || !vt || !out || p->struct_size != sizeof(gr_classifier_params) || p->tile_length == 0 || p->block_size == 0) {
+  // (callers built before seed0_span pass the shorter struct: the field is 0 for them)
+  if (!p || !vt || !out || (p->struct_size != sizeof(gr_classifier_params) && p->struct_size != offsetof(gr_classifier_params, seed0_span)) || p->tile_length == 0 ||
+      p->block_size == 0) {
     return GRP_ERR_INVALID;
   }
-  *out = new (std::nothrow) gr_classifier(*p, *vt, engine_ctx);
+  gr_classifier_params q{};
+  memcpy(&q, p, p->struct_size);
+  q.struct_size = sizeof(q);
+  *out = new (std::nothrow) gr_classifier(q, *vt, engine_ctx);
   return *out ? GRP_OK : GRP_ERR_NOMEM;
 }
 

@@ -666,14 +666,14 @@ bool
 Classifier::commit(void* reads, const uint32_t* lens, uint32_t r, const gr_read_decision& d, int& rc, bool engine_inserted, uint32_t engine_first_id)
 {
   const uint32_t len = lens[r];
-  const uint32_t tile = p_.tile_length, block = p_.block_size, k = p_.kmer_size;
+  const uint32_t tile = p_.tile_length, block = p_.block_size, k = p_.kmer_size, s0 = p_.seed0_span ? p_.seed0_span : k;
   const uint32_t nt = d.num_tiles;
   total_tiles_ += nt;
   if (nt) {
-    // one query per frame (:567-568); only the last tile can be clipped
+    // one query per frame (:567-568): tile + k - span0 frames per tile; only the last tile can be clipped
     const uint32_t start = (nt - 1) * tile;
     const uint32_t Lp = std::min(tile + k - 1, len - start);
-    queries_ += (uint64_t)(nt - 1) * tile + (Lp >= k ? Lp - k + 1 : 0);
+    queries_ += (uint64_t)(nt - 1) * (tile + k - s0) + (Lp >= s0 ? Lp - s0 + 1 : 0);
   }
   hits_ += d.hits;
   misses_ += d.misses;

@@ -36,7 +36,7 @@ uint64_t ntcard_f0(uint64_t zero0, uint64_t zero1, unsigned sbits);
 // A record with non-ACGT characters as the engine wants it (grp_ntcard_add): its
 // maximal ACGT runs of at least k bases (offset, length), and per run and seed the
 // number of extra counts of the run's last window — the stale repeats of
-// multiLensfrHashIterator (seed s of span k+s visits its V_s clean windows, the
+// multiLensfrHashIterator (k = the span of seed 0, k - 1 at odd -k; seed s of span k+s visits its V_s clean windows, the
 // iterator runs max_s V_s frames; multiLensfrHashIterator.hpp:49-68).
 void ntcard_split(const char* seq, size_t n, unsigned k, unsigned h, std::vector<std::pair<size_t, size_t>>& runs, std::vector<uint32_t>& extra);
 

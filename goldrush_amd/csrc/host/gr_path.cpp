@@ -491,7 +491,8 @@ int
 calc_ntcard_genome_size(PathRun& run, uint64_t& genome_size)
 {
   const Opts& opt = run.opt;
-  const unsigned k = (unsigned)opt.kmer_size, h = (unsigned)opt.hash_num;
+  // windows are counted with the seeds' own spans: seed s spans span0 + s, span0 = k, or k - 1 at odd k (make_seed_pattern)
+  const unsigned s0 = (unsigned)run.seeds[0].size(), h = (unsigned)opt.hash_num;
   std::cerr << "Calculating expected entries" << std::endl;
   const double s_time = now_s();
   uint64_t input_bytes = 0;
@@ -522,13 +523,13 @@ calc_ntcard_genome_size(PathRun& run, uint64_t& genome_size)
     packed.clear();
     for (size_t i = 0; i < b.rec.size(); ++i) {
       if (!b.non_acgt[i]) {
-        if (b.rec[i].seq_len >= k) {
+        if (b.rec[i].seq_len >= s0) {
           sel.push_back((uint32_t)i);
         }
         continue;
       }
       const char* seq = b.text + b.rec[i].seq_off;
-      ntcard_split(seq, b.rec[i].seq_len, k, h, runs, run_extra);
+      ntcard_split(seq, b.rec[i].seq_len, s0, h, runs, run_extra);
       for (size_t r = 0; r < runs.size(); ++r) {
         const size_t w0 = packed.size();
         packed.resize(w0 + (runs[r].second + 15) / 16);
@@ -1249,6 +1250,7 @@ gr_path_main(int argc, char** argv, const grp_engine_vt* vt)
   cp.world = run.world;
   cp.rank = run.rank;
   cp.debug = opt.debug;
+  cp.seed0_span = (uint32_t)run.seeds[0].size();
   if (opt.debug && run.world > 1) {
     std::cerr << "goldrush-path: --debug runs on one rank" << std::endl;
     return 1;

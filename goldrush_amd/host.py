@@ -32,7 +32,7 @@ class gr_classifier_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("tile_length", C.c_uint32), ("block_size", C.c_uint32), ("threshold", C.c_uint32),
                 ("unassigned_min", C.c_uint32), ("assigned_max", C.c_uint32), ("kmer_size", C.c_uint32), ("hash_num", C.c_uint32),
                 ("target_bases", C.c_uint64), ("max_paths", C.c_uint64), ("silver_path", C.c_int32), ("verbose", C.c_int32),
-                ("max_window", C.c_uint32), ("world", C.c_uint32), ("rank", C.c_uint32), ("debug", C.c_int32)]
+                ("max_window", C.c_uint32), ("world", C.c_uint32), ("rank", C.c_uint32), ("debug", C.c_int32), ("seed0_span", C.c_uint32)]
 
 
 class gr_classifier_state(C.Structure):
@@ -266,11 +266,12 @@ class Classifier:
     """gr_classifier over an engine (HIP engine by default)."""
 
     def __init__(self, engine_handle, vt: grp_engine_vt, tile=1000, block=10, threshold=10, unassigned_min=5, assigned_max=1, k=22, h=3,
-                 target_bases=0, max_paths=1, silver_path=False, verbose=False, max_window=0, world=1, rank=0, allgather=None, record=True):
+                 target_bases=0, max_paths=1, silver_path=False, verbose=False, max_window=0, world=1, rank=0, allgather=None, record=True, span0=0):
+        # span0: the span of seed 0 (k - 1 for make_seed_pattern's seeds at odd k); 0 = k
         self.lib = load()
         self.vt = vt
         p = gr_classifier_params(C.sizeof(gr_classifier_params), tile, block, threshold, unassigned_min, assigned_max, k, h, target_bases, max_paths,
-                                 1 if silver_path else 0, 1 if verbose else 0, max_window, world, rank, 0)
+                                 1 if silver_path else 0, 1 if verbose else 0, max_window, world, rank, 0, span0)
         out = _vp()
         rc = self.lib.gr_classifier_create(C.byref(p), C.byref(vt), engine_handle, C.byref(out))
         if rc != 0:

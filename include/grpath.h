@@ -62,7 +62,10 @@ typedef struct grp_reads grp_reads; /* a batch of packed reads resident in HBM *
 #define GRP_MAX_SEEDS 16 /* -h: up to 8 seeds each h has kernels of its own, 9 .. 16 share one many-seed form; the
                             oracle that checks the engine stops at 16, so 17 and more are refused */
 #define GRP_MAX_SPAN 256 /* k + h - 1 <= 256 bases (up to 32: one 64-bit window of 2-bit bases, up to 64: two, beyond: each
-                            care position read on its own — the long-span kernels) */
+                            care position read on its own — the long-span kernels).  Seed s spans span0 + s with span0 = k or
+                            span0 = k - 1 (make_seed_pattern at odd k: halves of k/2 positions, spaced_seeds.cpp:27-66); the tile
+                            string is tile + k - 1 bases either way, so a full tile has tile + k - span0 frames (at most 65 535)
+                            and a read takes part in the fill from span0 + h - 1 bases on; any other family is refused */
 #define GRP_MAX_TILE 65535 /* -t: an ID's count per tile is 16 bits (round 5: tile x h IDs need not fit the LDS any more) */
 
 typedef struct
@@ -75,8 +78,8 @@ typedef struct
                            MIBloomFilter::calcOptimalSize
                            (MIBloomFilter.hpp:94-101, goldrush_path.cpp:1183);
                            0 = not known yet, grp_set_filter_size follows (--ntcard) */
-  const char* const* seeds; /* h strings of '0'/'1'; seed i has span k+i
-                               (make_seed_pattern, spaced_seeds.cpp:63-66) */
+  const char* const* seeds; /* h strings of '0'/'1'; seed i has span k+i, or k-1+i at odd k
+                               (make_seed_pattern, spaced_seeds.cpp:27-66; see GRP_MAX_SPAN) */
   int32_t device;       /* HIP device ordinal; -1 = current device */
   uint32_t flags;       /* reserved, 0 */
 } grp_params;
@@ -136,7 +139,7 @@ const uint64_t* grp_reads_tile0(const grp_reads* reads);
  *                      ACGT bases.  Each seed counts all its windows once and its last
  *                      window stale_extra[(i-first)*h + s] more times (the iterator
  *                      repeats a seed that can no longer roll); stale_extra == NULL
- *                      means the plain-read rule: span_s - k repeats.  A record with
+ *                      means the plain-read rule: span_s - span_0 repeats.  A record with
  *                      non-ACGT characters is passed as its maximal ACGT runs, the
  *                      record's repeats attached to the run holding the seed's last
  *                      window.  Synchronous.

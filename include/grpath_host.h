@@ -110,7 +110,7 @@ double gr_sum_phred(const char* qual, size_t n);
 int gr_pack_2bit(const char* seq, size_t n, uint32_t* out_words);
 /* --ntcard host arithmetic (goldrush_path/ntcard.hpp): nts::sBits for the input size
  * (:177-178); compEst's F0 from the zero buckets of the two sample tables (:124-136,
- * :232); and a record with non-ACGT characters cut into the ACGT runs (>= k bases)
+ * :232); and a record with non-ACGT characters cut into the ACGT runs (>= k bases; k = the span of seed 0, -k - 1 at odd -k)
  * grp_ntcard_add takes, with the iterator's stale repeats per run and seed
  * (extra[run*h + s]).  gr_ntcard_split returns the number of runs (writes at most cap). */
 unsigned gr_ntcard_sbits(uint64_t input_bytes);
@@ -152,6 +152,9 @@ typedef struct
   uint32_t world, rank;   /* ranks sharing each window (1, 0 = single GPU) */
   int32_t debug;          /* --debug: reads are decided one by one on the host and the reference's per-read
                              lines and per-pass tile-state dumps go to stderr (goldrush_path.cpp:109-124, 938-1086) */
+  uint32_t seed0_span;    /* span of seed 0: kmer_size, or kmer_size - 1 at odd k (make_seed_pattern); a tile has
+                             tile_length + kmer_size - seed0_span frames (the "Total queries" count).  0 = kmer_size.
+                             A struct_size that ends in front of this field is accepted (0). */
 } gr_classifier_params;
 
 /* one committed read, in file order */

@@ -31,12 +31,15 @@ def main():
         if k == 22 and w == 16:
             preset = "1011011110110111101101"
         else:  # care positions at both ends, the rest drawn
+            last = k - 1 - k % 2  # (odd k: the last position is dropped from the seeds, below)
             care = np.zeros(k, dtype=bool)
-            care[0] = care[-1] = True
-            care[np.random.default_rng(k).choice(np.arange(1, k - 1), size=w - 2, replace=False)] = True
+            care[0] = care[last] = True
+            care[np.random.default_rng(k).choice(np.arange(1, last), size=w - 2, replace=False)] = True
             preset = "".join("1" if c else "0" for c in care)
     assert len(preset) == k and preset.count("1") == w
-    seeds = [preset[:k // 2] + "0" * i + preset[k // 2:] for i in range(a.h)]
+    # make_seed_pattern's family (spaced_seeds.cpp:27-66): halves of k/2 positions, so at odd k the preset's last
+    # position is dropped and seed 0 spans k - 1 (a tile of tile + 1 frames)
+    seeds = [preset[:k // 2] + "0" * i + preset[k // 2: 2 * (k // 2)] for i in range(a.h)]
     U = int(np.float32(min(4 ** w, 2 * G)) * np.float32(0.5) * np.float32(a.h))
     n = int(-float(U) / np.log(1.0 - 0.1))
     m = n + (64 - n % 64)
