@@ -5,6 +5,10 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 th
 driver launches one rank per GPU with torch.distributed.run — and where nothing did
 (`WORLD_SIZE` unset), `--gpus N` starts its N ranks itself (launch_ranks).  A launcher
 whose WORLD_SIZE is not N is an error.  Rank 0 prints ONE JSON line.
+A plain run does what the headline figure needs: setup, warm-up, the timed steps, the
+line (every figure in it comes from the timed steps or from setup).  `--full` adds the
+passes that are runs of their own behind the timed steps: cpu_baseline with
+aux.oracle_check, and aux.pipeline_shaped.
 
 Workload (default): BASELINE.json configs[2] "C2" — 10 M synthetic ONT-like reads,
 mean 25 kb, G = 3e9, k=22 w=16 h=3 tile=1000, o=0.1 (m = 61 146 729 472 bits), golden
@@ -36,12 +40,12 @@ roofline: the query kernel.  `achieved` = ALGORITHMIC bytes (128 
           random-64-B-line ceiling of the memory system (profiles/*gather_ceiling.json).
 roofline_insert / roofline_fill: k_batch_collect + apply (2 x 128 B per record slot) and k_fill
           (128 B per probe; `traffic` = its PMC read + write bytes).
-cpu_baseline: the CPU oracle (restatement of the reference) on bounded samples of the
+cpu_baseline: (--full) the CPU oracle (restatement of the reference) on bounded samples of the
           same workload, rank 0, N=1 only.
 aux     : end_to_end (fill + grp_finalize + the timed region: the whole goldrush-path run on resident
           reads), probe_accounting (executed against useful probes, the excess attributed), stream_keep
           (what the streaming windows kept across their in-launch inserts), phases.steady.fit (seconds
-          per read and per insert over the steady-state slices), pipeline_shaped, oracle_check.
+          per read and per insert over the steady-state slices); with --full: pipeline_shaped, oracle_check.
 
 --dump-outputs DIR: after the timed steps, what the last step handed its caller goes to DIR/<name>.npy
 (float64, every value exact): the decisions of the step's reads (commit_<field>.npy, one row per read in
@@ -386,8 +390,10 @@ def main():
                     "0 = the headline workload's uniform genome, where two reads share k-mers only where they overlap.  Not the headline: the line's config says so and aux.repeats sums up what the speculation did")
     ap.add_argument("--len-sigma", type=float, default=0.25, help="sigma of the log-normal read lengths (mean 25 kb, floor 20 kb); 0.25 = the headline workload (no read above ~64 kb), "
                     "0.6 = a realistic ONT tail (reads of 100 kb and more: the decision path for reads of more than 64 tiles)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipeline-shaped", action="store_true", help="skip aux.pipeline_shaped (the silver-mode pass over the same reads after the timed region)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the CPU baseline with the oracle's check of the GPU path's decisions (cpu_baseline, aux.oracle_check) and the silver-mode pass "
+                    "over the same reads (aux.pipeline_shaped), each a run of its own after the timed steps.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and aux.oracle_check")
+    ap.add_argument("--no-pipeline-shaped", action="store_true", help="with --full: skip aux.pipeline_shaped (the silver-mode pass over the same reads after the timed region)")
     ap.add_argument("--trace", action="store_true", help="per-slice timing / speculation statistics on stderr")
     ap.add_argument("--no-kernel-timing", action="store_true", help="developer: no HIP events around the launches (roofline fields become meaningless)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for single-GPU plumbing tests)")
@@ -627,7 +633,7 @@ def main():
         hl.gr_classifier_set_allgather(cls._h, C.cast(hl.gr_shm_allgather, C.c_void_p), shm)
     # the oracle's witness (cpu_baseline leg): what the GPU path decided for the first and the last WITNESS reads of
     # the stream stays inside the classifier (no callback per read) and is compared with the oracle's serial loop
-    witness = world == 1 and rs.n_batches == 1 and not a.no_cpu_baseline and n_reads >= 2 * WITNESS
+    witness = a.full and world == 1 and rs.n_batches == 1 and not a.no_cpu_baseline and n_reads >= 2 * WITNESS
     # --dump-outputs: the last step's commits are kept the same way (read numbers are the stream's while it is one batch)
     dump = a.dump_outputs if rank == 0 else None
     last_first = (a.steps - 1) * per_step
@@ -879,14 +885,14 @@ def main():
         out["aux"]["probe_accounting"] = {"useful": useful, "executed": executed, "executed_over_useful": executed / useful if useful else None, "beyond_useful": acc,
                                           "share_of_useful": {k_: v_ / useful for k_, v_ in acc.items()} if useful else None,
                                           "note": "tile counts x tile x h (a read's clipped last tile counted whole); streaming: grp_debug_stream_stats — tiles finished in front of an in-launch insert whose probes met a changed slot or whose fingerprints were gone"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(rs, eng, cls, out["phases"], silver, n_reads, m, pop, seeds, k, tile, G, kept=kept if witness else None)
             check = out["cpu_baseline"].pop("oracle_check", None)
             out["aux"]["oracle_check"] = check
             if check and not check["identical"]:
                 print(json.dumps(out), flush=True)
                 raise SystemExit("bench: the GPU path's decisions differ from the oracle's serial loop: %s" % check["first_difference"])
-        if world == 1 and not silver and not a.no_pipeline_shaped:
+        if a.full and world == 1 and not silver and not a.no_pipeline_shaped:
             # What bin/goldrush runs FIRST on the raw reads (bin/goldrush:253-260): --silver_path -M 5
             # -r 0.9 — every silver path starts on empty ID arrays (goldrush_path.cpp:156-187), so the
             # whole pass is the insert-heavy head regime, five times.  Same reads, same filter, IDs

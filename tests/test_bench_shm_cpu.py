@@ -166,3 +166,14 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks():
 
     if not torch.cuda.is_available():
         assert r.returncode != 0 and "no HIP device visible" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_knows_full_and_a_plain_run_does_not_ask_for_it():
+    """`--full` is an option of the benchmark, off by default; the switches under it are still accepted without it (the
+    scripts that pass them go on working).  Decided before torch is imported: runs without a GPU."""
+    r = _bench(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout
+    # the arguments are parsed before the world check refuses the run: an unknown option would be argparse's error (exit 2)
+    for extra in ([], ["--full"], ["--no-cpu-baseline", "--no-pipeline-shaped"], ["--full", "--no-cpu-baseline"]):
+        r = _bench(["--gpus", "1"] + extra, {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
+        assert r.returncode == 1 and "WORLD_SIZE=2" in r.stderr and "unrecognized" not in r.stderr, r.stderr[-500:]

@@ -1,5 +1,5 @@
 """GPU: bench.py keeps the driver's contract — one JSON line from rank 0 with the metric,
-the roofline object of the query kernel and (N = 1) the CPU baseline."""
+the roofline object of the query kernel and, with --full, (N = 1) the CPU baseline."""
 import json
 import os
 import subprocess
@@ -11,8 +11,35 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_line_has_the_contract_fields():
+def _check_headline(d):
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                "roofline", "phases"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "strong"
+    assert d["unit"] == "reads/s" and d["value"] > 0 and d["vs_baseline"] is None and d["data"] == "synthetic" and "workload" in d["config"]
+    assert d["metric"] == "reads/s through GoldRush-Path (hash + miBF query)" and d["dtype"] == "u64"
+    assert abs(d["value"] - 3 * 4096 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    ph = d["phases"]
+    assert ph["head"]["reads"] + ph["steady"]["reads"] == 3 * 4096 and d["config"]["reads_timed"] == 3 * 4096
+
+
+def test_a_plain_run_prints_the_headline_alone():
+    """Without --full the run is setup, warm-up, the timed steps and the line: the passes behind the timed steps (CPU
+    baseline with the oracle's check, the silver-mode pass) are not run and their fields are not in the line; what the
+    timed steps and the setup measured themselves (roofline, phases, aux) is."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "3", "--warmup", "2", "--reads", "60000", "--batch", "4096"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    _check_headline(d)
+    assert "cpu_baseline" not in d and "oracle_check" not in d["aux"] and "pipeline_shaped" not in d["aux"]
+    assert d["roofline"]["line_rate_Gprobes_per_s"] > 0 and d["aux"]["end_to_end"]["classify_s"] > 0 and d["aux"]["counters"]["reads_committed"] == 3 * 4096
+
+
+def test_bench_line_has_the_contract_fields():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--config", "C1", "--steps", "3", "--warmup", "2", "--reads", "60000", "--batch", "4096"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -33,6 +60,10 @@ def test_bench_line_has_the_contract_fields():
     assert ph["head"]["reads"] + ph["steady"]["reads"] == 3 * 4096 and d["config"]["reads_timed"] == 3 * 4096
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == "reads/s" and cb["sample"]
+    # --full: the oracle replayed the witness reads and agrees; the silver-mode pass ran behind the timed steps
+    oc = d["aux"]["oracle_check"]
+    assert oc["identical"] is True and oc["head_reads"] > 0
+    assert d["aux"]["pipeline_shaped"]["reads_consumed"] > 0
 
 
 def test_dump_outputs_hold_the_last_step_and_repeat(tmp_path):

@@ -20,4 +20,4 @@ PY
 }
 timeout 900 python3 bench.py --reads 300000 --steps 2 --warmup 0 --no-cpu-baseline --no-pipeline-shaped > $out/r04_claim_head.json 2> $out/r04_claim_head.err; show $out/r04_claim_head.json head300k
 timeout 900 python3 bench.py --config C4 --reads 300000 --no-cpu-baseline > $out/r04_claim_c4.json 2> $out/r04_claim_c4.err; show $out/r04_claim_c4.json c4_300k
-timeout 900 python3 bench.py --no-cpu-baseline > $out/r04_claim_default.json 2> $out/r04_claim_default.err; show $out/r04_claim_default.json default
+timeout 900 python3 bench.py --full --no-cpu-baseline > $out/r04_claim_default.json 2> $out/r04_claim_default.err; show $out/r04_claim_default.json default

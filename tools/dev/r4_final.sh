@@ -19,5 +19,5 @@ timeout 900 python3 bench.py --reads 300000 --steps 2 --warmup 0 --no-cpu-baseli
 timeout 900 python3 bench.py --config C4 --reads 4000000 --no-cpu-baseline > $out/${tag}_bench_c4_4M.json 2> /dev/null; show $out/${tag}_bench_c4_4M.json c4_4M
 tools/pmc_round.sh ${tag} > $out/${tag}_pmc.log 2>&1
 cp $out/${tag}_pmc_summary.json profiles/ 2>/dev/null
-python3 bench.py > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err; show $out/${tag}_bench_default_flags.json default
+python3 bench.py --full > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err; show $out/${tag}_bench_default_flags.json default
 tools/rocprof_round.sh ${tag} > $out/${tag}_rocprof_round.log 2>&1; tail -9 $out/${tag}_rocprof_round.log | head -8

@@ -12,7 +12,7 @@ t = d["aux"]["timed"]
 print("long_tail reads/s %.0f" % d["value"], "steady %.0f" % d["phases"]["steady"]["reads_per_s"], "head s %.2f" % d["phases"]["head"]["seconds"],
       {k: t.get(k) for k in ("windows", "stream_inserts", "stream_handbacks", "batches")}, {k: (v["launches"], round(v["ms"])) for k, v in d["aux"]["kernel_stats"].items() if v["launches"]}, d["config"].get("read_lengths"))
 PY
-python3 bench.py --no-cpu-baseline > $out/r04_v4_bench_default.json 2> $out/r04_v4_bench_default.err
+python3 bench.py --full --no-cpu-baseline > $out/r04_v4_bench_default.json 2> $out/r04_v4_bench_default.err
 python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r04_v4_bench_default.json").read().strip().splitlines()[-1])

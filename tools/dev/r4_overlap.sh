@@ -26,5 +26,5 @@ for v in "off 0.3" "8 0.3" "16 0.3" "8 0.1"; do
 done
 for v in "off 0.3" "8 0.3"; do
   set -- $v
-  GRP_BATCH_OVERLAP=$1 GRP_BATCH_OVERLAP_P=$2 timeout 900 python3 bench.py --no-cpu-baseline > $out/r04_ovl_default_$1.json 2> /dev/null; show $out/r04_ovl_default_$1.json default_$1
+  GRP_BATCH_OVERLAP=$1 GRP_BATCH_OVERLAP_P=$2 timeout 900 python3 bench.py --full --no-cpu-baseline > $out/r04_ovl_default_$1.json 2> /dev/null; show $out/r04_ovl_default_$1.json default_$1
 done

@@ -7,7 +7,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 tests=${@:-tests/test_gpu_batch.py tests/test_gpu_classifier.py}
 timeout 1500 python3 -m pytest $tests -m gpu -x -q > $out/${tag}_tests.log 2>&1; tail -3 $out/${tag}_tests.log
-timeout 900 python3 bench.py --no-cpu-baseline > $out/${tag}_bench_nocpu.json 2> $out/${tag}_bench_nocpu.err
+timeout 900 python3 bench.py --full --no-cpu-baseline > $out/${tag}_bench_nocpu.json 2> $out/${tag}_bench_nocpu.err
 python3 - $out/${tag}_bench_nocpu.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -25,8 +25,8 @@ timeout 600 python3 tools/gather_ceiling.py $out/${tag}_gather_ceiling.json > /d
 cp $out/${tag}_gather_ceiling.json profiles/ 2>/dev/null
 tools/pmc_round.sh ${tag} > $out/${tag}_pmc.log 2>&1
 cp $out/${tag}_pmc_summary.json profiles/ 2>/dev/null
-timeout 900 python3 bench.py > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err; show $out/${tag}_bench_default_flags.json default
+timeout 900 python3 bench.py --full > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err; show $out/${tag}_bench_default_flags.json default
 tools/rocprof_round.sh ${tag} > $out/${tag}_rocprof_round.log 2>&1; show $out/${tag}_bench_under_rocprof.json under_rocprof; cat $out/${tag}_kernel_trace_timed_region.json
-timeout 600 python3 bench.py --config C1 --no-cpu-baseline > $out/${tag}_bench_c1_full_stream.json 2> /dev/null; show $out/${tag}_bench_c1_full_stream.json c1
+timeout 600 python3 bench.py --full --config C1 --no-cpu-baseline > $out/${tag}_bench_c1_full_stream.json 2> /dev/null; show $out/${tag}_bench_c1_full_stream.json c1
 timeout 900 python3 bench.py --config C4 --reads 4000000 --no-cpu-baseline > $out/${tag}_bench_c4_4M.json 2> /dev/null; show $out/${tag}_bench_c4_4M.json c4_4M
 EXTRA="" tools/dev/r5_silver_prof.sh ${tag} > $out/${tag}_silver_prof.txt 2>&1; tail -16 $out/${tag}_silver_prof.txt

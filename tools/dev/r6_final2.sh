@@ -10,7 +10,7 @@ tools/dev/rank_truth_check.sh C1 300000 ${tag} > $out/${tag}_truth_ranks.txt 2>&
 tools/dev/rank_truth_check.sh C2 ${2:-1000000} ${tag} >> $out/${tag}_truth_ranks.txt 2>&1; tail -1 $out/${tag}_truth_ranks.txt
 tools/pmc_round.sh ${tag} > $out/${tag}_pmc.log 2>&1
 cp $out/${tag}_pmc_summary.json profiles/ 2>/dev/null
-timeout 900 python3 bench.py > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
+timeout 900 python3 bench.py --full > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
 python3 - $out/${tag}_bench_default_flags.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 tag=${1:-r06_final}
 tools/pmc_round.sh ${tag} > $out/${tag}_pmc.log 2>&1
 cp $out/${tag}_pmc_summary.json profiles/ 2>/dev/null
-timeout 900 python3 bench.py > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
+timeout 900 python3 bench.py --full > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
 for i in 1 2 3; do
   timeout 600 python3 bench.py --no-cpu-baseline --no-pipeline-shaped > $out/${tag}_soak_$i.json 2> /dev/null
 done

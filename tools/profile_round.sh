@@ -14,7 +14,7 @@ cp $out/${tag}_gather_ceiling.json profiles/ 2>/dev/null
 tools/pmc_round.sh ${tag} > $out/${tag}_pmc.log 2>&1
 cp $out/${tag}_pmc_summary.json profiles/ 2>/dev/null
 # the driver's command: C2, whole stream, with the like-for-like CPU baseline
-python3 bench.py > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
+python3 bench.py --full > $out/${tag}_bench_default_flags.json 2> $out/${tag}_bench_default_flags.err
 # C1 (BASELINE configs[1]), whole stream
 python3 bench.py --config C1 --no-cpu-baseline --no-pipeline-shaped > $out/${tag}_bench_c1_full_stream.json 2> /dev/null
 tools/rocprof_round.sh ${tag}
@@ -29,7 +29,7 @@ tools/dev/mode_truth_check.sh C2 1500000 > $out/${tag}_truth_modes_c2.txt 2>&1
 # the N = 8 time model from this build's default line and the measured 1-rank / 2-rank pair (counted constants)
 python3 tools/scale_model.py $out/${tag}_bench_default_flags.json --ranks $out/${tag}_ranks_C1_one.json $out/${tag}_ranks_C1_two.json > $out/${tag}_scale_model.txt 2>&1
 # a repeat-rich genome (40 % repeat families): golden pass + pipeline-shaped pass, aux.repeats
-python3 bench.py --repeat-frac 0.4 --no-cpu-baseline > $out/${tag}_bench_repeats.json 2> /dev/null
+python3 bench.py --full --repeat-frac 0.4 --no-cpu-baseline > $out/${tag}_bench_repeats.json 2> /dev/null
 # what a record of the collect pass costs by where its count lives (gather_bench modes 21-37, 50)
 tools/collect_matrix.sh ${tag} > /dev/null 2>&1
 # the drop-in binary end to end: 100 k reads of C1 as a 5 GB FASTQ, silver and golden, reads kept on the device / second parse
