@@ -131,7 +131,7 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
   const uint32_t gunit = gunit0 + blockIdx.x;
   const uint32_t unit = gunit / hn;
   const uint32_t s = gunit - unit * hn;
-  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
+  const uint32_t parts = gr::geom::tile_parts(frames_per_tile(sd, tile_len));
   const uint32_t jb = batch_unit_jb(b, unit, parts);
   const uint32_t* e = b.ins + (size_t)(jb >> 8) * 6;
   const uint32_t read_idx = e[0], tile_start = e[1];
@@ -143,10 +143,8 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
   const uint32_t blk_unit0 = e[5] + (tj / b.block_tiles) * b.block_tiles * parts;
   const uint32_t blk_unit1 = min(blk_unit0 + b.block_tiles * parts, e[5] + (e[2] - e[1]) * parts);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
 
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
@@ -534,10 +532,8 @@ k_ovl_sample(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, ui
   const uint32_t r = rd.tile_read[t];
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   if (threadIdx.x == 0) {
@@ -883,13 +879,7 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
     const uint64_t gunits = units * c->params.h;
     for (uint64_t u0 = 0; u0 < gunits; u0 += MAX_GRID_WGS) {
       const uint32_t nb = (uint32_t)std::min<uint64_t>(gunits - u0, MAX_GRID_WGS);
-      if (long_span(c)) {
-        DISPATCH_H(c->params.h, (k_batch_collect<HH, GRP_WT_LONG><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
-      } else if (c->uniform_weight == 16) {
-        DISPATCH_H(c->params.h, (k_batch_collect<HH, 16><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
-      } else {
-        DISPATCH_H(c->params.h, (k_batch_collect<HH, 0><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
-      }
+      DISPATCH_HW(c, (k_batch_collect<HH, WW><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, b, (uint32_t)u0)));
     }
     HIP_TRY(c, hipGetLastError());
     // k_batch_apply does nothing when the chains overflowed (counters[1] > ovf_cap): the caller
@@ -953,13 +943,7 @@ grp_window_overlap(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   for (uint64_t b0 = 0; b0 < nt; b0 += MAX_GRID_WGS) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(nt - b0, MAX_GRID_WGS);
-    if (long_span(c)) {
-      k_ovl_sample<GRP_WT_LONG><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);
-    } else if (c->uniform_weight == 16) {
-      k_ovl_sample<16><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);
-    } else {
-      k_ovl_sample<0><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift);
-    }
+    DISPATCH_W(c, (k_ovl_sample<WW><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, c->params.tile, t0 + b0, ob.d_samples + b0 * OVL_CAP_T, ob.d_n + b0, ovl_shift)));
   }
   k_ovl_mark<<<dim3(count), dim3(THREADS), 0, c->stream>>>(r->dev, first, t0, ob.d_samples, ob.d_n, ob.d_tab, (uint32_t)(tab - 1));
   k_ovl_count<<<dim3(count), dim3(THREADS), 0, c->stream>>>(r->dev, first, t0, ob.d_samples, ob.d_n, ob.d_tab, (uint32_t)(tab - 1), threshold, ob.d_prev);

@@ -174,13 +174,17 @@ stage_bases(uint32_t* sBases, const uint32_t* __restrict__ packed, uint64_t word
   return b0 & 15u;
 }
 
-// Frames of a full tile.  The tile string is tile + k - 1 bases with the reference's -k (read_hashing.cpp:44-45), and a
-// frame exists while seed 0, the shortest, can roll (multiLensfrHashIterator.hpp:29-68): tile + k - span0 frames, one
-// more than tile at odd k, where seed 0 spans k - 1 (spaced_seeds.cpp:27-66).  A tile of Lp bases has Lp - span0 + 1.
+// The tile geometry (host/gr_tile_geom.hpp) of the seeds on the device
 __device__ __forceinline__ uint32_t
 frames_per_tile(const DevSeeds* __restrict__ sd, uint32_t tile_len)
 {
-  return tile_len + sd->k - sd->span[0];
+  return gr::geom::frames_per_tile(tile_len, sd->k, sd->span[0]);
+}
+
+__device__ __forceinline__ gr::geom::TileExtent
+tile_extent(const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t len, uint32_t ti)
+{
+  return gr::geom::tile_extent(tile_len, sd->k, sd->span[0], len, ti);
 }
 
 // ---- wave / block reductions -------------------------------------------------
@@ -197,7 +201,8 @@ wave_sum(uint32_t v)
 
 // ---- fill ------------------------------------------------------------------------
 
-template<int H>
+// WT: 0, or GRP_WT_LONG for seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H, int WT = 0>
 __global__ void __launch_bounds__(THREADS)
 k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk_begin)
 {
@@ -237,78 +242,7 @@ k_fill(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk
         mask[j][s] = 0;
         widx[j][s] = 0;
         if (ok) {
-          uint64_t hv = seed_hash(sTab, sd, s, window_at(sBases, boff + i));
-          uint64_t pos = grp_mod_m(hv, f.m, f.m_inv);
-          widx[j][s] = pos >> 5;
-          mask[j][s] = 1u << (uint32_t)(pos & 31u);
-        }
-      }
-    }
-    // test first (plain load), set only where needed: the filter saturates and
-    // most probes find their bit already set
-#pragma unroll
-    for (int j = 0; j < FR; ++j) {
-#pragma unroll
-      for (int s = 0; s < H; ++s) {
-        val[j][s] = mask[j][s] ? words[widx[j][s]] : 0xFFFFFFFFu;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < FR; ++j) {
-#pragma unroll
-      for (int s = 0; s < H; ++s) {
-        if (mask[j][s] & ~val[j][s]) {
-          atomicOr(&words[widx[j][s]], mask[j][s]);
-        }
-      }
-    }
-  }
-}
-
-// k_fill for seeds of spans beyond 64 bases (DevSeeds::wide == 2): the same body with seed_hash_long.  A copy, not a
-// shared inline body: sharing one moved k_fill<5..8>'s scalar registers (+4 SGPRs), and the forms of spans up to 64
-// keep their code.
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_fill_long(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint64_t chunk_begin)
-{
-  extern __shared__ uint4 smem4[];
-  ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  const uint32_t hn = frame_seeds<H>(sd);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
-
-  const uint64_t chunk = chunk_begin + blockIdx.x;
-  const uint32_t r = rd.chunk_read[chunk];
-  const uint32_t ci = (uint32_t)(chunk - rd.chunk0[r]);
-  const uint32_t len = rd.len[r];
-  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
-  const uint32_t npos = len - s0 + 1u; // chunk exists => len >= s0 + h - 1
-  const uint32_t p0 = ci * FILL_CHUNK;
-  const uint32_t np = min(FILL_CHUNK, npos - p0);
-
-  load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
-  __syncthreads();
-
-  uint32_t* words = f.bv;
-  constexpr int FR = (H <= GRP_H_GROUP) ? 4 : 2; // the many-seed form: 2 x 16 probes in flight per lane (4 x 16 spill)
-  for (uint32_t i0 = threadIdx.x; i0 < np; i0 += THREADS * FR) {
-    uint64_t widx[FR][H];
-    uint32_t mask[FR][H];
-    uint32_t val[FR][H];
-#pragma unroll
-    for (int j = 0; j < FR; ++j) {
-      const uint32_t i = i0 + j * THREADS;
-      const uint32_t p = p0 + i;
-#pragma unroll
-      for (int s = 0; s < H; ++s) {
-        // seed s is valid at read position p iff p + span_s <= len
-        // (stale re-inserts of the iterator set the same bit again)
-        const bool ok = seed_on<H>(s, hn) && (i < np) && (p + sd->span[s] <= len);
-        mask[j][s] = 0;
-        widx[j][s] = 0;
-        if (ok) {
-          uint64_t hv = seed_hash_long(sTab, sd, s, window_at(sBases, boff + i));
+          uint64_t hv = seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + i));
           uint64_t pos = grp_mod_m(hv, f.m, f.m_inv);
           widx[j][s] = pos >> 5;
           mask[j][s] = 1u << (uint32_t)(pos & 31u);
@@ -1565,16 +1499,14 @@ __device__ inline void
 insert_collect_unit(const DevFilter& f, const DevReads& rd, const DevSeeds* __restrict__ sd, const ulonglong2* sTab, uint32_t* sBases, uint32_t* sWave /* [THREADS / 64 + 1] */, uint32_t tile_len,
                     uint32_t read_idx, uint32_t tile_start, uint32_t block_tiles, const InsertTable& tb, uint32_t* counter, uint32_t unit)
 {
-  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
+  const uint32_t parts = gr::geom::tile_parts(frames_per_tile(sd, tile_len));
   const uint32_t tj = unit / parts; // tile inside the inserted range
   const uint32_t ti = tile_start + tj;
   const uint32_t part = unit % parts;
   const unsigned long long block_bit = 1ull << (tj / block_tiles);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
 
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
   __syncthreads();
@@ -1992,7 +1924,7 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
   const uint32_t par = (ev >> 1) & 1u;
   const uint32_t members = ldc(sc.ctl + SCT_MEMBERS); // the workgroups this insert waits for (those that had begun when it was published)
   uint32_t* const bar = sc.ctl + SCT_BAR + (par * 2u) * 32u;
-  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
+  const uint32_t parts = gr::geom::tile_parts(frames_per_tile(sd, tile_len));
   const uint32_t n_units = (tile_end - tile_start) * parts;
   const unsigned long long t_enter = wall_clock64(); // workgroup 0 leaves the phase times of the insert for the host's trace
   // collect
@@ -2606,11 +2538,8 @@ k_query(DevFilter f,
     }
   }
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  // tile string = seq.substr(ti*tile, tile + k - 1)   (read_hashing.cpp:44-45); frames while seed 0 can roll
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
 
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   for (uint32_t i = threadIdx.x; i < hist_cap; i += THREADS) {
@@ -2671,7 +2600,7 @@ k_query(DevFilter f,
                                                                                                  // 0 in the many-seed form: every seed hashed on its own)
   constexpr uint32_t OV = (uint32_t)H - 1u, USE = 64u - OV;
   static_assert(THREADS == 256, "the helper-lane layout below is written for four waves per workgroup (my_wave == 3 is the last one, FBH = 3 * USE + 64)");
-  constexpr uint32_t FBH = 3u * USE + 64u;
+  constexpr uint32_t FBH = gr::geom::helper_pass_frames(H);
   const uint32_t ftile = frames_per_tile(sd, tile_len);
   const bool helper = n_left != 0u && (ftile + FBH * FR - 1u) / (FBH * FR) == (ftile + THREADS * FR - 1u) / (THREADS * FR);
   const uint32_t FB = helper ? FBH : (uint32_t)THREADS; // frames per block of THREADS lanes
@@ -3327,14 +3256,12 @@ insert_tiles(const DevFilter& f,
 
   const uint32_t r = read_idx;
   // one frame per thread: `parts` workgroups share a tile
-  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
+  const uint32_t parts = gr::geom::tile_parts(frames_per_tile(sd, tile_len));
   const uint32_t ti = tile_start + blockIdx.x / parts;
   const uint32_t part = blockIdx.x % parts;
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
 
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
@@ -3392,7 +3319,8 @@ insert_tiles(const DevFilter& f,
   }
 }
 
-template<int H>
+// WT: 0, or GRP_WT_LONG for seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H, int WT = 0>
 __global__ void __launch_bounds__(THREADS)
 k_insert(DevFilter f,
          DevReads rd,
@@ -3405,24 +3333,7 @@ k_insert(DevFilter f,
          uint64_t dedup_mask,
          unsigned long long epoch_tag)
 {
-  insert_tiles<H, 0>(f, rd, sd, tile_len, read_idx, tile_start, id, dedup, dedup_mask, epoch_tag);
-}
-
-// seeds of spans beyond 64 bases (DevSeeds::wide == 2)
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_insert_long(DevFilter f,
-              DevReads rd,
-              const DevSeeds* __restrict__ sd,
-              uint32_t tile_len,
-              uint32_t read_idx,
-              uint32_t tile_start,
-              uint32_t id,
-              unsigned long long* __restrict__ dedup,
-              uint64_t dedup_mask,
-              unsigned long long epoch_tag)
-{
-  insert_tiles<H, GRP_WT_LONG>(f, rd, sd, tile_len, read_idx, tile_start, id, dedup, dedup_mask, epoch_tag);
+  insert_tiles<H, WT>(f, rd, sd, tile_len, read_idx, tile_start, id, dedup, dedup_mask, epoch_tag);
 }
 
 // ---- whole-read insert (all ID blocks of a read in two launches) ------------------
@@ -3571,10 +3482,8 @@ debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t 
   const uint32_t hn = frame_seeds<H>(sd);
   uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
   const uint32_t len = rd.len[read_idx];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = tile_idx * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, tile_idx);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[read_idx], len, start, Lp);
   __syncthreads();
@@ -3594,18 +3503,10 @@ debug_tile_hashes(const DevReads& rd, const DevSeeds* __restrict__ sd, uint32_t 
   }
 }
 
-template<int H>
+// WT: 0, or GRP_WT_LONG for seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H, int WT = 0>
 __global__ void __launch_bounds__(THREADS)
 k_debug_tile_hashes(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
 {
-  debug_tile_hashes<H, 0>(rd, sd, tile_len, read_idx, tile_idx, out, cap);
+  debug_tile_hashes<H, WT>(rd, sd, tile_len, read_idx, tile_idx, out, cap);
 }
-
-// seeds of spans beyond 64 bases (DevSeeds::wide == 2)
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_debug_tile_hashes_long(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint32_t read_idx, uint32_t tile_idx, uint64_t* __restrict__ out, uint64_t cap)
-{
-  debug_tile_hashes<H, GRP_WT_LONG>(rd, sd, tile_len, read_idx, tile_idx, out, cap);
-}
-

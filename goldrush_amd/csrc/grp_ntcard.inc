@@ -16,7 +16,8 @@ namespace {
 constexpr uint32_t NTC_RBITS = 27; // nts::rBits (ntcard.hpp:34)
 constexpr uint32_t NTC_NSAMP = 2;  // nts::nSamp (ntcard.hpp:38)
 
-template<int H>
+// WT: 0, or GRP_WT_LONG for seeds of spans beyond 64 bases (DevSeeds::wide == 2)
+template<int H, int WT = 0>
 __global__ void __launch_bounds__(THREADS)
 k_ntcard(DevReads rd,
          const DevSeeds* __restrict__ sd,
@@ -56,72 +57,7 @@ k_ntcard(DevReads rd,
       if (p + span > len) {
         continue; // no window of seed s starts here
       }
-      const uint64_t hv = seed_hash(sTab, sd, s, w);
-      // ntComp (:81-94)
-      uint32_t ind = NTC_NSAMP;
-      if ((hv >> (63u - sbits)) == 1ull) {
-        ind = 0;
-      }
-      if ((hv >> (64u - sbits)) == smask) {
-        ind = 1;
-      }
-      if (ind < NTC_NSAMP) {
-        // the seed's last window is counted again for every frame it stays stale:
-        // span_s - span_0 frames for a plain read, or what the host computed
-        uint32_t times = 1u;
-        if (p + span == len) {
-          times += extra ? extra[(size_t)(r - first) * hn + s] : (span - s0);
-        }
-        const uint64_t slot = (((uint64_t)s * NTC_NSAMP + ind) << NTC_RBITS) | (hv & ((1ull << NTC_RBITS) - 1ull));
-        atomicAdd(&counters[slot], times);
-      }
-    }
-  }
-}
-
-// k_ntcard for seeds of spans beyond 64 bases (DevSeeds::wide == 2): the same body with seed_hash_long (a copy, as
-// k_fill_long: a shared inline body moved k_ntcard<5..8>'s scalar registers)
-template<int H>
-__global__ void __launch_bounds__(THREADS)
-k_ntcard_long(DevReads rd,
-              const DevSeeds* __restrict__ sd,
-              const uint2* __restrict__ chunks, // (read, chunk index inside the read)
-              const uint32_t* __restrict__ extra, // [read - first][h] stale repeats of the last window, or nullptr
-              uint32_t first,
-              uint32_t* __restrict__ counters,
-              uint32_t sbits)
-{
-  extern __shared__ uint4 smem4[];
-  ulonglong2* sTab = reinterpret_cast<ulonglong2*>(smem4);
-  const uint32_t hn = frame_seeds<H>(sd);
-  uint32_t* sBases = reinterpret_cast<uint32_t*>(sTab + hn * sd->wmax * 4u);
-
-  const uint2 ck = chunks[blockIdx.x];
-  const uint32_t r = ck.x;
-  const uint32_t len = rd.len[r];
-  const uint32_t s0 = sd->span[0];     // the shortest seed: k, or k - 1 at odd k
-  const uint32_t npos = len - s0 + 1u; // listed => len >= s0
-  const uint32_t p0 = ck.y * FILL_CHUNK;
-  const uint32_t np = min(FILL_CHUNK, npos - p0);
-
-  load_tab(sTab, sd);
-  const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, p0, np + s0 + hn - 2u);
-  __syncthreads();
-
-  const uint64_t smask = (1ull << (sbits - 1u)) - 1ull; // ntcard.hpp:182
-  for (uint32_t i = threadIdx.x; i < np; i += THREADS) {
-    const uint32_t p = p0 + i;
-    const Win w = window_at(sBases, boff + i);
-#pragma unroll
-    for (int s = 0; s < H; ++s) {
-      if (!seed_on<H>(s, hn)) {
-        continue;
-      }
-      const uint32_t span = sd->span[s];
-      if (p + span > len) {
-        continue; // no window of seed s starts here
-      }
-      const uint64_t hv = seed_hash_long(sTab, sd, s, w);
+      const uint64_t hv = seed_hash_t<WT>(sTab, sd, s, w);
       // ntComp (:81-94)
       uint32_t ind = NTC_NSAMP;
       if ((hv >> (63u - sbits)) == 1ull) {
@@ -230,15 +166,8 @@ grp_ntcard_add(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, c
   const size_t lds = tab_bytes(c) + bases_bytes(FILL_CHUNK + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_NTCARD, hashes);
-    if (long_span(c)) {
-      DISPATCH_H(c->params.h,
-                 (k_ntcard_long<HH><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
-                   r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
-    } else {
-      DISPATCH_H(c->params.h,
-                 (k_ntcard<HH><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
-                   r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
-    }
+    DISPATCH_H_SPAN(c, (k_ntcard<HH, WW><<<dim3((uint32_t)chunks.size()), dim3(THREADS), lds, c->stream>>>(
+                         r->dev, c->d_seeds, c->d_ntc_chunks, stale_extra ? c->d_ntc_extra : nullptr, first, c->d_ntc, c->ntc_sbits)));
     HIP_TRY(c, hipGetLastError());
   }
   // `chunks` (and the caller's array) must outlive the copies

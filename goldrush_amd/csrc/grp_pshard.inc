@@ -52,9 +52,8 @@ k_ps_partition(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t len = rd.len[r];
   const uint32_t k = sd->k;
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const gr::geom::TileExtent ext = gr::geom::tile_extent(tile_len, k, k, len, ti); // (seed 0 spans k here: the launch refuses anything else)
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   if (threadIdx.x < PS_MAX_OWNERS) {
@@ -140,9 +139,7 @@ k_ps_vote(DevReads rd, const DevSeeds* __restrict__ sd, uint32_t tile_len, uint6
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t len = rd.len[r];
   const uint32_t k = sd->k;
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const uint32_t frames = gr::geom::tile_extent(tile_len, k, k, len, ti).frames; // (seed 0 spans k here: the launch refuses anything else)
   for (uint32_t i = threadIdx.x; i < hist_cap; i += THREADS) {
     sKeys[i] = 0u;
     if (i < hist_cap / 2u) {
@@ -296,9 +293,8 @@ k_touch_probe(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t len = rd.len[r];
   const uint32_t k = sd->k;
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= k) ? (Lp - k + 1u) : 0u;
+  const gr::geom::TileExtent ext = gr::geom::tile_extent(tile_len, k, k, len, ti); // (seed 0 spans k here: the launch refuses anything else)
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
   load_tab(sTab, sd);
   const uint32_t boff = stage_bases(sBases, rd.packed, rd.word_off[r], len, start, Lp);
   __syncthreads();

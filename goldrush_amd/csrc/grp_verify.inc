@@ -172,7 +172,7 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
   const uint32_t r = rd.tile_read[t];
   const uint32_t ti = (uint32_t)(t - rd.tile0[r]);
   const uint32_t reader = r - bv.first;
-  const uint32_t parts = (frames_per_tile(sd, tile_len) + THREADS - 1) / THREADS;
+  const uint32_t parts = gr::geom::tile_parts(frames_per_tile(sd, tile_len));
   // only the tiles this batch inserted have records; the others are k_query<.., VER>'s
   uint32_t unit0 = 0;
   {
@@ -187,10 +187,8 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
     unit0 = e[5] + (ti - e[1]) * parts;
   }
   const uint32_t len = rd.len[r];
-  const uint32_t k = sd->k, s0 = sd->span[0];
-  const uint32_t start = ti * tile_len;
-  const uint32_t Lp = min(tile_len + k - 1u, len - start);
-  const uint32_t frames = (Lp >= s0) ? (Lp - s0 + 1u) : 0u;
+  const gr::geom::TileExtent ext = tile_extent(sd, tile_len, len, ti);
+  const uint32_t start = ext.start, Lp = ext.Lp, frames = ext.frames;
 
   for (uint32_t i = threadIdx.x; i < VF_DCAP; i += THREADS) {
     dKeys[i] = 0u;
@@ -437,7 +435,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   c->carry.valid = false;
   // Per read of the batch: its entry in the insert list (the kernels tell from it which tiles have records).  The
   // floors travel in the same page-locked block: one copy per call, nothing per tile on the host.
-  const uint32_t tile = c->params.tile, k = c->params.k, h = c->params.h, s0 = span0(c), ftile = tile_frames(c);
+  const uint32_t h = c->params.h, ftile = tile_frames(c);
   if ((uint64_t)count + total > br.vf_stage_cap) {
     if (br.h_vf_stage) {
       (void)hipHostFree(br.h_vf_stage);
@@ -468,8 +466,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
         const uint32_t ntile = (uint32_t)(r->tile0[rd_i + 1] - r->tile0[rd_i]);
         uint64_t fr = (uint64_t)(te - ts) * ftile; // only a read's last tile can be clipped
         if (te == ntile && ntile) {
-          const uint32_t Lp = std::min(tile + k - 1, r->len[rd_i] - (ntile - 1) * tile);
-          fr -= ftile - (Lp >= s0 ? Lp - s0 + 1 : 0);
+          fr -= ftile - tile_extent(c, r->len[rd_i], ntile - 1).frames;
         }
         r_records += fr * h;
         recorded_tiles += te - ts;
@@ -518,16 +515,8 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       vf.read_ins = d_read_ins;
       vf.n_reads = count;
       Timer t(c, GRP_K_VERIFY, r_records);
-      if (long_span(c)) {
-        DISPATCH_H(c->params.h, (k_batch_delta<HH, GRP_WT_LONG><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
-                                                                                                                              reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
-      } else if (c->uniform_weight == 16) {
-        DISPATCH_H(c->params.h, (k_batch_delta<HH, 16><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
-                                                                                                                     reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
-      } else {
-        DISPATCH_H(c->params.h, (k_batch_delta<HH, 0><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
-                                                                                                                    reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
-      }
+      DISPATCH_HW(c, (k_batch_delta<HH, WW><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
+                                                                                                             reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
       HIP_TRY(c, hipGetLastError());
     }
     const QueryGeom g = query_geom(c, false);
@@ -538,7 +527,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       bq.skip_read_ins = d_read_ins;
       bq.skip_reads = count;
       c->view = &bq;
-      DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, nt_batch, t0, nullptr, g, so.list_cap));
+      lrc = launch_query(c, r, nt_batch, t0, nullptr, g, so.list_cap);
       c->view = nullptr;
       if (lrc != GRP_OK) {
         return lrc;
@@ -547,7 +536,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
     }
     if (extra) { // the reads behind the batch: the plain query (the next window's first decisions)
       Timer t(c, GRP_K_QUERY, x_probes);
-      DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, nt_all - nt_batch, t0, nullptr, g, so.list_cap, nullptr, nullptr, 0, nullptr, (uint32_t)nt_batch, false, true));
+      lrc = launch_query(c, r, nt_all - nt_batch, t0, nullptr, g, so.list_cap, nullptr, nullptr, 0, nullptr, (uint32_t)nt_batch, false, true);
       if (lrc != GRP_OK) {
         return lrc;
       }
@@ -564,7 +553,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       bf.redo_count = reinterpret_cast<const unsigned long long*>(so.d_qctr) + 4;
       c->view = &bf;
       const QueryGeom gf = query_geom(c, true);
-      DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, VERIFY_REDO_ON_DEVICE, t0, so.d_flag_idx, gf, so.list_cap));
+      lrc = launch_query(c, r, VERIFY_REDO_ON_DEVICE, t0, so.d_flag_idx, gf, so.list_cap);
       c->view = nullptr;
       if (lrc != GRP_OK) {
         return lrc;

@@ -15,9 +15,10 @@
 //   k_insert      hash -> rank -> exact per-call rank dedup -> reservoir rule
 //                 (MIBFConstructSupport.hpp:247-283)
 // Seeds of spans 65 .. 256 bases (DevSeeds::wide == 2, long_span) run their own
-// instantiations of every hashing kernel (WT == GRP_WT_LONG, k_fill_long, k_ntcard_long,
-// k_insert_long, k_debug_tile_hashes_long); the forms of spans up to 64 are untouched.
+// instantiation of every hashing kernel, WT == GRP_WT_LONG (DISPATCH_H_SPAN / DISPATCH_HW
+// pick it); the forms of spans up to 64 are untouched.
 #include "grp_device.h"
+#include "host/gr_tile_geom.hpp"
 #include "host/gr_tiles_core.hpp"
 
 #include "../../include/grpath.h"
@@ -389,7 +390,7 @@ constexpr uint32_t FILL_CHUNK = 2048; // read positions per fill workgroup
 constexpr uint64_t LIST_PREFIX = 8192; // list entries copied back together with the tile summaries
 constexpr uint32_t SMALL_TILES = 512;  // windows up to this many tiles use the direct (zero-copy) path
 constexpr uint32_t SMALL_STRIDE = 32;  // list entries per tile in the direct path
-constexpr int THREADS = 256;
+constexpr int THREADS = gr::geom::WG_THREADS;
 // A HIP grid holds fewer than 2^32 work-items per dimension (larger ones are truncated
 // modulo 2^32 without an error): no launch of 256-lane workgroups exceeds this many
 constexpr uint32_t MAX_GRID_WGS = 1u << 22;
@@ -514,16 +515,15 @@ bases_bytes(uint32_t nbases)
 }
 
 // seeds of spans beyond 64 bases (DevSeeds::wide == 2): every hashing kernel runs its long-span form (WT ==
-// GRP_WT_LONG, or the *_long kernels), the only code that reads bases past the 64th of a frame
+// GRP_WT_LONG), the only code that reads bases past the 64th of a frame
 inline bool
 long_span(const grp_ctx* c)
 {
   return c->h_seeds.wide > 1u;
 }
 
-// span of seed 0, the shortest seed: k, or k - 1 at odd k (make_seed_pattern, spaced_seeds.cpp:27-66).  The tile string
-// stays tile + k - 1 bases (read_hashing.cpp:44-45), so a full tile has tile + k - span0 frames (grp_kernels.inc
-// tile_frames); the longest seed spans span0 + h - 1 bases, the minimum length of a read that takes part in the fill.
+// span of seed 0, the shortest seed: k, or k - 1 at odd k.  The tile geometry that follows from it is
+// host/gr_tile_geom.hpp's; these are its functions for a context.
 inline uint32_t
 span0(const grp_ctx* c)
 {
@@ -533,14 +533,20 @@ span0(const grp_ctx* c)
 inline uint32_t
 tile_frames(const grp_ctx* c)
 {
-  return c->params.tile + c->params.k - span0(c);
+  return gr::geom::frames_per_tile(c->params.tile, c->params.k, span0(c));
 }
 
-// units of THREADS frames per tile of the kernels that walk a tile that way (k_insert, k_insert_collect, k_batch_collect)
+// (k_insert, k_insert_collect, k_batch_collect walk a tile in these units)
 inline uint32_t
 tile_parts(const grp_ctx* c)
 {
-  return (tile_frames(c) + THREADS - 1) / THREADS;
+  return gr::geom::tile_parts(tile_frames(c));
+}
+
+inline gr::geom::TileExtent
+tile_extent(const grp_ctx* c, uint32_t len, uint32_t ti)
+{
+  return gr::geom::tile_extent(c->params.tile, c->params.k, span0(c), len, ti);
 }
 
 template<typename K>
@@ -595,6 +601,32 @@ decide_lds_bytes(uint32_t lds_tiles)
     DISPATCH_H_CASES_FEW(CALL)                                                                                         \
     default: return set_err(c, GRP_ERR_INVALID, "h=%u has no kernel form here", (unsigned)(hval));                    \
   }
+
+// The hash form of a launch, the kernels' WT parameter: GRP_WT_LONG for seeds of spans beyond 64 bases, the only form
+// that reads them; else 16 for seeds that all have make_seed_pattern's default weight, where the kernel has that form —
+// the care loop unrolled, in the kernels whose launches are latency-bound (k_insert_collect, k_batch_collect,
+// k_batch_delta, k_ovl_sample); else 0, run-time weights.
+inline int
+hash_form(const grp_ctx* c, bool has_16)
+{
+  return long_span(c) ? GRP_WT_LONG : (has_16 && c->uniform_weight == 16) ? 16 : 0;
+}
+
+// CALL with WW, the hash form: DISPATCH_W_SPAN for the kernels of forms {0, LONG}, DISPATCH_W for those that have the
+// weight-16 form as well (only the forms named here are compiled).  DISPATCH_H_SPAN / DISPATCH_HW: with HH beside it.
+#define DISPATCH_W_SPAN(cc, CALL)                                                                                      \
+  switch (hash_form(cc, false)) {                                                                                      \
+    case GRP_WT_LONG: { constexpr int WW = GRP_WT_LONG; CALL; } break;                                                 \
+    default: { constexpr int WW = 0; CALL; } break;                                                                    \
+  }
+#define DISPATCH_W(cc, CALL)                                                                                           \
+  switch (hash_form(cc, true)) {                                                                                       \
+    case GRP_WT_LONG: { constexpr int WW = GRP_WT_LONG; CALL; } break;                                                 \
+    case 16: { constexpr int WW = 16; CALL; } break;                                                                   \
+    default: { constexpr int WW = 0; CALL; } break;                                                                    \
+  }
+#define DISPATCH_H_SPAN(cc, CALL) DISPATCH_W_SPAN(cc, DISPATCH_H((cc)->params.h, CALL))
+#define DISPATCH_HW(cc, CALL) DISPATCH_W(cc, DISPATCH_H((cc)->params.h, CALL))
 
 // decision buffers of a slot: [64 bytes of counters][cap decisions], on the device and page-locked on the host
 int
@@ -797,7 +829,7 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
         const char* e = getenv("GRP_STREAM_KEEP");
         return e ? std::max(0, std::min(2, atoi(e))) : 2;
       }();
-      const uint32_t fb = 3u * (64u - ((uint32_t)HH - 1u)) + 64u; // frames per pass at least (k_query: the helper-lane layout)
+      const uint32_t fb = gr::geom::helper_pass_frames(HH); // frames per pass at least (k_query: the helper-lane layout)
       const uint32_t passes = (tile_frames(c) + fb - 1u) / fb;
       const uint32_t words = passes * (uint32_t)THREADS * (uint32_t)HH;
       const int want_cu = std::min(per_cu, 3);
@@ -849,18 +881,17 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
   return go(k_query<HH, SFR, QWT, false>);
 }
 
-// QWT: the hash form of every k_query the launch may take — 0, or GRP_WT_LONG for seeds of spans beyond 64 bases
-template<int HH>
+// The query of `n_launch` tiles in the form of the context's h and hash form (QWT of launch_query_wt: 0, or GRP_WT_LONG
+// for seeds of spans beyond 64 bases)
 int
 launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles = nullptr, grp_id_count* out_lists = nullptr, uint32_t direct_stride = 0, const DevStreamCtl* stream_ctl = nullptr,
              uint32_t blk0 = 0,          // no tile list: the launch covers tiles [blk0, blk0 + n_launch) of the window
              bool list_flags = false,    // a tile list that is NOT the redo of flagged tiles: flagged tiles are collected as without a list
              bool plain = false)         // the plain query even while a batch view is set (the reads behind the batch)
 {
-  if (long_span(c)) {
-    return launch_query_wt<HH, GRP_WT_LONG>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain);
-  }
-  return launch_query_wt<HH, 0>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain);
+  int rc = GRP_OK;
+  DISPATCH_H_SPAN(c, (rc = launch_query_wt<HH, WW>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain)));
+  return rc;
 }
 
 int
@@ -1642,11 +1673,7 @@ grp_bv_insert(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
   for (uint64_t b = ch0; b < ch1;) {
     uint32_t nb = (uint32_t)std::min<uint64_t>(ch1 - b, MAX_GRID_WGS);
     Timer t(c, GRP_K_FILL, b == ch0 ? probes : 0);
-    if (long_span(c)) {
-      DISPATCH_H(c->params.h, (k_fill_long<HH><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
-    } else {
-      DISPATCH_H(c->params.h, (k_fill<HH><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
-    }
+    DISPATCH_H_SPAN(c, (k_fill<HH, WW><<<dim3(nb), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, b)));
     HIP_TRY(c, hipGetLastError());
     b += nb;
   }
@@ -1928,17 +1955,14 @@ ensure_dev(grp_ctx* c, T*& p, uint64_t& cap, uint64_t want)
 uint64_t
 count_probes(const grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
 {
-  const uint32_t tile = c->params.tile, k = c->params.k, s0 = span0(c);
   uint64_t probes = 0;
   for (uint32_t i = first; i < first + count; ++i) {
-    const uint32_t ntile = r->len[i] / tile;
+    const uint32_t ntile = r->len[i] / c->params.tile;
     if (ntile == 0) {
       continue;
     }
-    // all tiles but the last have tile + k - span0 frames; the last may be clipped
-    const uint32_t start = (ntile - 1) * tile;
-    const uint32_t Lp = std::min(tile + k - 1, r->len[i] - start);
-    probes += ((uint64_t)(ntile - 1) * tile_frames(c) + (Lp - s0 + 1)) * c->params.h;
+    // all tiles but the last are full; the last may be clipped
+    probes += ((uint64_t)(ntile - 1) * tile_frames(c) + tile_extent(c, r->len[i], ntile - 1).frames) * c->params.h;
   }
   return probes;
 }
@@ -1968,8 +1992,7 @@ enqueue_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, ui
   }
   const QueryGeom g = query_geom(c, false);
   Timer t(c, GRP_K_QUERY, q.probes);
-  int lrc = GRP_OK;
-  DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, q.nt, q.t0, nullptr, g, list_cap));
+  int lrc = launch_query(c, r, q.nt, q.t0, nullptr, g, list_cap);
   if (lrc != GRP_OK) {
     return lrc;
   }
@@ -1993,8 +2016,7 @@ enqueue_redo_flagged(grp_ctx* c, const grp_reads* r, uint64_t list_cap, QueryRun
   HIP_TRY(c, hipMemcpyAsync(c->q->d_qctr, cursor, sizeof(cursor), hipMemcpyHostToDevice, c->stream));
   const QueryGeom g = query_geom(c, true);
   Timer t(c, GRP_K_QUERY, 0);
-  int lrc = GRP_OK;
-  DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, q.flagged, q.t0, c->q->d_flag_idx, g, list_cap));
+  int lrc = launch_query(c, r, q.flagged, q.t0, c->q->d_flag_idx, g, list_cap);
   if (lrc != GRP_OK) {
     return lrc;
   }
@@ -2064,8 +2086,7 @@ grp_query_tiles(grp_ctx* c,
     {
       const QueryGeom g = query_geom(c, false);
       Timer t(c, GRP_K_QUERY_LAT, probes);
-      int lrc = GRP_OK;
-      DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, nt, t0, nullptr, g, (uint64_t)SMALL_TILES * SMALL_STRIDE, c->dmap_small_tiles, c->dmap_small_lists, SMALL_STRIDE));
+      int lrc = launch_query(c, r, nt, t0, nullptr, g, (uint64_t)SMALL_TILES * SMALL_STRIDE, c->dmap_small_tiles, c->dmap_small_lists, SMALL_STRIDE);
       if (lrc != GRP_OK) {
         return lrc;
       }
@@ -2796,15 +2817,14 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
     const QueryGeom g = query_geom(c, false);
     {
       Timer t(c, GRP_K_QUERY, 0); // the probes actually executed are added at _end
-      int lrc = GRP_OK;
-      DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc));
+      int lrc = launch_query(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc);
       if (lrc == GRP_ERR_BUSY && sl.resumable) {
         // the runtime cannot keep every workgroup of the window resident (the device is shared): the window is
         // begun in its classic form — it ends where it parks, grp_classify_stream_insert says GRP_ERR_STATE
         sl.resumable = false;
         sc.ctl = nullptr;
         ++c->n_stream_coop_refused;
-        DISPATCH_H(c->params.h, lrc = launch_query<HH>(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc));
+        lrc = launch_query(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc);
       }
       if (lrc != GRP_OK) {
         sl.busy = false;
@@ -3087,11 +3107,7 @@ grp_insert_tiles(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t til
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
-    if (long_span(c)) {
-      DISPATCH_H(c->params.h, (k_insert_long<HH><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
-    } else {
-      DISPATCH_H(c->params.h, (k_insert<HH><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
-    }
+    DISPATCH_H_SPAN(c, (k_insert<HH, WW><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
   }
   HIP_TRY(c, hipGetLastError());
   return GRP_OK;
@@ -3142,13 +3158,7 @@ grp_insert_read(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t tile
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
-    if (long_span(c)) {
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, GRP_WT_LONG><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
-    } else if (c->uniform_weight == 16) { // make_seed_pattern's default weight: care loop unrolled (the launch is latency-bound)
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, 16><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
-    } else {
-      DISPATCH_H(c->params.h, (k_insert_collect<HH, 0><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
-    }
+    DISPATCH_HW(c, (k_insert_collect<HH, WW><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, block_tiles, tb, parity)));
     k_insert_apply<<<dim3((uint32_t)((max_ranks + THREADS - 1) / THREADS)), dim3(THREADS), 0, c->stream>>>(c->f, tb, parity, block_tiles, first_id, id_offset);
   }
   HIP_TRY(c, hipGetLastError());
@@ -3321,9 +3331,7 @@ grp_debug_tile_hashes(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_
     return set_err(c, GRP_ERR_INVALID, "grp_debug_tile_hashes: tile index out of range");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t start = tile_idx * tile;
-  const uint32_t Lp = std::min(tile + k - 1, r->len[read_idx] - start);
-  const uint64_t nv = (uint64_t)(Lp - span0(c) + 1) * c->params.h; // (Lp >= tile >= the longest span)
+  const uint64_t nv = (uint64_t)tile_extent(c, r->len[read_idx], tile_idx).frames * c->params.h;
   *n_values = nv;
   if (nv > cap) {
     return set_err(c, GRP_ERR_NOMEM, "grp_debug_tile_hashes: %llu values, capacity %llu", (unsigned long long)nv, (unsigned long long)cap);
@@ -3331,11 +3339,7 @@ grp_debug_tile_hashes(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_
   uint64_t* d = nullptr;
   HIP_TRY(c, hipMalloc(&d, nv * 8));
   const size_t lds = tab_bytes(c) + bases_bytes(tile + k + c->params.h);
-  if (long_span(c)) {
-    DISPATCH_H(c->params.h, (k_debug_tile_hashes_long<HH><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
-  } else {
-    DISPATCH_H(c->params.h, (k_debug_tile_hashes<HH><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
-  }
+  DISPATCH_H_SPAN(c, (k_debug_tile_hashes<HH, WW><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, d, nv * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -2,6 +2,7 @@
 // (goldrush_path.cpp:960-1094); silver_path_check() is :156-187.
 #include "gr_classifier.hpp"
 #include "gr_params.hpp"
+#include "gr_tile_geom.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -670,10 +671,8 @@ Classifier::commit(void* reads, const uint32_t* lens, uint32_t r, const gr_read_
   const uint32_t nt = d.num_tiles;
   total_tiles_ += nt;
   if (nt) {
-    // one query per frame (:567-568): tile + k - span0 frames per tile; only the last tile can be clipped
-    const uint32_t start = (nt - 1) * tile;
-    const uint32_t Lp = std::min(tile + k - 1, len - start);
-    queries_ += (uint64_t)(nt - 1) * (tile + k - s0) + (Lp >= s0 ? Lp - s0 + 1 : 0);
+    // one query per frame (:567-568); only the last tile can be clipped
+    queries_ += (uint64_t)(nt - 1) * geom::frames_per_tile(tile, k, s0) + geom::tile_extent(tile, k, s0, len, nt - 1).frames;
   }
   hits_ += d.hits;
   misses_ += d.misses;

@@ -18,14 +18,15 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 K, H, TILE, BLOCK = 22, 3, 500, 4
 
 
-def make_stream():
+def make_stream(**errors):
     """reads of a covered genome A; clusters of overlapping reads of islands B1..B4 nobody has covered come in between: the
-    first read of a cluster inserts, the ones behind it — queried by the launch BEFORE that insert — must be decided against it"""
+    first read of a cluster inserts, the ones behind it — queried by the launch BEFORE that insert — must be decided against it.
+    `errors`: synth.make_reads' sub / ins / dele rates of the reads of A (its defaults when not given)"""
     from goldrush_amd import synth
 
     ga = synth.random_genome(160_000, 101)
-    cover = [r[1] for r in synth.make_reads(ga, 70, mean_len=5000, min_len=3500, seed=102, max_len=9000)]   # the head: these fill the path
-    steady = [r[1] for r in synth.make_reads(ga, 260, mean_len=5000, min_len=3500, seed=103, max_len=9000)]  # covered: (mostly) no insert
+    cover = [r[1] for r in synth.make_reads(ga, 70, mean_len=5000, min_len=3500, seed=102, max_len=9000, **errors)]   # the head: these fill the path
+    steady = [r[1] for r in synth.make_reads(ga, 260, mean_len=5000, min_len=3500, seed=103, max_len=9000, **errors)]  # covered: (mostly) no insert
     reads = cover + steady
     rng = np.random.default_rng(104)
     for i, at in enumerate((120, 170, 230, 300)):

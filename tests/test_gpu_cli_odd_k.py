@@ -6,8 +6,9 @@ import glob
 import os
 import subprocess
 
-import numpy as np
 import pytest
+
+from helpers import palindromic_preset
 
 pytestmark = pytest.mark.gpu
 
@@ -16,18 +17,6 @@ def _verbose_counters(stderr):
     keep = ("Visited", "Saw:", "Assigned:", "Unassigned:", "Total queries", "Total hits", "Total misses", "Num reads", "Average Phred",
             "m_filterSize", "expected hash space", "minimum average phred", "num_", "Total reads skipped")
     return [l for l in stderr.splitlines() if l.strip().startswith(keep)]
-
-
-def _odd_preset(k, weight, seed):
-    """an odd-length preset of weight `weight` + 1 whose middle and first positions are care positions (the last character
-    is dropped)"""
-    rng = np.random.default_rng(seed)
-    half = k // 2
-    left = np.zeros(half, dtype=bool)
-    left[0] = True
-    left[rng.choice(np.arange(1, half), size=weight // 2 - 1, replace=False)] = True
-    s = "".join("1" if b else "0" for b in left)
-    return s + "1" + s[::-1]
 
 
 def _mk_fastq(path, genome_len, n_reads, seed, short=(), sub=0.01):
@@ -89,7 +78,7 @@ def test_designed_k23_silver_then_golden(oracle, host, tmp_path):
 
 
 @pytest.mark.parametrize("args,tag", [(["-k23", "-w17", "-h3", "-s10110111101101111011011"], "preset23"), (["-k23", "-w16", "-h9"], "h9"),
-                                      (["-k129", "-w31", "-h2", "-s" + _odd_preset(129, 30, 5)], "long129")])
+                                      (["-k129", "-w31", "-h2", "-s" + palindromic_preset(129, 30, 5)], "long129")])
 def test_odd_k_silver_paths(oracle, host, tmp_path, args, tag):
     fq = str(tmp_path / "reads.fq")
     _mk_fastq(fq, 150_000, 140, seed=7, sub=0.004 if tag == "long129" else 0.01)

@@ -2,50 +2,19 @@
 against the CPU oracle, bit for bit: tile hashes, fill, inserts, queries and the classification window; ntCard tables;
 the order-exact forms (a resumable streaming window that applies inserts itself and keeps tiles, batches) against the
 oracle's serial loop (process_read, goldrush_path.cpp:892-1094); spans beyond 256 refused."""
-import time
-
 import numpy as np
 import pytest
 
-from helpers import canon_list, default_seeds, random_reads
+from helpers import compare_queries, default_seeds, keep_stream, low_error_reads, palindromic_preset, random_reads, stream_resumable
 
 pytestmark = pytest.mark.gpu
 
 
-def _symmetric_seed(k, weight, seed):
-    """A palindromic care pattern of span k whose ends are care positions (the last one at base k - 1), ~weight ones."""
-    rng = np.random.default_rng(seed)
-    half = k // 2
-    left = np.zeros(half, dtype=bool)
-    left[0] = True
-    left[rng.choice(np.arange(1, half), size=max(weight // 2 - 1, 0), replace=False)] = True
-    s = "".join("1" if b else "0" for b in left)
-    return s + ("1" if k % 2 else "") + s[::-1]
-
-
 def _long_seeds(k, h, seed):
-    seeds = default_seeds(h, _symmetric_seed(k, 30, seed))
+    seeds = default_seeds(h, palindromic_preset(k, 30, seed))
     assert [len(s) for s in seeds] == [k + i for i in range(h)]
     assert all(s[-1] == "1" and s.count("1") <= 32 for s in seeds)
     return seeds
-
-
-def _compare_queries(eng, omf, batch, reads):
-    tiles, lists, stats = eng.query_tiles(batch)
-    ti = q = hh = ms = 0
-    for seq in reads:
-        for top_id, top_count, lst, ctr in omf.query_read(seq):
-            t = tiles[ti]
-            assert (int(t["top_id"]), int(t["top_count"])) == (top_id, top_count), ti
-            got = [(int(a), int(c)) for a, c in lists[t["list_off"]: t["list_off"] + t["list_n"]]]
-            assert got == canon_list(lst), ti
-            q += ctr[0]
-            hh += ctr[1]
-            ms += ctr[2]
-            ti += 1
-    assert ti == len(tiles)
-    assert (stats["queries"], stats["hits"], stats["misses"]) == (q, hh, ms)
-    return hh
 
 
 @pytest.mark.parametrize("k,h,tile", [(63, 3, 400), (65, 1, 300), (96, 3, 500), (128, 5, 700), (200, 3, 1000), (254, 3, 600), (129, 1, 129)])
@@ -85,7 +54,7 @@ def test_long_spans_match_oracle(oracle, native, k, h, tile):
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
     assert counts.any()
-    assert _compare_queries(eng, omf, b, reads) > 0
+    assert compare_queries(eng, omf, b, reads)[1] > 0
     # whole reads in ID blocks of 2 tiles (k_insert_collect + k_insert_apply) on top of the tile inserts above
     for ri in (1, 3):
         nt = len(reads[ri]) // tile
@@ -94,7 +63,7 @@ def test_long_spans_match_oracle(oracle, native, k, h, tile):
             omf.insert_read_tiles(reads[ri], bs, min(bs + 2, nt), 40 + ri + bs // 2)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # the classification window (hash + query + decisions in one call) against the host decision on the queried tiles
     dp = dict(threshold=2, unassigned_min=2, assigned_max=1 << 30)
     dec = eng.classify_reads(b, 0, len(reads), **dp)
@@ -168,65 +137,6 @@ def test_long_span_ntcard_tables_match_oracle(oracle, native, k, h):
 K_LONG, H_LONG = 126, 3  # spans 126 - 128
 
 
-def _reads(genome_len, n, seed, mean_len=5000):
-    from goldrush_amd import synth
-
-    g = synth.random_genome(genome_len, seed)
-    return g, [r[1] for r in synth.make_reads(g, n, mean_len=mean_len, min_len=3500, seed=seed + 1, max_len=9000, sub=0.004, ins=0.0005, dele=0.0005)]
-
-
-def _keep_stream():
-    """tests/stream_keep_scenario.py's stream with few errors: reads of a covered genome, and clusters of overlapping reads of
-    uncovered islands in between — the first read of a cluster inserts, the ones behind it (queried by the launch BEFORE
-    that insert) must be decided against it"""
-    from goldrush_amd import synth
-
-    ga = synth.random_genome(160_000, 101)
-    mk = lambda n, seed: [r[1] for r in synth.make_reads(ga, n, mean_len=5000, min_len=3500, seed=seed, max_len=9000, sub=0.004, ins=0.0005, dele=0.0005)]
-    reads = mk(70, 102) + mk(260, 103)
-    rng = np.random.default_rng(104)
-    for i, at in enumerate((120, 170, 230, 300)):
-        gb = synth.random_genome(9_000, 200 + i)
-        cluster = [gb[o:o + 6000].tobytes() for o in (0, 1500, 3000, 700)]
-        for j, s in enumerate(cluster):
-            reads.insert(at + j + int(rng.integers(0, 2)), s)
-    return reads
-
-
-def _stream_resumable(eng, b, reads, tile, block, limit=120.0):
-    """ONE resumable window over all reads; every insert record answered with stream_insert (the IDs the serial loop
-    allocates) -> the commit tuples of oracle_engine.serial_reference"""
-    n = len(reads)
-    v = eng.stream_begin(b, 0, n, 0, resumable=True)
-    gen, ids_inserted = 1, 0
-    got = []
-    for j in range(n):
-        t0 = time.time()
-        while int(v["pad"][j]) != gen:
-            assert time.time() - t0 < limit, "record %d of generation %d never came" % (j, gen)
-            assert not eng.stream_poll(0) or int(v["pad"][j]) == gen, "the launch ended without record %d" % j
-        d = v[j].copy()
-        kind = int(d["kind"])
-        assert kind != 0
-        first_id = 0
-        if kind in (2, 4):
-            ids_inserted += 1
-            first_id = ids_inserted
-            if kind == 2:
-                ts, te, off = 0, int(d["num_tiles"]), 0
-                ids_inserted += len(reads[j]) // (tile * block)
-            else:
-                ts, te, off = int(d["trim_start"]), int(d["trim_end"]) + 1, 1
-                ids_inserted += (int(d["trim_end"]) - int(d["trim_start"])) // block
-            gen = eng.stream_insert(0, j, ts, te, block, first_id, off)
-        got.append((j, kind, int(d["num_tiles"]), int(d["num_assigned"]), int(d["trim_start"]) if kind == 4 else 0, int(d["trim_end"]) if kind == 4 else 0, first_id, 1))
-    t0 = time.time()
-    while not eng.stream_poll(0):
-        assert time.time() - t0 < 60
-    eng.stream_end(0)
-    return got
-
-
 def test_long_span_window_applies_inserts_itself(oracle, native):
     """The head of a path at spans 124 - 128 (h = 5): most reads insert, in the launch; records and the final ID / count
     arrays equal the serial loop's."""
@@ -234,7 +144,7 @@ def test_long_span_window_applies_inserts_itself(oracle, native):
 
     k, h, tile, block = 124, 5, 500, 4
     seeds = _long_seeds(k, h, 41)
-    _, reads = _reads(150_000, 90, 31)
+    _, reads = low_error_reads(150_000, 90, 31)
     reads.insert(7, reads[3][: tile - 1])  # a read without a single tile
     m = oracle.load().orc_calc_optimal_size(2_000_000, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, tile, k, reads, block=block)
@@ -242,7 +152,7 @@ def test_long_span_window_applies_inserts_itself(oracle, native):
     b = eng.upload(reads)
     eng.bv_insert(b)
     assert eng.finalize() == mf_ref.pop
-    got = _stream_resumable(eng, b, reads, tile, block)
+    got = stream_resumable(eng, b, reads, tile, block)
     assert got == exp
     kinds = [g[1] for g in got]
     assert sum(q in (2, 4) for q in kinds) >= 10 and sum(q not in (2, 4) for q in kinds) >= 10
@@ -259,14 +169,14 @@ def test_long_span_window_keeps_tiles(oracle, native):
 
     tile, block = 500, 4
     seeds = _long_seeds(K_LONG, H_LONG, 43)
-    reads = _keep_stream()
+    reads = keep_stream()
     m = oracle.load().orc_calc_optimal_size(2_500_000, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, tile, K_LONG, reads, block=block)
     eng = native.Engine(K_LONG, H_LONG, tile, m, seeds)
     b = eng.upload(reads)
     eng.bv_insert(b)
     assert eng.finalize() == mf_ref.pop
-    got = _stream_resumable(eng, b, reads, tile, block)
+    got = stream_resumable(eng, b, reads, tile, block)
     assert got == exp
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, mf_ref.ids()) and np.array_equal(counts, mf_ref.counts())
@@ -289,7 +199,7 @@ def test_long_span_batches_equal_the_serial_loop(oracle, native, window, verify)
 
     tile, block = 500, 4
     seeds = _long_seeds(K_LONG, H_LONG, 47)
-    _, reads = _reads(150_000, 140, 21)
+    _, reads = low_error_reads(150_000, 140, 21)
     m = oracle.load().orc_calc_optimal_size(2_000_000, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, tile, K_LONG, reads, block=block)
     eng = native.Engine(K_LONG, H_LONG, tile, m, seeds)
@@ -311,8 +221,8 @@ def test_long_span_batches_equal_the_serial_loop(oracle, native, window, verify)
 
 def test_spans_beyond_256_are_refused(native):
     with pytest.raises(native.GrpError, match="256"):
-        native.Engine(257, 1, 1000, 1 << 20, [_symmetric_seed(257, 30, 1)])
+        native.Engine(257, 1, 1000, 1 << 20, [palindromic_preset(257, 30, 1)])
     with pytest.raises(native.GrpError, match="256"):
-        native.Engine(254, 4, 1000, 1 << 20, default_seeds(4, _symmetric_seed(254, 30, 2)))  # longest seed 257
-    eng = native.Engine(253, 4, 1000, 1 << 20, default_seeds(4, _symmetric_seed(253, 30, 3)))  # longest seed 256: accepted
+        native.Engine(254, 4, 1000, 1 << 20, default_seeds(4, palindromic_preset(254, 30, 2)))  # longest seed 257
+    eng = native.Engine(253, 4, 1000, 1 << 20, default_seeds(4, palindromic_preset(253, 30, 3)))  # longest seed 256: accepted
     eng.close()

@@ -2,50 +2,19 @@
 bit for bit: tile hashes, fill, inserts, queries and the classification window; ntCard tables; the order-exact forms (a
 resumable streaming window that applies inserts itself, keeping tiles and keeping nothing; batches) against the oracle's
 serial loop (process_read, goldrush_path.cpp:892-1094); 17 seeds refused."""
-import time
-
 import numpy as np
 import pytest
 
-from helpers import SEED22, canon_list, default_seeds, random_reads
+from helpers import SEED22, compare_queries, default_seeds, keep_stream, low_error_reads, palindromic_preset, random_reads, stream_resumable
 
 pytestmark = pytest.mark.gpu
 
 
-def _preset(k, weight, seed):
-    """a palindromic care pattern of span k whose ends are care positions, ~weight ones"""
-    rng = np.random.default_rng(seed)
-    half = k // 2
-    left = np.zeros(half, dtype=bool)
-    left[0] = True
-    left[rng.choice(np.arange(1, half), size=max(weight // 2 - 1, 0), replace=False)] = True
-    s = "".join("1" if b else "0" for b in left)
-    return s + ("1" if k % 2 else "") + s[::-1]
-
-
 def _seeds(k, h, seed=1):
-    preset = SEED22 if k == 22 else _preset(k, min(30, k - 2 if k % 2 == 0 else k - 1), seed + k)
+    preset = SEED22 if k == 22 else palindromic_preset(k, min(30, k - 2 if k % 2 == 0 else k - 1), seed + k)
     seeds = default_seeds(h, preset)
     assert [len(s) for s in seeds] == [k + i for i in range(h)]
     return seeds
-
-
-def _compare_queries(eng, omf, batch, reads):
-    tiles, lists, stats = eng.query_tiles(batch)
-    ti = q = hh = ms = 0
-    for seq in reads:
-        for top_id, top_count, lst, ctr in omf.query_read(seq):
-            t = tiles[ti]
-            assert (int(t["top_id"]), int(t["top_count"])) == (top_id, top_count), ti
-            got = [(int(a), int(c)) for a, c in lists[t["list_off"]: t["list_off"] + t["list_n"]]]
-            assert got == canon_list(lst), ti
-            q += ctr[0]
-            hh += ctr[1]
-            ms += ctr[2]
-            ti += 1
-    assert ti == len(tiles)
-    assert (stats["queries"], stats["hits"], stats["misses"]) == (q, hh, ms)
-    return hh, ms
 
 
 # (22, 9): spans 22 - 30; (22, 11): 22 - 32, the 32-base boundary inside the family; (24, 10): 24 - 33; (49, 16): 49 - 64;
@@ -89,7 +58,7 @@ def test_many_seeds_match_oracle(oracle, native, k, h, tile):
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
     assert counts.any()
-    hits, misses = _compare_queries(eng, omf, b, reads)
+    _, hits, misses = compare_queries(eng, omf, b, reads)
     assert hits > 0 and misses > 0
     # whole reads in ID blocks of 2 tiles (k_insert_collect + k_insert_apply) on top of the tile inserts above
     for ri in (4, 8):
@@ -99,7 +68,7 @@ def test_many_seeds_match_oracle(oracle, native, k, h, tile):
             omf.insert_read_tiles(reads[ri], bs, min(bs + 2, nt), 40 + ri + bs // 2)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # the classification window (hash + query + decisions in one call) against the host decision on the queried tiles
     dp = dict(threshold=2, unassigned_min=2, assigned_max=1 << 30)
     dec = eng.classify_reads(b, 0, len(reads), **dp)
@@ -140,7 +109,7 @@ def test_many_seeds_ids_per_frame(oracle, native, h, tile, n_ids):
         ids[rng.random(pop) < 0.05] |= np.uint32(0x80000000)  # a few saturated ones: the bit is stripped before counting
     eng.import_ids(0, ids=ids, counts=np.zeros(pop, dtype=np.uint32))
     omf.ids()[:] = ids
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     dec = eng.classify_reads(b)
     assert all(int(d["num_tiles"]) == len(r) // tile for d, r in zip(dec, reads))
     assert (eng.verify_stats()["window_flagged"] > 0) == (n_ids > 3 and tile >= 1500)
@@ -204,65 +173,6 @@ def test_many_seeds_ntcard_tables_match_oracle(oracle, native, h):
 # Reads with few errors: a frame of 16 seeds is lost to an error in any of its spans.
 
 
-def _reads(genome_len, n, seed, mean_len=5000):
-    from goldrush_amd import synth
-
-    g = synth.random_genome(genome_len, seed)
-    return g, [r[1] for r in synth.make_reads(g, n, mean_len=mean_len, min_len=3500, seed=seed + 1, max_len=9000, sub=0.004, ins=0.0005, dele=0.0005)]
-
-
-def _keep_stream():
-    """tests/stream_keep_scenario.py's stream with few errors: reads of a covered genome, and clusters of overlapping reads of
-    uncovered islands in between — the first read of a cluster inserts, the ones behind it (queried by the launch BEFORE
-    that insert) must be decided against it"""
-    from goldrush_amd import synth
-
-    ga = synth.random_genome(160_000, 101)
-    mk = lambda n, seed: [r[1] for r in synth.make_reads(ga, n, mean_len=5000, min_len=3500, seed=seed, max_len=9000, sub=0.004, ins=0.0005, dele=0.0005)]
-    reads = mk(70, 102) + mk(260, 103)
-    rng = np.random.default_rng(104)
-    for i, at in enumerate((120, 170, 230, 300)):
-        gb = synth.random_genome(9_000, 200 + i)
-        cluster = [gb[o:o + 6000].tobytes() for o in (0, 1500, 3000, 700)]
-        for j, s in enumerate(cluster):
-            reads.insert(at + j + int(rng.integers(0, 2)), s)
-    return reads
-
-
-def _stream_resumable(eng, b, reads, tile, block, u=5, limit=120.0):
-    """ONE resumable window over all reads; every insert record answered with stream_insert (the IDs the serial loop
-    allocates) -> the commit tuples of oracle_engine.serial_reference"""
-    n = len(reads)
-    v = eng.stream_begin(b, 0, n, 0, unassigned_min=u, resumable=True)
-    gen, ids_inserted = 1, 0
-    got = []
-    for j in range(n):
-        t0 = time.time()
-        while int(v["pad"][j]) != gen:
-            assert time.time() - t0 < limit, "record %d of generation %d never came" % (j, gen)
-            assert not eng.stream_poll(0) or int(v["pad"][j]) == gen, "the launch ended without record %d" % j
-        d = v[j].copy()
-        kind = int(d["kind"])
-        assert kind != 0
-        first_id = 0
-        if kind in (2, 4):
-            ids_inserted += 1
-            first_id = ids_inserted
-            if kind == 2:
-                ts, te, off = 0, int(d["num_tiles"]), 0
-                ids_inserted += len(reads[j]) // (tile * block)
-            else:
-                ts, te, off = int(d["trim_start"]), int(d["trim_end"]) + 1, 1
-                ids_inserted += (int(d["trim_end"]) - int(d["trim_start"])) // block
-            gen = eng.stream_insert(0, j, ts, te, block, first_id, off)
-        got.append((j, kind, int(d["num_tiles"]), int(d["num_assigned"]), int(d["trim_start"]) if kind == 4 else 0, int(d["trim_end"]) if kind == 4 else 0, first_id, 1))
-    t0 = time.time()
-    while not eng.stream_poll(0):
-        assert time.time() - t0 < 60
-    eng.stream_end(0)
-    return got
-
-
 @pytest.mark.parametrize("h,tile,keeps", [(16, 250, True), (12, 250, True), (16, 1000, False)])
 def test_many_seeds_window_applies_inserts_itself(oracle, native, h, tile, keeps):
     """tests/stream_keep_scenario.py's stream at h seeds: the in-launch inserts keep the tiles they can where the LDS has
@@ -274,14 +184,14 @@ def test_many_seeds_window_applies_inserts_itself(oracle, native, h, tile, keeps
     k, block = 22, 4
     u = 5 if tile < 1000 else 2
     seeds = _seeds(k, h)
-    reads = _keep_stream()
+    reads = keep_stream()
     m = oracle.load().orc_calc_optimal_size(2_500_000 * h // 3, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, tile, k, reads, block=block, u=u)
     eng = native.Engine(k, h, tile, m, seeds)
     b = eng.upload(reads)
     eng.bv_insert(b)
     assert eng.finalize() == mf_ref.pop
-    got = _stream_resumable(eng, b, reads, tile, block, u=u)
+    got = stream_resumable(eng, b, reads, tile, block, u=u)
     assert got == exp
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, mf_ref.ids()) and np.array_equal(counts, mf_ref.counts())
@@ -307,7 +217,7 @@ def test_many_seeds_batches_equal_the_serial_loop(oracle, native, h, window, ver
 
     k, tile, block = 22, 500, 4
     seeds = _seeds(k, h)
-    _, reads = _reads(150_000, 140, 21)
+    _, reads = low_error_reads(150_000, 140, 21)
     m = oracle.load().orc_calc_optimal_size(2_000_000, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, tile, k, reads, block=block)
     eng = native.Engine(k, h, tile, m, seeds)

@@ -6,28 +6,16 @@ global-table redo, the classifier) against the oracle's serial loop; ntCard tabl
 import numpy as np
 import pytest
 
-from helpers import random_reads
+from helpers import compare_queries, palindromic_preset, random_reads, stream_resumable
 
 pytestmark = pytest.mark.gpu
-
-
-def _odd_preset(k, weight, seed):
-    """an odd-length palindromic preset of k characters whose middle is a care position: make_seed_pattern drops the
-    last character (substr(k/2, k/2)), so seed 0 spans k - 1 and ends in a care position"""
-    rng = np.random.default_rng(seed)
-    half = k // 2
-    left = np.zeros(half, dtype=bool)
-    left[0] = True
-    left[rng.choice(np.arange(1, half), size=weight // 2 - 1, replace=False)] = True
-    s = "".join("1" if b else "0" for b in left)
-    return s + "1" + s[::-1]
 
 
 def _seeds(oracle, k, h):
     """designed seeds (-w 16) where glibc's rand() finds a half of 8 care positions quickly; an odd preset beyond"""
     from goldrush_amd import host
 
-    preset = "" if k <= 65 else _odd_preset(k, 30, k)
+    preset = "" if k <= 65 else palindromic_preset(k, 30, k)
     seeds = host.make_seed_pattern(preset, k, 16, h)
     assert seeds == oracle.make_seed_pattern(preset, k, 16, h)
     assert [len(s) for s in seeds] == [k - 1 + i for i in range(h)]
@@ -42,26 +30,6 @@ def _frames(length, tile, k, span0):
         lp = min(tile + k - 1, length - t * tile)
         out.append(lp - span0 + 1)
     return out
-
-
-def _compare_queries(eng, omf, batch, reads):
-    from helpers import canon_list
-
-    tiles, lists, stats = eng.query_tiles(batch)
-    ti = q = hh = ms = 0
-    for seq in reads:
-        for top_id, top_count, lst, ctr in omf.query_read(seq):
-            t = tiles[ti]
-            assert (int(t["top_id"]), int(t["top_count"])) == (top_id, top_count), ti
-            got = [(int(a), int(c)) for a, c in lists[t["list_off"]: t["list_off"] + t["list_n"]]]
-            assert got == canon_list(lst), ti
-            q += ctr[0]
-            hh += ctr[1]
-            ms += ctr[2]
-            ti += 1
-    assert ti == len(tiles)
-    assert (stats["queries"], stats["hits"], stats["misses"]) == (q, hh, ms)
-    return q, hh
 
 
 @pytest.mark.parametrize("k,h,tile", [(23, 3, 1000), (21, 1, 300), (33, 3, 500), (33, 1, 400), (65, 1, 300), (65, 3, 400), (129, 2, 500),
@@ -103,7 +71,7 @@ def test_odd_k_matches_oracle(oracle, native, k, h, tile):
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
     assert counts.any()
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     for ri in (1, 3):  # whole reads in ID blocks of 2 tiles (k_insert_collect + k_insert_apply)
         nt = len(reads[ri]) // tile
         eng.insert_read(b, ri, 0, nt, 2, 40 + ri, 0)
@@ -111,7 +79,7 @@ def test_odd_k_matches_oracle(oracle, native, k, h, tile):
             omf.insert_read_tiles(reads[ri], bs, min(bs + 2, nt), 40 + ri + bs // 2)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    q, hits = _compare_queries(eng, omf, b, reads)
+    q, hits, _ = compare_queries(eng, omf, b, reads)
     assert hits > 0 and q == sum(sum(_frames(len(s), tile, k, span0)) for s in reads)
     eng.close()
 
@@ -137,7 +105,7 @@ def test_odd_preset_of_23_characters(oracle, native):
         nt = len(reads[ri]) // tile
         eng.insert_tiles(b, ri, 0, nt, ri + 1)
         omf.insert_read_tiles(reads[ri], 0, nt, ri + 1)
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     eng.close()
 
 
@@ -163,7 +131,7 @@ def test_odd_k_global_table_redo(oracle, native):
         eng.import_ids(0, ids=ids, counts=np.zeros(pop, dtype=np.uint32))
         omf.ids()[:] = ids
         before = eng.verify_stats()["window_flagged"]
-        _compare_queries(eng, omf, b, reads)
+        compare_queries(eng, omf, b, reads)
         dec = eng.classify_reads(b)
         assert all(int(d["num_tiles"]) == len(r) // tile for d, r in zip(dec, reads))
         assert (eng.verify_stats()["window_flagged"] > before) == flagged
@@ -175,38 +143,21 @@ def test_odd_k_global_table_redo(oracle, native):
 K, H, TILE, BLOCK = 23, 3, 500, 4
 
 
-def _keep_stream():
-    """tests/stream_keep_scenario.py's stream (that module fixes K = 22): reads of a covered genome, clusters of
-    overlapping reads of uncovered islands in between"""
-    from goldrush_amd import synth
-
-    ga = synth.random_genome(160_000, 101)
-    reads = [r[1] for r in synth.make_reads(ga, 70, mean_len=5000, min_len=3500, seed=102, max_len=9000)]
-    reads += [r[1] for r in synth.make_reads(ga, 260, mean_len=5000, min_len=3500, seed=103, max_len=9000)]
-    rng = np.random.default_rng(104)
-    for i, at in enumerate((120, 170, 230, 300)):
-        gb = synth.random_genome(9_000, 200 + i)
-        cluster = [gb[o:o + 6000].tobytes() for o in (0, 1500, 3000, 700)]
-        for j, s in enumerate(cluster):
-            reads.insert(at + j + int(rng.integers(0, 2)), s)
-    return reads
-
-
 def test_odd_k_window_keeps_tiles(oracle, native):
     """ONE resumable streaming window applying its inserts itself and keeping the tiles they leave untouched: the serial
     loop's records and arrays"""
     from oracle_engine import serial_reference
-    from test_gpu_long_spans import _stream_resumable
+    from stream_keep_scenario import make_stream
 
     seeds = _seeds(oracle, K, H)
-    reads = _keep_stream()
+    reads = make_stream()  # (that module fixes K = 22; the stream serves any k)
     m = oracle.load().orc_calc_optimal_size(2_500_000, 1, 0.1)
     exp, mf_ref = serial_reference(oracle, m, seeds, TILE, K, reads, block=BLOCK)
     eng = native.Engine(K, H, TILE, m, seeds)
     b = eng.upload(reads)
     eng.bv_insert(b)
     assert eng.finalize() == mf_ref.pop
-    got = _stream_resumable(eng, b, reads, TILE, BLOCK)
+    got = stream_resumable(eng, b, reads, TILE, BLOCK)
     assert got == exp
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, mf_ref.ids()) and np.array_equal(counts, mf_ref.counts())

@@ -3,7 +3,7 @@ same seeded inputs.  Integer / bit / index work: the bar is bit-exact."""
 import numpy as np
 import pytest
 
-from helpers import SEED22, canon_list, default_seeds, random_reads
+from helpers import SEED22, canon_list, compare_queries, default_seeds, palindromic_preset, random_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -116,23 +116,6 @@ def test_fill_bits_pop_rank(oracle, native):
         assert rank[i] == omf.rank(int(pos[i]))
 
 
-def _compare_queries(eng, omf, batch, reads):
-    tiles, lists, stats = eng.query_tiles(batch)
-    ti = 0
-    q = h = ms = 0
-    for seq in reads:
-        for res in omf.query_read(seq):
-            top_id, top_count, lst, ctr = res
-            t = tiles[ti]
-            assert (int(t["top_id"]), int(t["top_count"])) == (top_id, top_count), ti
-            got = [(int(a), int(c)) for a, c in lists[t["list_off"]: t["list_off"] + t["list_n"]]]
-            assert got == canon_list(lst), ti
-            q += ctr[0]; h += ctr[1]; ms += ctr[2]
-            ti += 1
-    assert ti == len(tiles)
-    assert (stats["queries"], stats["hits"], stats["misses"]) == (q, h, ms)
-
-
 def test_insert_and_query_match_oracle(oracle, native):
     eng, oseeds, omf, m = _mk(oracle, native)
     genome = random_reads(1, 60000, 60000, seed=31)[0]
@@ -142,7 +125,7 @@ def test_insert_and_query_match_oracle(oracle, native):
     for s in reads:
         omf.bv_insert_read(s)
     assert eng.finalize() == omf.finalize()
-    _compare_queries(eng, omf, b, reads)  # empty ID array: all misses
+    compare_queries(eng, omf, b, reads)  # empty ID array: all misses
     # inserts: whole reads in blocks of 10 tiles (goldrush_path.cpp:982-994),
     # overlapping reads so that counts > 1 and the reservoir rule is exercised
     next_id = 0
@@ -158,18 +141,18 @@ def test_insert_and_query_match_oracle(oracle, native):
         ids, counts = eng.export_ids()
         assert np.array_equal(ids, omf.ids())
         assert np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # partial (trimmed) insert with a dedup scope that is not tile-0 based
     eng.insert_tiles(b, 8, 1, 3, 77)
     omf.insert_read_tiles(reads[8], 1, 3, 77)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # reset (silver path rollover, goldrush_path.cpp:180-181)
     eng.reset_ids(); omf.reset_ids()
     ids, counts = eng.export_ids()
     assert not ids.any() and not counts.any()
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
 
 
 def test_query_dense_random_ids_and_saturation_bit(oracle, native):
@@ -189,7 +172,7 @@ def test_query_dense_random_ids_and_saturation_bit(oracle, native):
         ids[sat] |= np.uint32(0x80000000)  # includes bare 0x80000000 ("saturated empty")
         eng.import_ids(0, ids=ids, counts=np.zeros(pop, dtype=np.uint32))
         omf.ids()[:] = ids
-        _compare_queries(eng, omf, b, reads)
+        compare_queries(eng, omf, b, reads)
 
 
 @pytest.mark.parametrize("h", [5, 8])
@@ -214,7 +197,7 @@ def test_tiles_where_every_probe_returns_another_id(oracle, native, h):
     ids = rng.integers(1, 1 << 30, size=pop, dtype=np.uint32)  # (almost) every probe another ID
     eng.import_ids(0, ids=ids, counts=np.zeros(pop, dtype=np.uint32))
     omf.ids()[:] = ids
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     dec = eng.classify_reads(b)
     assert all(int(d["num_tiles"]) == len(r) // TILE for d, r in zip(dec, reads))
     assert (eng.verify_stats()["window_flagged"] > 0) == (h == 8)
@@ -261,7 +244,7 @@ def test_tiles_whose_worst_case_table_does_not_fit_the_lds(oracle, native, tile,
         eng.import_ids(0, ids=ids, counts=np.zeros(pop, dtype=np.uint32))
         omf.ids()[:] = ids
         before = eng.verify_stats()["window_flagged"]
-        _compare_queries(eng, omf, b, reads)
+        compare_queries(eng, omf, b, reads)
         dec = eng.classify_reads(b)
         assert all(int(d["num_tiles"]) == len(r) // tile for d, r in zip(dec, reads))
         assert (eng.verify_stats()["window_flagged"] > before) == flagged
@@ -299,22 +282,11 @@ def test_other_geometries(oracle, native, h, tile):
             ti += 1
 
 
-def _symmetric_seed(k, weight, seed):
-    """A palindromic care pattern of span k (ends are care positions), like the reference's designed seeds."""
-    rng = np.random.default_rng(seed)
-    half = k // 2
-    left = np.zeros(half, dtype=bool)
-    left[0] = True
-    left[rng.choice(np.arange(1, half), size=max(weight // 2 - 1, 0), replace=False)] = True
-    s = "".join("1" if b else "0" for b in left)
-    return s + ("1" if k % 2 else "") + s[::-1]
-
-
 @pytest.mark.parametrize("k,h,tile", [(31, 3, 400), (32, 1, 300), (33, 2, 400), (40, 3, 500), (48, 5, 700), (62, 3, 400), (64, 1, 1000)])
 def test_spans_beyond_one_window(oracle, native, k, h, tile):
     """k + h - 1 up to 64 bases: the frames of seeds wider than 32 bases are hashed from two
     64-bit windows of 2-bit bases.  Hashes, fill, inserts and queries against the oracle, bit for bit."""
-    base = _symmetric_seed(k, min(k // 2 * 2 - 2, 24), 7 + k)
+    base = palindromic_preset(k, min(k // 2 * 2 - 2, 24), 7 + k)
     seeds = default_seeds(h, base)
     assert all(len(sd) == k + i for i, sd in enumerate(seeds)) and len(seeds[-1]) <= 64
     m = oracle.load().orc_calc_optimal_size(300_000, 1, 0.1)
@@ -338,7 +310,7 @@ def test_spans_beyond_one_window(oracle, native, k, h, tile):
         omf.insert_read_tiles(reads[ri], 0, nt, ri + 1)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # the classification window (hash + query + decisions in one call) against the host decision on the queried tiles
     from goldrush_amd import host
     dp = dict(threshold=2, unassigned_min=2, assigned_max=1 << 30)
@@ -397,14 +369,14 @@ def test_bucket_overflow_side_table(oracle, native):
     omf.counts()[:] = cnt
     gi, gc = eng.export_ids()
     assert np.array_equal(gi, ids) and np.array_equal(gc, cnt)
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     for ri in (0, 2, 4):
         nt = len(reads[ri]) // TILE
         eng.insert_tiles(b, ri, 0, nt, 1000 + ri)
         omf.insert_read_tiles(reads[ri], 0, nt, 1000 + ri)
     gi, gc = eng.export_ids()
     assert np.array_equal(gi, omf.ids()) and np.array_equal(gc, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     eng.reset_ids()
     omf.reset_ids()
     gi, gc = eng.export_ids()
@@ -436,7 +408,7 @@ def test_ragged_and_degenerate_batches(oracle, native):
         eng.insert_tiles(b, ri, 0, nt, 10 + ri)
         omf.insert_read_tiles(reads[ri], 0, nt, 10 + ri)
     eng.insert_tiles(b, 0, 0, 0, 99)  # empty tile range: no-op
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
     # sub-ranges of the batch, including ranges that hold no tile at all
     t, l, s = eng.query_tiles(b, 8, 2)
     assert len(t) == 0
@@ -529,7 +501,7 @@ def test_insert_read_equals_block_loop(oracle, native):
         omf.insert_read_tiles(seq, bs, bs + 1, 5000 + bs)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, b, reads)
+    compare_queries(eng, omf, b, reads)
 
 
 def test_sharded_fill_or_merge(oracle, native):

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import SEED22, canon_list, default_seeds
+from helpers import SEED22, canon_list, compare_queries, default_seeds
 
 pytestmark = pytest.mark.gpu
 
@@ -28,22 +28,6 @@ def _check_rank_samples(eng, omf, m, seed, n=6000):
         p = int(pos[i])
         assert bit[i] == omf.bit(p), p
         assert rank[i] == omf.rank(p), p
-
-
-def _compare_queries(eng, omf, batch, reads, first, count):
-    tiles, lists, stats = eng.query_tiles(batch, first, count)
-    ti = 0
-    q = h = ms = 0
-    for seq in reads[first:first + count]:
-        for top_id, top_count, lst, ctr in omf.query_read(seq):
-            t = tiles[ti]
-            assert (int(t["top_id"]), int(t["top_count"])) == (top_id, top_count), ti
-            got = [(int(a), int(c)) for a, c in lists[t["list_off"]: t["list_off"] + t["list_n"]]]
-            assert got == canon_list(lst), ti
-            q += ctr[0]; h += ctr[1]; ms += ctr[2]
-            ti += 1
-    assert ti == len(tiles)
-    assert (stats["queries"], stats["hits"], stats["misses"]) == (q, h, ms)
 
 
 def _compare_pshard(eng, omf, batch, reads, first, count, n_owners):
@@ -97,7 +81,7 @@ def test_filter_of_2_pow_33_bits_matches_oracle(oracle, native):
     assert np.array_equal(bits, _oracle_bits_view(omf))
     del bits
     _check_rank_samples(eng, omf, m, 11)
-    _compare_queries(eng, omf, batch, reads, 0, 4)  # empty ID array: all misses
+    compare_queries(eng, omf, batch, reads, 0, 4)  # empty ID array: all misses
     next_id = 0
     rng = np.random.default_rng(3)
     ins = [int(x) for x in rng.choice(n_reads, size=50, replace=False)]
@@ -111,7 +95,7 @@ def test_filter_of_2_pow_33_bits_matches_oracle(oracle, native):
     assert int((ids != 0).sum()) > 2_500_000
     del ids, counts
     for ri in ins[:6] + [0, 1]:
-        _compare_queries(eng, omf, batch, reads, ri, 1)
+        compare_queries(eng, omf, batch, reads, ri, 1)
     # the order-exact classifier over a stretch of the stream against the oracle's decisions
     dec = eng.classify_reads(batch, ins[0], 1)
     res = omf.query_read(reads[ins[0]])
@@ -164,8 +148,8 @@ def test_filter_of_c2_size_matches_oracle(oracle, native):
         next_id = _insert_whole(eng, omf, batch, reads, ri, next_id)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, batch, reads, 0, 24)
-    _compare_queries(eng, omf, batch, reads, 88, 6)
+    compare_queries(eng, omf, batch, reads, 0, 24)
+    compare_queries(eng, omf, batch, reads, 88, 6)
     # developer builds (make DEV=1, include/grpath_dev.h) also carry the priced-and-rejected position-sharded form of the
     # query: the same reads through it (8 virtual owners as on a node, and 3: a number that does not divide anything)
     if native.load().grp_dev_hooks():
@@ -222,8 +206,8 @@ def test_filter_of_c4_size_matches_oracle(oracle, native):
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
     del ids, counts
-    _compare_queries(eng, omf, batch, reads, 0, 8)
-    _compare_queries(eng, omf, batch, reads, 76, 4)
+    compare_queries(eng, omf, batch, reads, 0, 8)
+    compare_queries(eng, omf, batch, reads, 76, 4)
     # silver-path rollover: both arrays zeroed (goldrush_path.cpp:180-181), bits and ranks untouched
     eng.reset_ids()
     omf.reset_ids()
@@ -233,7 +217,7 @@ def test_filter_of_c4_size_matches_oracle(oracle, native):
     next_id = _insert_whole(eng, omf, batch, reads, 40, 0)
     ids, counts = eng.export_ids()
     assert np.array_equal(ids, omf.ids()) and np.array_equal(counts, omf.counts())
-    _compare_queries(eng, omf, batch, reads, 39, 3)
+    compare_queries(eng, omf, batch, reads, 39, 3)
     eng.close()
     dr.free()
 
