@@ -779,74 +779,50 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
   const uint64_t want = std::max<uint64_t>(next_pow2_64(n_rec + n_rec / 2), 1u << 16);
   if (want > br.tab_cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(br.d_log_keys);
-    (void)hipFree(br.d_log_head);
-    (void)hipFree(br.d_log_bits);
-    br.d_log_keys = nullptr;
-    br.d_log_head = br.d_log_bits = nullptr;
-    br.tab_cap = br.log_tab_cap = 0;
-    HIP_TRY(c, hipMalloc(&br.d_log_keys, want * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc(&br.d_log_head, want * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_log_bits, std::max<uint64_t>(want / 8, 64)));
+    clear_all(br.d_log_keys, br.d_log_head, br.d_log_bits);
+    br.tab_cap = 0;
+    HIP_TRY(c, br.d_log_keys.reset(want));
+    HIP_TRY(c, br.d_log_head.reset(want));
+    HIP_TRY(c, br.d_log_bits.reset(std::max<uint64_t>(want / 8, 64) / 4)); // (in words)
     HIP_TRY(c, hipMemsetAsync(br.d_log_keys, 0, want * sizeof(unsigned long long), c->stream));
     HIP_TRY(c, hipMemsetAsync(br.d_log_head, 0xFF, want * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(br.d_log_bits, 0, std::max<uint64_t>(want / 8, 64), c->stream));
-    br.tab_cap = br.log_tab_cap = want;
+    br.tab_cap = want;
   }
   if (!br.d_counters) {
-    HIP_TRY(c, hipMalloc(&br.d_counters, 8 * sizeof(uint32_t)));
+    HIP_TRY(c, br.d_counters.reset(8));
     HIP_TRY(c, hipMemsetAsync(br.d_counters, 0, 8 * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipHostMalloc(&br.h_counters, 4 * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(c, br.h_counters.reset(4, hipHostMallocDefault));
     memset(br.h_counters, 0, 4 * sizeof(uint32_t));
     br.ctr_set = 0;
   }
-  if (h_ins.size() > br.ins_stage_cap) {
+  if (h_ins.size() > br.h_ins_stage.cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (br.h_ins_stage) {
-      (void)hipHostFree(br.h_ins_stage);
-      br.h_ins_stage = nullptr;
-    }
-    br.ins_stage_cap = 0;
-    const uint64_t n = 2 * h_ins.size() + 6 * 1024;
-    HIP_TRY(c, hipHostMalloc(&br.h_ins_stage, n * sizeof(uint32_t), hipHostMallocDefault));
-    br.ins_stage_cap = n;
+    HIP_TRY(c, br.h_ins_stage.reset(2 * h_ins.size() + 6 * 1024, hipHostMallocDefault));
   }
-  int rc = ensure_dev(c, br.d_ins, br.ins_cap, (uint64_t)n_ins * 6);
+  int rc = ensure_dev(c, br.d_ins, (uint64_t)n_ins * 6);
   if (rc == GRP_OK && n_rec > br.rec_cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(br.d_rec_key);
-    (void)hipFree(br.d_rec_loc);
-    (void)hipFree(br.d_rec_old);
-    (void)hipFree(br.d_rec_chain);
-    (void)hipFree(br.d_ovf_next);
-    (void)hipFree(br.d_ovf_jb);
-    (void)hipFree(br.d_chained);
-    (void)hipFree(br.d_log_old);
-    (void)hipFree(br.d_log_writer);
-    (void)hipFree(br.d_log_next);
-    (void)hipFree(br.d_log_slot);
-    br.d_rec_key = br.d_rec_loc = br.d_rec_old = nullptr;
-    br.d_rec_chain = br.d_ovf_next = br.d_ovf_jb = br.d_chained = nullptr;
-    br.d_log_old = br.d_log_writer = br.d_log_next = br.d_log_slot = nullptr;
+    clear_all(br.d_rec_key, br.d_rec_loc, br.d_rec_old, br.d_rec_chain, br.d_ovf_next, br.d_ovf_jb, br.d_chained, br.d_log_old, br.d_log_writer, br.d_log_next, br.d_log_slot);
     br.rec_cap = br.log_cap = br.ovf_cap = 0;
     const uint64_t n = n_rec + n_rec / 4 + 1024;
-    HIP_TRY(c, hipMalloc(&br.d_rec_key, n * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc(&br.d_rec_loc, n * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc(&br.d_rec_old, n * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc(&br.d_rec_chain, n * sizeof(uint32_t)));
+    HIP_TRY(c, br.d_rec_key.reset(n));
+    HIP_TRY(c, br.d_rec_loc.reset(n));
+    HIP_TRY(c, br.d_rec_old.reset(n));
+    HIP_TRY(c, br.d_rec_chain.reset(n));
     HIP_TRY(c, hipMemsetAsync(br.d_rec_chain, 0xFF, n * sizeof(uint32_t), c->stream)); // every batch leaves it clean (k_batch_clear)
     // touches of a rank by a second (read, block): ~ranks^2 / (2 pop) for independent reads,
     // more where reads of the batch overlap (then the batch is taken back anyway)
     const long ovf_test = getenv("GRP_BATCH_OVF_CAP") ? atol(getenv("GRP_BATCH_OVF_CAP")) : 0; // tests: a tiny chain store, so that batches are refused on the device
     const uint64_t no = ovf_test > 0 ? (uint64_t)ovf_test : n / 4 + 65536;
-    HIP_TRY(c, hipMalloc(&br.d_ovf_next, no * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_ovf_jb, no * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_chained, no * sizeof(uint32_t)));
+    HIP_TRY(c, br.d_ovf_next.reset(no));
+    HIP_TRY(c, br.d_ovf_jb.reset(no));
+    HIP_TRY(c, br.d_chained.reset(no));
     const uint64_t nl = n + no; // one entry per write at most
-    HIP_TRY(c, hipMalloc(&br.d_log_old, nl * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_log_writer, nl * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_log_next, nl * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&br.d_log_slot, nl * sizeof(uint32_t)));
+    HIP_TRY(c, br.d_log_old.reset(nl));
+    HIP_TRY(c, br.d_log_writer.reset(nl));
+    HIP_TRY(c, br.d_log_next.reset(nl));
+    HIP_TRY(c, br.d_log_slot.reset(nl));
     br.rec_cap = n;
     br.ovf_cap = no;
     br.log_cap = nl;
@@ -913,21 +889,16 @@ grp_window_overlap(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   HIP_TRY(c, hipSetDevice(c->device));
   grp_ctx::OverlapBuf& ob = c->ovl;
   const uint64_t tab = std::max<uint64_t>(next_pow2_64(nt * 128), 1u << 16); // ~62 samples per tile: load < 1/2
-  if (nt > ob.samples_cap) {
+  if (nt * OVL_CAP_T > ob.d_samples.cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(ob.d_samples);
-    ob.d_samples = nullptr;
-    ob.samples_cap = 0;
-    const uint64_t n = nt + nt / 4 + 64;
-    HIP_TRY(c, hipMalloc(&ob.d_samples, n * OVL_CAP_T * sizeof(unsigned long long)));
-    ob.samples_cap = n;
+    HIP_TRY(c, ob.d_samples.reset((nt + nt / 4 + 64) * OVL_CAP_T));
   }
-  int rc = ensure_dev(c, ob.d_n, ob.n_cap, nt);
+  int rc = ensure_dev(c, ob.d_n, nt);
   if (rc == GRP_OK) {
-    rc = ensure_dev(c, ob.d_tab, ob.tab_cap, tab);
+    rc = ensure_dev(c, ob.d_tab, tab);
   }
   if (rc == GRP_OK) {
-    rc = ensure_dev(c, ob.d_prev, ob.prev_cap, count);
+    rc = ensure_dev(c, ob.d_prev, count);
   }
   if (rc != GRP_OK) {
     return rc;
@@ -980,7 +951,7 @@ grp_batch_classify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   }
   BatchRun& br = c->batch;
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_dev(c, br.d_floor, br.floor_cap, std::max<uint64_t>(count, 1));
+  int rc = ensure_dev(c, br.d_floor, std::max<uint64_t>(count, 1));
   if (rc != GRP_OK) {
     return rc;
   }

@@ -132,10 +132,9 @@ grp_bv_merge_ranks(grp_ctx* c)
   const uint32_t world = c->comm_world;
   const uint64_t slice_words = ((c->n_bv_words + world - 1) / world + 3) / 4 * 4; // 16-byte multiples
   const size_t slice_bytes = slice_words * 4, total = slice_bytes * world;
-  uint8_t *mine = nullptr, *got = nullptr;
-  HIP_TRY(c, hipMalloc(&mine, total));
-  if (hipMalloc(&got, total) != hipSuccess) {
-    (void)hipFree(mine);
+  DevBuf<uint8_t> mine, got;
+  HIP_TRY(c, mine.reset(total));
+  if (got.reset(total) != hipSuccess) {
     return set_err(c, GRP_ERR_NOMEM, "grp_bv_merge_ranks: no room for two copies of the bit vector");
   }
   // every exit waits for the stream (the buffers are freed); a collective, the OR kernel or the import that failed
@@ -146,8 +145,7 @@ grp_bv_merge_ranks(grp_ctx* c)
     if (g_rccl.CommGetAsyncError && g_rccl.CommGetAsyncError(c->comm, &async) != 0) {
       async = -1;
     }
-    (void)hipFree(mine);
-    (void)hipFree(got);
+    clear_all(mine, got);
     if (rc == GRP_OK && se != hipSuccess) {
       return set_err(c, GRP_ERR_HIP, "grp_bv_merge_ranks: the merge failed on the stream: %s", hipGetErrorString(se));
     }
@@ -167,7 +165,7 @@ grp_bv_merge_ranks(grp_ctx* c)
     return done(set_err(c, GRP_ERR_HIP, "ncclAllToAll: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "failed"));
   }
   for (uint32_t p = 1; p < world; ++p) {
-    k_bv_or<<<dim3(4096), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<uint4*>(got), reinterpret_cast<const uint4*>(got + (size_t)p * slice_bytes), slice_words / 4, nullptr, nullptr, 0);
+    k_bv_or<<<dim3(4096), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<uint4*>(got.p), reinterpret_cast<const uint4*>(got.p + (size_t)p * slice_bytes), slice_words / 4, nullptr, nullptr, 0);
   }
   if (hipGetLastError() != hipSuccess) {
     return done(set_err(c, GRP_ERR_HIP, "grp_bv_merge_ranks: OR kernel failed"));
@@ -229,20 +227,20 @@ grp_bv_or_words(grp_ctx* c, uint64_t first, uint64_t n, const uint32_t* words)
     return set_err(c, GRP_ERR_INVALID, "grp_bv_or_words: bad range (first must be a multiple of 4 words), or after grp_finalize");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  uint32_t* tmp = nullptr;
+  DevBuf<uint32_t> tmp;
   const uint64_t n_pad = (n + 3) / 4 * 4;
-  HIP_TRY(c, hipMalloc(&tmp, n_pad * 4));
+  HIP_TRY(c, tmp.reset(n_pad));
   hipError_t e = hipMemsetAsync(tmp, 0, n_pad * 4, c->stream);
   if (e == hipSuccess) {
     e = hipMemcpyAsync(tmp, words, n * 4, hipMemcpyHostToDevice, c->stream);
   }
   if (e == hipSuccess) {
     // (the vector is padded with 3 zero words: a padded tail never reaches beyond it)
-    k_bv_or<<<dim3(1024), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<uint4*>(c->f.bv + first), reinterpret_cast<const uint4*>(tmp), n_pad / 4, nullptr, nullptr, 0);
+    k_bv_or<<<dim3(1024), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<uint4*>(c->f.bv + first), reinterpret_cast<const uint4*>(tmp.p), n_pad / 4, nullptr, nullptr, 0);
     e = hipGetLastError();
   }
   const hipError_t se = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
+  tmp.clear();
   if (e == hipSuccess) {
     e = se;
   }

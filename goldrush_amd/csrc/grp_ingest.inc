@@ -320,6 +320,7 @@ struct grp_fastq
 {
   grp_ctx* ctx = nullptr;
   uint8_t* d_text = nullptr; // 16-byte aligned; the text begins `lead` bytes behind it
+  DevBuf<uint8_t> own_text;  // what d_text points into where no slot of the context was free
   uint32_t lead = 0;
   int pool_slot = -1; // >= 0: d_text lies in the context's ingest buffer of that slot, given back by grp_fastq_free
   uint64_t n_bytes = 0;
@@ -334,24 +335,16 @@ ingest_stage(grp_ctx* c, uint64_t front_bytes, uint64_t rec_bytes)
 {
   grp_ctx::IngestPool& ip = c->ingest;
   if (!ip.h_scal) {
-    HIP_TRY(c, hipHostMalloc(&ip.h_scal, 8 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&ip.dm_scal), ip.h_scal, 0));
+    HIP_TRY(c, ip.h_scal.reset(8, hipHostMallocMapped | hipHostMallocCoherent));
   }
   if (front_bytes && !ip.h_front) {
-    HIP_TRY(c, hipHostMalloc(&ip.h_front, FQ_FRONT + 64, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&ip.dm_front), ip.h_front, 0));
+    HIP_TRY(c, ip.h_front.reset(FQ_FRONT + 64, hipHostMallocMapped | hipHostMallocCoherent));
   }
-  if (rec_bytes > ip.h_rec_bytes) {
+  if (rec_bytes > ip.h_rec.cap) {
     if (ip.h_rec) {
       (void)hipStreamSynchronize(c->stream2);
-      (void)hipHostFree(ip.h_rec);
-      ip.h_rec = nullptr;
-      ip.h_rec_bytes = 0;
     }
-    const uint64_t want = rec_bytes + rec_bytes / 4 + 4096;
-    HIP_TRY(c, hipHostMalloc(&ip.h_rec, want, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&ip.dm_rec), ip.h_rec, 0));
-    ip.h_rec_bytes = want;
+    HIP_TRY(c, ip.h_rec.reset(rec_bytes + rec_bytes / 4 + 4096, hipHostMallocMapped | hipHostMallocCoherent));
   }
   return GRP_OK;
 }
@@ -426,19 +419,15 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       if (ip.text_used[i]) {
         continue;
       }
-      if (ip.text_cap[i] < n_bytes + 64) {
+      if (ip.text[i].cap < n_bytes + 64) {
         (void)hipStreamSynchronize(c->stream);
         (void)hipStreamSynchronize(c->stream2);
         (void)hipStreamSynchronize(c->stream3);
-        (void)hipFree(ip.text[i]);
-        ip.text[i] = nullptr;
-        ip.text_cap[i] = 0;
         const uint64_t want = FQ_FRONT + n_bytes + n_bytes / 8 + 64;
-        if (hipMalloc(&ip.text[i], want) != hipSuccess) {
-          set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: hipMalloc(%llu) failed", (unsigned long long)want);
+        if (ip.text[i].reset(want) != hipSuccess) {
+          set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: allocating %llu bytes of device memory failed", (unsigned long long)want);
           return fail(GRP_ERR_NOMEM);
         }
-        ip.text_cap[i] = want;
       }
       slot = i;
       ip.last_slot = slot;
@@ -448,9 +437,11 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       fq->pool_slot = slot;
       fq->d_text = ip.text[slot] + (dev_off & ~(uint64_t)15);
       fq->lead = (uint32_t)(dev_off & 15u);
-    } else if (hipMalloc(&fq->d_text, n_bytes + 64) != hipSuccess) {
-      set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: hipMalloc(%llu) failed", (unsigned long long)n_bytes);
+    } else if (fq->own_text.reset(n_bytes + 64) != hipSuccess) {
+      set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: allocating %llu bytes of device memory failed", (unsigned long long)n_bytes);
       return fail(GRP_ERR_NOMEM);
+    } else {
+      fq->d_text = fq->own_text;
     }
   }
   // table of the host's pow() values (calc_phred_average.cpp:21-24)
@@ -460,7 +451,7 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       const int q = (int)((char)ch - 33);
       tab[ch] = std::pow(10.0, -q / 10.0);
     }
-    if (hipMalloc(&c->d_delog, sizeof(tab)) != hipSuccess || hipMemcpy(c->d_delog, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) {
+    if (c->d_delog.reset(256) != hipSuccess || hipMemcpy(c->d_delog, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) {
       set_err(c, GRP_ERR_HIP, "grp_fastq_parse: cannot set up the Phred table");
       return fail(GRP_ERR_HIP);
     }
@@ -482,7 +473,7 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
   // not the host.
   hipStream_t ps = c->stream2;
   if (!c->ingest.uploaded) {
-    FQ_TRY(hipEventCreateWithFlags(&c->ingest.uploaded, hipEventDisableTiming));
+    FQ_TRY(c->ingest.uploaded.create(hipEventDisableTiming));
   }
   const uint32_t lead = fq->lead;
   const uint64_t n_total = lead + n_bytes; // what the kernels see: the slot's 16-byte group the text begins in, from its start
@@ -503,7 +494,7 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       return fail(GRP_ERR_HIP);
     }
     memcpy(c->ingest.h_front, text, front_len);
-    k_ing_bytes<<<dim3((uint32_t)std::min<uint64_t>((front_len + THREADS - 1) / THREADS, 64)), dim3(THREADS), 0, ps>>>(fq->d_text + lead, c->ingest.dm_front, front_len);
+    k_ing_bytes<<<dim3((uint32_t)std::min<uint64_t>((front_len + THREADS - 1) / THREADS, 64)), dim3(THREADS), 0, ps>>>(fq->d_text + lead, c->ingest.h_front.dev, front_len);
     FQ_TRY(hipGetLastError());
   }
   FQ_TRY(hipEventRecord(c->ingest.uploaded, ps));
@@ -523,8 +514,8 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       return fail2(GRP_ERR_HIP);                                                                                       \
     }                                                                                                                  \
   } while (0)
-  if (ensure_dev(c, ip.d_counts, ip.counts_cap, n_blocks) != GRP_OK || ensure_dev(c, ip.d_base, ip.base_cap, n_blocks) != GRP_OK ||
-      ensure_dev(c, ip.d_super, ip.super_cap, n_blocks / ((1u << GRP_SUPER_SHIFT) / GRP_CHUNK_BUCKETS) + 2) != GRP_OK || ensure_dev(c, ip.d_total, ip.total_cap, 1) != GRP_OK) {
+  if (ensure_dev(c, ip.d_counts, n_blocks) != GRP_OK || ensure_dev(c, ip.d_base, n_blocks) != GRP_OK ||
+      ensure_dev(c, ip.d_super, n_blocks / ((1u << GRP_SUPER_SHIFT) / GRP_CHUNK_BUCKETS) + 2) != GRP_OK || ensure_dev(c, ip.d_total, 1) != GRP_OK) {
     return fail2(GRP_ERR_NOMEM);
   }
   uint32_t* const d_counts = ip.d_counts;
@@ -534,10 +525,10 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
   if (ingest_stage(c, 0, 0) != GRP_OK) {
     return fail2(GRP_ERR_HIP);
   }
-  k_ing_words<<<dim3(1), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.dm_scal), reinterpret_cast<const unsigned long long*>(d_total), 1);
+  k_ing_words<<<dim3(1), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.h_scal.dev), reinterpret_cast<const unsigned long long*>(d_total), 1);
   FQ_TRY2(hipStreamSynchronize(ps));
   const uint64_t n_nl = ip.h_scal[0];
-  if (ensure_dev(c, ip.d_nl, ip.nl_cap, n_nl + 2) != GRP_OK) {
+  if (ensure_dev(c, ip.d_nl, n_nl + 2) != GRP_OK) {
     return fail2(GRP_ERR_NOMEM);
   }
   uint64_t* const d_nl = ip.d_nl;
@@ -553,22 +544,17 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
     if (ingest_stage(c, 0, n_rec * sizeof(grp_fastq_record)) != GRP_OK) {
       return fail2(GRP_ERR_HIP);
     }
-    k_ing_words<<<dim3(1), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.dm_scal) + 1, reinterpret_cast<const unsigned long long*>(d_nl + (4 * n_rec - 1)), 1);
-    if (n_rec * sizeof(grp_fastq_record) > ip.rec_bytes) {
-      (void)hipFree(ip.d_rec);
-      ip.d_rec = nullptr;
-      ip.rec_bytes = 0;
-      const uint64_t want = (n_rec + n_rec / 4 + 64) * sizeof(grp_fastq_record);
-      FQ_TRY2(hipMalloc(&ip.d_rec, want));
-      ip.rec_bytes = want;
+    k_ing_words<<<dim3(1), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.h_scal.dev) + 1, reinterpret_cast<const unsigned long long*>(d_nl + (4 * n_rec - 1)), 1);
+    if (n_rec * sizeof(grp_fastq_record) > ip.d_rec.cap) {
+      FQ_TRY2(ip.d_rec.reset((n_rec + n_rec / 4 + 64) * sizeof(grp_fastq_record)));
     }
-    grp_fastq_record* const d_rec = static_cast<grp_fastq_record*>(ip.d_rec);
+    grp_fastq_record* const d_rec = reinterpret_cast<grp_fastq_record*>(ip.d_rec.p);
     k_fq_records<<<dim3((uint32_t)((n_rec + (THREADS / 64) - 1) / (THREADS / 64))), dim3(THREADS), 0, ps>>>(fq->d_text, d_nl, n_rec, lead, d_rec);
     k_fq_phred<<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog, d_rec);
     FQ_TRY2(hipGetLastError());
     static_assert(sizeof(grp_fastq_record) % 8 == 0, "the record table goes down as 64-bit words");
     const uint64_t rec_words = n_rec * sizeof(grp_fastq_record) / 8;
-    k_ing_words<<<dim3((uint32_t)std::min<uint64_t>((rec_words + THREADS - 1) / THREADS, 256)), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.dm_rec), reinterpret_cast<const unsigned long long*>(d_rec), rec_words);
+    k_ing_words<<<dim3((uint32_t)std::min<uint64_t>((rec_words + THREADS - 1) / THREADS, 256)), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.h_rec.dev), reinterpret_cast<const unsigned long long*>(d_rec), rec_words);
     FQ_TRY2(hipGetLastError());
     FQ_TRY2(hipStreamSynchronize(ps));
     const uint64_t last_nl = ip.h_scal[1];
@@ -636,13 +622,12 @@ grp_fastq_prefetch(grp_ctx* c, const char* text, uint64_t n_bytes)
     }
     if (!ip.text[i]) {
       const uint64_t want = FQ_FRONT + n_bytes + n_bytes / 8 + 64;
-      if (hipMalloc(&ip.text[i], want) != hipSuccess) {
+      if (ip.text[i].reset(want) != hipSuccess) {
         (void)hipGetLastError();
         return GRP_ERR_BUSY;
       }
-      ip.text_cap[i] = want;
     }
-    if (ip.text_cap[i] >= FQ_FRONT + n_bytes + 64) {
+    if (ip.text[i].cap >= FQ_FRONT + n_bytes + 64) {
       slot = i;
     }
   }
@@ -657,7 +642,7 @@ grp_fastq_prefetch(grp_ctx* c, const char* text, uint64_t n_bytes)
   HIP_TRY(c, hipMemcpyAsync(ip.text[slot] + FQ_FRONT, text, n_bytes, hipMemcpyHostToDevice, c->stream3));
   HIP_TRY(c, hipMemsetAsync(ip.text[slot] + FQ_FRONT + n_bytes, 0, 64, c->stream3));
   if (!ip.text_up[slot]) {
-    HIP_TRY(c, hipEventCreateWithFlags(&ip.text_up[slot], hipEventDisableTiming));
+    HIP_TRY(c, ip.text_up[slot].create(hipEventDisableTiming));
   }
   HIP_TRY(c, hipEventRecord(ip.text_up[slot], c->stream3));
   ip.pre[ip.n_pre].slot = slot;
@@ -688,7 +673,6 @@ grp_fastq_pack(grp_ctx* c, grp_fastq* fq, const uint32_t* sel, uint32_t n_sel, g
   }
   HIP_TRY(c, hipSetDevice(c->device));
   grp_reads* rd = new grp_reads();
-  rd->owns_packed = true;
   std::vector<uint64_t>&seq_off = rd->h_seq_off, &word_off = rd->h_word_off; // (the copies below read them: they stay with the batch)
   seq_off.resize(n_sel);
   word_off.resize((size_t)n_sel + 1);
@@ -727,40 +711,40 @@ grp_fastq_pack(grp_ctx* c, grp_fastq* fq, const uint32_t* sel, uint32_t n_sel, g
   const uint64_t o_wo = 0, o_t0 = o_wo + up8(((uint64_t)n_sel + 1) * 8), o_c0 = o_t0 + up8(((uint64_t)n_sel + 1) * 8), o_so = o_c0 + up8(((uint64_t)n_sel + 1) * 8);
   const uint64_t o_len = o_so + up8(std::max<uint64_t>(n_sel, 1) * 8), o_tr = o_len + up8(std::max<uint64_t>(n_sel, 1) * 4), o_cr = o_tr + up8(std::max<uint64_t>(nt, 1) * 4);
   const uint64_t slab_bytes = o_cr + up8(std::max<uint64_t>(nch, 1) * 4);
-  if (hipMalloc(&rd->d_packed, std::max<uint64_t>(w, 1) * 4 + 16) != hipSuccess || hipMalloc(&rd->d_slab, slab_bytes) != hipSuccess) {
-    return bail(set_err(c, GRP_ERR_NOMEM, "grp_fastq_pack: hipMalloc(%llu words + %llu bytes) failed", (unsigned long long)w, (unsigned long long)slab_bytes));
+  if (rd->d_packed.reset(std::max<uint64_t>(w, 1) + 4) != hipSuccess || rd->d_slab.reset(slab_bytes) != hipSuccess) {
+    return bail(set_err(c, GRP_ERR_NOMEM, "grp_fastq_pack: allocating %llu words + %llu bytes of device memory failed", (unsigned long long)w, (unsigned long long)slab_bytes));
   }
-  uint8_t* const slab = static_cast<uint8_t*>(rd->d_slab);
-  rd->d_word_off = reinterpret_cast<uint64_t*>(slab + o_wo);
-  rd->d_tile0 = reinterpret_cast<uint64_t*>(slab + o_t0);
-  rd->d_chunk0 = reinterpret_cast<uint64_t*>(slab + o_c0);
+  uint8_t* const slab = rd->d_slab;
+  uint64_t* const d_word_off = reinterpret_cast<uint64_t*>(slab + o_wo);
+  uint64_t* const d_tile0 = reinterpret_cast<uint64_t*>(slab + o_t0);
+  uint64_t* const d_chunk0 = reinterpret_cast<uint64_t*>(slab + o_c0);
   uint64_t* const d_so = reinterpret_cast<uint64_t*>(slab + o_so);
-  rd->d_len = reinterpret_cast<uint32_t*>(slab + o_len);
-  rd->d_tile_read = reinterpret_cast<uint32_t*>(slab + o_tr);
-  rd->d_chunk_read = reinterpret_cast<uint32_t*>(slab + o_cr);
-  hipError_t e = hipMemcpyAsync(rd->d_word_off, word_off.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rd->d_tile0, rd->tile0.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rd->d_chunk0, rd->chunk0.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
+  uint32_t* const d_len = reinterpret_cast<uint32_t*>(slab + o_len);
+  uint32_t* const d_tile_read = reinterpret_cast<uint32_t*>(slab + o_tr);
+  uint32_t* const d_chunk_read = reinterpret_cast<uint32_t*>(slab + o_cr);
+  hipError_t e = hipMemcpyAsync(d_word_off, word_off.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tile0, rd->tile0.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_chunk0, rd->chunk0.data(), ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && n_sel) e = hipMemcpyAsync(d_so, seq_off.data(), (size_t)n_sel * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && n_sel) e = hipMemcpyAsync(rd->d_len, rd->len.data(), (size_t)n_sel * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nt) e = hipMemcpyAsync(rd->d_tile_read, rd->h_tile_read.data(), nt * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && nch) e = hipMemcpyAsync(rd->d_chunk_read, rd->h_chunk_read.data(), nch * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && n_sel) e = hipMemcpyAsync(d_len, rd->len.data(), (size_t)n_sel * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && nt) e = hipMemcpyAsync(d_tile_read, rd->h_tile_read.data(), nt * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && nch) e = hipMemcpyAsync(d_chunk_read, rd->h_chunk_read.data(), nch * 4, hipMemcpyHostToDevice, c->stream);
   if (e != hipSuccess) {
     return bail(set_err(c, GRP_ERR_HIP, "grp_fastq_pack: upload failed: %s", hipGetErrorString(e)));
   }
   if (n_sel) {
-    k_fq_pack<<<dim3(n_sel), dim3(THREADS), 0, c->stream>>>(fq->d_text + fq->lead, d_so, rd->d_len, rd->d_word_off, rd->d_packed);
+    k_fq_pack<<<dim3(n_sel), dim3(THREADS), 0, c->stream>>>(fq->d_text + fq->lead, d_so, d_len, d_word_off, rd->d_packed);
     if (hipGetLastError() != hipSuccess) {
       return bail(set_err(c, GRP_ERR_HIP, "grp_fastq_pack: kernel launch failed"));
     }
   }
   rd->dev.packed = rd->d_packed;
-  rd->dev.word_off = rd->d_word_off;
-  rd->dev.len = rd->d_len;
-  rd->dev.tile0 = rd->d_tile0;
-  rd->dev.tile_read = rd->d_tile_read;
-  rd->dev.chunk0 = rd->d_chunk0;
-  rd->dev.chunk_read = rd->d_chunk_read;
+  rd->dev.word_off = d_word_off;
+  rd->dev.len = d_len;
+  rd->dev.tile0 = d_tile0;
+  rd->dev.tile_read = d_tile_read;
+  rd->dev.chunk0 = d_chunk0;
+  rd->dev.chunk_read = d_chunk_read;
   *out = rd;
   return GRP_OK;
 }
@@ -824,7 +808,7 @@ grp_fastq_free(grp_fastq* fq)
     bool marked = false;
     if (fq->ctx->stream) {
       if (!ip.text_done[fq->pool_slot]) {
-        (void)hipEventCreateWithFlags(&ip.text_done[fq->pool_slot], hipEventDisableTiming);
+        (void)ip.text_done[fq->pool_slot].create(hipEventDisableTiming);
       }
       marked = ip.text_done[fq->pool_slot] && hipEventRecord(ip.text_done[fq->pool_slot], fq->ctx->stream) == hipSuccess;
     }
@@ -836,7 +820,6 @@ grp_fastq_free(grp_fastq* fq)
     if (fq->ctx && fq->ctx->stream) {
       (void)hipStreamSynchronize(fq->ctx->stream);
     }
-    (void)hipFree(fq->d_text);
   }
   delete fq;
 }

@@ -111,7 +111,7 @@ grp_ntcard_begin(grp_ctx* c, uint32_t sbits)
   HIP_TRY(c, hipSetDevice(c->device));
   const uint64_t n = ((uint64_t)c->params.h * NTC_NSAMP) << NTC_RBITS;
   if (!c->d_ntc) {
-    HIP_TRY(c, hipMalloc(&c->d_ntc, n * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_ntc.reset(n));
   }
   HIP_TRY(c, hipMemsetAsync(c->d_ntc, 0, n * sizeof(uint32_t), c->stream));
   c->ntc_sbits = sbits;
@@ -151,9 +151,9 @@ grp_ntcard_add(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, c
   if (chunks.size() > MAX_GRID_WGS) { // 2^22 chunks = 8.6 G bases per call
     return set_err(c, GRP_ERR_INVALID, "grp_ntcard_add: too many bases in one call");
   }
-  int rc = ensure_dev(c, c->d_ntc_chunks, c->ntc_chunks_cap, chunks.size());
+  int rc = ensure_dev(c, c->d_ntc_chunks, chunks.size());
   if (rc == GRP_OK && stale_extra) {
-    rc = ensure_dev(c, c->d_ntc_extra, c->ntc_extra_cap, (uint64_t)count * h);
+    rc = ensure_dev(c, c->d_ntc_extra, (uint64_t)count * h);
   }
   if (rc != GRP_OK) {
     return rc;
@@ -186,8 +186,8 @@ grp_ntcard_finish(grp_ctx* c, uint64_t* zero_buckets)
   }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t tables = c->params.h * NTC_NSAMP;
-  unsigned long long* d_z = nullptr;
-  HIP_TRY(c, hipMalloc(&d_z, tables * sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d_z;
+  HIP_TRY(c, d_z.reset(tables));
   hipError_t e = hipMemsetAsync(d_z, 0, tables * sizeof(unsigned long long), c->stream);
   if (e == hipSuccess) {
     k_ntcard_zeros<<<dim3(2048, tables), dim3(THREADS), 0, c->stream>>>(c->d_ntc, d_z);
@@ -199,9 +199,7 @@ grp_ntcard_finish(grp_ctx* c, uint64_t* zero_buckets)
   if (e == hipSuccess) {
     e = hipStreamSynchronize(c->stream);
   }
-  (void)hipFree(d_z);
-  (void)hipFree(c->d_ntc);
-  c->d_ntc = nullptr;
+  clear_all(d_z, c->d_ntc);
   if (e != hipSuccess) {
     return set_err(c, GRP_ERR_HIP, "grp_ntcard_finish: %s", hipGetErrorString(e));
   }

@@ -344,19 +344,6 @@ k_touch_fill(uint32_t* __restrict__ table, uint64_t n_words, uint32_t threshold_
 
 } // namespace
 
-namespace {
-struct PsOnExit // (developer entry points: what they allocate lives for one call)
-{
-  std::function<void()> f;
-  ~PsOnExit()
-  {
-    if (f) {
-      f();
-    }
-  }
-};
-} // namespace
-
 extern "C" {
 
 // Measurement (VERDICT r04 item 4): the hash-and-test pass of a touched-rank filter of `table_mib` MiB with a share
@@ -389,25 +376,15 @@ grp_debug_touch_filter(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t 
     return set_err(c, GRP_ERR_INVALID, "grp_debug_touch_filter: %llu tiles", (unsigned long long)nt);
   }
   const uint64_t n_words = (uint64_t)table_mib << 18;
-  uint32_t* d_table = nullptr;
-  unsigned long long* d_dirty = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PsOnExit tidy{ [&] { // every way out — the HIP_TRY returns below included (ADVICE r05) — frees what was taken
-    if (e0) {
-      (void)hipEventDestroy(e0);
-    }
-    if (e1) {
-      (void)hipEventDestroy(e1);
-    }
-    (void)hipFree(d_table);
-    (void)hipFree(d_dirty);
-  } };
-  HIP_TRY(c, hipMalloc(&d_table, n_words * 4));
-  HIP_TRY(c, hipMalloc(&d_dirty, 8));
+  DevBuf<uint32_t> d_table; // (developer entry points: what they allocate lives for one call)
+  DevBuf<unsigned long long> d_dirty;
+  Event e0, e1;
+  HIP_TRY(c, d_table.reset(n_words));
+  HIP_TRY(c, d_dirty.reset(1));
   k_touch_fill<<<dim3(4096), dim3(THREADS), 0, c->stream>>>(d_table, n_words, (uint32_t)(fill * 1048576.0));
   const size_t lds = tab_bytes(c) + bases_bytes(tile + c->params.k + H);
-  HIP_TRY(c, hipEventCreate(&e0));
-  HIP_TRY(c, hipEventCreate(&e1));
+  HIP_TRY(c, e0.create(hipEventDefault));
+  HIP_TRY(c, e1.create(hipEventDefault));
   float best = 1e30f;
   for (int rep = 0; rep < 3; ++rep) {
     HIP_TRY(c, hipMemsetAsync(d_dirty, 0, 8, c->stream));
@@ -484,33 +461,25 @@ grp_pshard_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   if (ps.bin_cap >= (1ull << 32)) {
     return set_err(c, GRP_ERR_INVALID, "grp_pshard_query: window too large (a bin holds < 2^32 records)");
   }
-  grp_tile_summary* d_tiles = nullptr;
-  grp_id_count* d_lists = nullptr;
-  unsigned long long* d_ctr = nullptr;
-  hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-  PsOnExit tidy{ [&] { // every way out — the HIP_TRY returns below included (ADVICE r05) — frees what was taken
-    for (auto& e : ev) {
-      if (e) {
-        (void)hipEventDestroy(e);
-      }
-    }
-    (void)hipFree(ps.bin_fill);
-    (void)hipFree(ps.keys);
-    (void)hipFree(ps.tags);
-    (void)hipFree(ps.answers);
-    (void)hipFree(ps.segs);
-    (void)hipFree(d_tiles);
-    (void)hipFree(d_lists);
-    (void)hipFree(d_ctr);
-  } };
+  DevBuf<unsigned long long> bin_fill, keys, d_ctr; // (the views go into `ps`)
+  DevBuf<uint16_t> tags;
+  DevBuf<uint32_t> answers;
+  DevBuf<uint2> segs;
+  DevBuf<grp_tile_summary> d_tiles;
+  DevBuf<grp_id_count> d_lists;
+  Event ev[5];
   const uint64_t lcap = std::max<uint64_t>(list_cap, 1);
-  if (hipMalloc(&ps.bin_fill, PS_MAX_OWNERS * 8) != hipSuccess || hipMalloc(&ps.keys, n_owners * ps.bin_cap * 8) != hipSuccess || hipMalloc(&ps.tags, n_owners * ps.bin_cap * 2) != hipSuccess ||
-      hipMalloc(&ps.answers, n_owners * ps.bin_cap * 4) != hipSuccess || hipMalloc(&ps.segs, nt * n_owners * sizeof(uint2)) != hipSuccess || hipMalloc(&d_tiles, nt * sizeof(grp_tile_summary)) != hipSuccess ||
-      hipMalloc(&d_lists, lcap * sizeof(grp_id_count)) != hipSuccess || hipMalloc(&d_ctr, 8) != hipSuccess) {
+  if (bin_fill.reset(PS_MAX_OWNERS) != hipSuccess || keys.reset(n_owners * ps.bin_cap) != hipSuccess || tags.reset(n_owners * ps.bin_cap) != hipSuccess || answers.reset(n_owners * ps.bin_cap) != hipSuccess ||
+      segs.reset(nt * n_owners) != hipSuccess || d_tiles.reset(nt) != hipSuccess || d_lists.reset(lcap) != hipSuccess || d_ctr.reset(1) != hipSuccess) {
     return set_err(c, GRP_ERR_NOMEM, "grp_pshard_query: no memory for the bins of %llu probes", (unsigned long long)probes);
   }
-  for (auto& e : ev) {
-    HIP_TRY(c, hipEventCreate(&e));
+  ps.bin_fill = bin_fill;
+  ps.keys = keys;
+  ps.tags = tags;
+  ps.answers = answers;
+  ps.segs = segs;
+  for (Event& e : ev) {
+    HIP_TRY(c, e.create(hipEventDefault));
   }
   HIP_TRY(c, hipMemsetAsync(ps.bin_fill, 0, PS_MAX_OWNERS * 8, c->stream));
   HIP_TRY(c, hipMemsetAsync(d_ctr, 0, 8, c->stream));

@@ -436,17 +436,10 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   // Per read of the batch: its entry in the insert list (the kernels tell from it which tiles have records).  The
   // floors travel in the same page-locked block: one copy per call, nothing per tile on the host.
   const uint32_t h = c->params.h, ftile = tile_frames(c);
-  if ((uint64_t)count + total > br.vf_stage_cap) {
-    if (br.h_vf_stage) {
-      (void)hipHostFree(br.h_vf_stage);
-      br.h_vf_stage = nullptr;
-    }
-    br.vf_stage_cap = 0;
-    const uint64_t n = 2 * ((uint64_t)count + total) + 4096;
-    HIP_TRY(c, hipHostMalloc(&br.h_vf_stage, n * sizeof(uint32_t), hipHostMallocDefault));
-    br.vf_stage_cap = n;
+  if ((uint64_t)count + total > br.h_vf_stage.cap) {
+    HIP_TRY(c, br.h_vf_stage.reset(2 * ((uint64_t)count + total) + 4096, hipHostMallocDefault));
   }
-  rc = ensure_dev(c, br.d_vf_stage, br.vf_stage_dev_cap, (uint64_t)count + total);
+  rc = ensure_dev(c, br.d_vf_stage, (uint64_t)count + total);
   if (rc != GRP_OK) {
     return rc;
   }
@@ -490,14 +483,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   auto enqueue = [&]() -> int {
     c->q = &so;
     redo_on_device = false;
-    int erc = ensure_dev(c, so.d_tiles, so.d_tiles_cap, nt_all);
-    if (erc == GRP_OK) {
-      erc = ensure_dev(c, so.d_lists, so.d_lists_cap, std::max<uint64_t>(so.list_cap, 1));
-    }
-    if (erc == GRP_OK) {
-      erc = ensure_dev(c, so.d_flag_idx, so.d_flag_cap, nt_all);
-    }
-    if (erc != GRP_OK) {
+    if (const int erc = slot_query_bufs(c, so, nt_all, std::max<uint64_t>(so.list_cap, 1)); erc != GRP_OK) {
       return erc;
     }
     if (so.side_used) {
@@ -516,7 +502,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       vf.n_reads = count;
       Timer t(c, GRP_K_VERIFY, r_records);
       DISPATCH_HW(c, (k_batch_delta<HH, WW><<<dim3((uint32_t)nt_batch), dim3(THREADS), lds_delta, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, b, bv, vf, so.d_tiles, so.d_lists, so.list_cap,
-                                                                                                             reinterpret_cast<unsigned long long*>(so.d_qctr), so.d_flag_idx, (uint32_t)so.d_flag_cap)));
+                                                                                                             reinterpret_cast<unsigned long long*>(so.d_qctr.p), so.d_flag_idx, (uint32_t)so.d_flag_idx.cap)));
       HIP_TRY(c, hipGetLastError());
     }
     const QueryGeom g = query_geom(c, false);
@@ -550,7 +536,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       // A list longer than the launch takes the old way below.
       Timer t(c, GRP_K_QUERY, 0);
       DevBatchView bf = bv;
-      bf.redo_count = reinterpret_cast<const unsigned long long*>(so.d_qctr) + 4;
+      bf.redo_count = reinterpret_cast<const unsigned long long*>(so.d_qctr.p) + 4;
       c->view = &bf;
       const QueryGeom gf = query_geom(c, true);
       lrc = launch_query(c, r, VERIFY_REDO_ON_DEVICE, t0, so.d_flag_idx, gf, so.list_cap);
@@ -561,7 +547,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       HIP_TRY(c, hipGetLastError());
       redo_on_device = true;
     }
-    erc = classify_enqueue_decide(c, so, c->stream);
+    int erc = classify_enqueue_decide(c, so, c->stream);
     if (erc == GRP_OK) {
       erc = classify_enqueue_fetch(c, so, c->stream);
     }
@@ -602,7 +588,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
     }
     c->n_verify_uncertified += so.h_qctr[6];
     c->n_verify_unpatched += so.h_qctr[7];
-    if (so.h_qctr[4] && redo_on_device && so.h_qctr[4] <= VERIFY_REDO_ON_DEVICE && so.h_qctr[4] <= so.d_flag_cap) {
+    if (so.h_qctr[4] && redo_on_device && so.h_qctr[4] <= VERIFY_REDO_ON_DEVICE && so.h_qctr[4] <= so.d_flag_idx.cap) {
       // redone behind the patch, inside the launches that have just been waited for
       c->n_verify_flagged += so.h_qctr[4];
       c->n_flagged_tiles += so.h_qctr[4];

@@ -17,6 +17,7 @@
 // Seeds of spans 65 .. 256 bases (DevSeeds::wide == 2, long_span) run their own
 // instantiation of every hashing kernel, WT == GRP_WT_LONG (DISPATCH_H_SPAN / DISPATCH_HW
 // pick it); the forms of spans up to 64 are untouched.
+#include "grp_buffers.h"
 #include "grp_device.h"
 #include "host/gr_tile_geom.hpp"
 #include "host/gr_tiles_core.hpp"
@@ -27,7 +28,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <chrono>
 #include <cmath>
 #include <mutex>
@@ -45,8 +45,8 @@ thread_local std::string g_create_error;
 
 struct EventPair
 {
-  hipEvent_t a, b;
-  int kind;
+  Event a, b;
+  int kind = 0;
 };
 
 } // namespace
@@ -55,65 +55,52 @@ struct EventPair
 // per-window device / pinned buffers of the query + decision kernels
 struct QuerySlot
 {
-  grp_tile_summary* d_tiles = nullptr;
-  uint64_t d_tiles_cap = 0;
-  grp_id_count* d_lists = nullptr;
-  uint64_t d_lists_cap = 0;
-  uint64_t* d_qctr = nullptr; // [3] list arena cursor, [4] flagged tiles (kept zero between calls)
+  DevBuf<grp_tile_summary> d_tiles;
+  DevBuf<grp_id_count> d_lists;
+  DevBuf<uint64_t> d_qctr; // [3] list arena cursor, [4] flagged tiles (kept zero between calls)
   uint64_t* h_qctr = nullptr; // pinned: the first 64 bytes of h_dec_raw (one copy brings counters and decisions, slot_dec_alloc)
-  uint32_t* d_flag_idx = nullptr;
-  uint64_t d_flag_cap = 0;
-  // decide scratch
-  uint32_t* d_dec_ids = nullptr;
-  uint8_t* d_dec_asg = nullptr;
-  uint64_t* d_dec_scratch = nullptr;
-  std::vector<uint32_t> h_long_reads; // reads of the window of more than 256 tiles: decided by a launch of their own (classify_enqueue_decide)
-  uint32_t* d_long_reads = nullptr;
-  uint64_t long_reads_cap = 0;
+  DevBuf<uint32_t> d_flag_idx;
+  // decide scratch: one capacity for the three (slot_dec_scratch)
+  DevBuf<uint32_t> d_dec_ids;
+  DevBuf<uint8_t> d_dec_asg;
+  DevBuf<uint64_t> d_dec_scratch;
   uint64_t d_dec_cap = 0;
+  std::vector<uint32_t> h_long_reads; // reads of the window of more than 256 tiles: decided by a launch of their own (classify_enqueue_decide)
+  DevBuf<uint32_t> d_long_reads;
   grp_read_decision* d_dec = nullptr; // = d_dec_raw + 2: two entries (64 bytes) in front of the decisions carry the window's counters
   grp_read_decision* h_dec = nullptr; // = h_dec_raw + 2, pinned
-  grp_read_decision* d_dec_raw = nullptr;
-  grp_read_decision* h_dec_raw = nullptr;
-  uint64_t dec_cap = 0;
+  DevBuf<grp_read_decision> d_dec_raw;
+  HostBuf<grp_read_decision> h_dec_raw;
   // a window in flight (grp_classify_reads_begin)
-  hipEvent_t done = nullptr;   // decisions of the window are in h_dec
-  hipEvent_t qdone = nullptr;  // the window's query kernel has finished (decide stream waits on it)
+  Event done;                  // decisions of the window are in h_dec
+  Event qdone;                 // the window's query kernel has finished (decide stream waits on it)
   bool side_used = false;      // `done` was last recorded on the decide stream
   // streaming window (grp_classify_stream_*)
-  grp_read_decision* h_sdec = nullptr;    // mapped, coherent: the kernel publishes decisions here
-  grp_read_decision* dmap_sdec = nullptr;
-  uint64_t sdec_cap = 0;
+  HostBuf<grp_read_decision> h_sdec;      // mapped, coherent: the kernel publishes decisions here
   // abort flag: the host raises the one in mapped host memory (a plain store); every
   // 64th workgroup reads that one when it starts and relays it to the flag in DEVICE
   // memory, which is what all workgroups test (a PCIe round trip in every workgroup
   // costs the kernel 2.4x, measured; a 4-byte hipMemcpyAsync takes ~1.5 ms to land
   // beside a full-device kernel, measured)
-  uint32_t* d_abort = nullptr;
-  uint32_t* h_abort = nullptr;            // mapped, coherent
-  uint32_t* dmap_abort = nullptr;
-  uint32_t* d_tiles_done = nullptr;
-  uint64_t tiles_done_cap = 0;
-  unsigned long long* d_executed = nullptr;
-  unsigned long long* h_executed = nullptr; // pinned
+  DevBuf<uint32_t> d_abort;
+  HostBuf<uint32_t> h_abort;              // mapped, coherent
+  DevBuf<uint32_t> d_tiles_done;
+  DevBuf<unsigned long long> d_executed;
+  HostBuf<unsigned long long> h_executed; // pinned
   bool streaming = false;
   // a streaming window that applies inserts itself (grp_classify_stream_insert)
-  uint32_t* d_tile_ver = nullptr; // round 6: per tile of a resumable window, the generation its summary belongs to (DevStreamCtl::tile_ver)
-  uint64_t tile_ver_cap = 0;
-  uint32_t* d_rel = nullptr;    // release words of a resumable window's grid-wide waits: a 128-byte line per workgroup (STREAM_REL_WGS of them)
-  uint32_t* d_dbg = nullptr;    // developer (GRP_STREAM_DEBUG): a state word per workgroup of the streaming launch
-  uint32_t* d_sctl = nullptr;   // SCT_* control block
-  uint32_t* h_cmd = nullptr;    // mapped, coherent: [0] sequence number, [1..10] the command
-  uint32_t* dmap_cmd = nullptr;
-  uint32_t* h_ack = nullptr;    // mapped, coherent: [0] inserts applied by the launch, [1] failure code
-  uint32_t* dmap_ack = nullptr;
+  DevBuf<uint32_t> d_tile_ver; // round 6: per tile of a resumable window, the generation its summary belongs to (DevStreamCtl::tile_ver)
+  DevBuf<uint32_t> d_rel;      // release words of a resumable window's grid-wide waits: a 128-byte line per workgroup (STREAM_REL_WGS of them)
+  DevBuf<uint32_t> d_dbg;      // developer (GRP_STREAM_DEBUG): a state word per workgroup of the streaming launch
+  DevBuf<uint32_t> d_sctl;     // SCT_* control block
+  HostBuf<uint32_t> h_cmd;     // mapped, coherent: [0] sequence number, [1..10] the command
+  HostBuf<uint32_t> h_ack;     // mapped, coherent: [0] inserts applied by the launch, [1] failure code
   bool resumable = false;       // the window in flight takes grp_classify_stream_insert
   uint32_t stripe_reads = 0, n_owners = 1, owner = 0; // its stripes (0: the whole window is this launch's)
   uint32_t gen = 1;             // generation of the records the host is waiting for
   uint32_t cmd_seq = 0;         // commands posted to the window in flight
-  uint32_t* h_stripe_tiles = nullptr; // pinned: this rank's tiles of a striped window
-  uint32_t* d_stripe_tiles = nullptr;
-  uint64_t stripe_tiles_cap = 0;
+  HostBuf<uint32_t> h_stripe_tiles; // pinned: this rank's tiles of a striped window
+  DevBuf<uint32_t> d_stripe_tiles;
   bool busy = false;
   const grp_reads* reads = nullptr;
   uint32_t first = 0, count = 0;
@@ -130,64 +117,76 @@ struct BatchRun
   bool active = false;
   uint32_t n_ins = 0, block_tiles = 0;
   uint64_t n_units = 0, n_rec = 0;
-  uint32_t* h_counters = nullptr; // page-locked [4]: records that own a chain, chained touches, log entries, error
+  HostBuf<uint32_t> h_counters;   // page-locked [4]: records that own a chain, chained touches, log entries, error
   std::vector<uint32_t> h_ins;    // [n_ins][6]: read, tile_start, tile_end, first_id, id_offset, first unit
-  uint32_t* h_ins_stage = nullptr; // page-locked copy of h_ins: the upload does not wait for the stream
-  uint64_t ins_stage_cap = 0;
-  uint32_t* d_counters = nullptr; // two sets of 4: a batch's clean-up zeroes the NEXT batch's set (k_batch_clear)
+  HostBuf<uint32_t> h_ins_stage;  // page-locked copy of h_ins: the upload does not wait for the stream
+  DevBuf<uint32_t> d_counters;    // two sets of 4: a batch's clean-up zeroes the NEXT batch's set (k_batch_clear)
   uint32_t ctr_set = 0;
-  uint32_t* d_ins = nullptr;
-  uint64_t ins_cap = 0;
+  DevBuf<uint32_t> d_ins;
   uint32_t epoch = 0; // of the current / last batch: the claim field of the count words (grp_device.h), 1 .. GRP_EPOCH_MAX
-  uint64_t tab_cap = 0, cur_cap = 0;    // allocated slots / slots the current batch uses (both tables)
-  unsigned long long* d_rec_key = nullptr; // records, one per (frame, seed) of the inserted tiles
-  unsigned long long* d_rec_loc = nullptr;
-  unsigned long long* d_rec_old = nullptr;
-  uint32_t* d_rec_chain = nullptr;
+  uint64_t tab_cap = 0, cur_cap = 0;    // allocated slots / slots the current batch uses (the three log tables)
+  DevBuf<unsigned long long> d_rec_key; // records, one per (frame, seed) of the inserted tiles
+  DevBuf<unsigned long long> d_rec_loc;
+  DevBuf<unsigned long long> d_rec_old;
+  DevBuf<uint32_t> d_rec_chain;
   uint64_t rec_cap = 0;
-  uint32_t* d_ovf_next = nullptr; // touches of a rank by other (read, block)s than its owner's, chained per record
-  uint32_t* d_ovf_jb = nullptr;
-  uint32_t* d_chained = nullptr; // the records that own a chain (k_batch_apply walks these, not all records)
+  DevBuf<uint32_t> d_ovf_next; // touches of a rank by other (read, block)s than its owner's, chained per record
+  DevBuf<uint32_t> d_ovf_jb;
+  DevBuf<uint32_t> d_chained;  // the records that own a chain (k_batch_apply walks these, not all records)
   uint64_t ovf_cap = 0;
-  unsigned long long* d_log_keys = nullptr;
-  uint32_t* d_log_head = nullptr;
-  uint32_t* d_log_bits = nullptr; // 1 bit per log table slot: something was logged with this home slot
-  uint64_t log_tab_cap = 0;
-  uint32_t* d_log_old = nullptr;
-  uint32_t* d_log_writer = nullptr;
-  uint32_t* d_log_next = nullptr;
-  uint32_t* d_log_slot = nullptr; // log entry -> its slot in the log table (to clean it)
+  DevBuf<unsigned long long> d_log_keys;
+  DevBuf<uint32_t> d_log_head;
+  DevBuf<uint32_t> d_log_bits; // 1 bit per log table slot: something was logged with this home slot
+  DevBuf<uint32_t> d_log_old;
+  DevBuf<uint32_t> d_log_writer;
+  DevBuf<uint32_t> d_log_next;
+  DevBuf<uint32_t> d_log_slot; // log entry -> its slot in the log table (to clean it)
   uint64_t log_cap = 0;
-  uint32_t* d_floor = nullptr;    // grp_batch_classify: per read of the window
-  uint64_t floor_cap = 0;
+  DevBuf<uint32_t> d_floor;    // grp_batch_classify: per read of the window
   // grp_batch_verify: the window's tiles with records, then the tiles queried again; per read its insert entry
-  uint32_t* h_vf_stage = nullptr; // page-locked: per read of the batch its insert entry, then the floors
-  uint64_t vf_stage_cap = 0;
-  uint32_t* d_vf_stage = nullptr;
-  uint64_t vf_stage_dev_cap = 0;
+  HostBuf<uint32_t> h_vf_stage; // page-locked: per read of the batch its insert entry, then the floors
+  DevBuf<uint32_t> d_vf_stage;
   uint32_t first_read = 0;        // reads are numbered from here in the log
 };
 
 constexpr int FQ_TEXT_SLOTS = 3; // device text buffers of the FASTQ ingest (grp_ingest.inc)
 
-struct grp_ctx
+// The stream handles are a base of the context: a base is destroyed after every member, so the buffers and events
+// below free themselves in `delete c` while the streams still exist, and the streams go last.
+struct CtxStreams
 {
-  int device = 0;
-  std::string arch;
-  bool coherent_arch = false; // gfx942 / gfx950: agent-scope accesses are served by the memory side
-  BatchRun batch;
   hipStream_t stream = nullptr;
   // decision kernel + copy-back of a pipelined window run here, next to the following
   // window's query kernel on `stream`
   hipStream_t stream2 = nullptr;
   hipStream_t stream3 = nullptr; // the uploads of coming FASTQ chunks (grp_fastq_prefetch): a copy must not stand in front of the parse of the chunk before it
+  ~CtxStreams()
+  {
+    for (hipStream_t s : { stream3, stream2, stream }) {
+      if (s) {
+        (void)hipStreamDestroy(s);
+      }
+    }
+  }
+};
+
+struct grp_ctx : CtxStreams
+{
+  int device = 0;
+  std::string arch;
+  bool coherent_arch = false; // gfx942 / gfx950: agent-scope accesses are served by the memory side
+  BatchRun batch;
   grp_params params{};
   std::vector<std::string> seeds;
   DevSeeds h_seeds{};
-  DevSeeds* d_seeds = nullptr;
-  uint32_t* d_gtab = nullptr; // count tables of k_query<..., GT> (query_geom: tiles whose worst case does not fit the LDS)
-  uint64_t gtab_cap = 0;
-  DevFilter f{};
+  DevBuf<DevSeeds> d_seeds;
+  DevBuf<uint32_t> d_gtab; // count tables of k_query<..., GT> (query_geom: tiles whose worst case does not fit the LDS)
+  DevFilter f{}; // the view the kernels take; the memory belongs to the owners below
+  DevBuf<uint32_t> bv;
+  DevBuf<uint4> buckets;
+  DevBuf<ulonglong2> far;
+  DevBuf<unsigned long long> ovf_keys;
+  DevBuf<uint32_t> ovf_ids;
   uint64_t nsb = 0;      // superbuckets
   uint64_t n_bv_words = 0;
   uint64_t n_ovf = 0;    // IDs living in the overflow table
@@ -200,14 +199,10 @@ struct grp_ctx
   // grp_window_overlap (grp_batch.inc): samples per tile, their table, the result per read
   struct OverlapBuf
   {
-    unsigned long long* d_samples = nullptr;
-    uint64_t samples_cap = 0; // in tiles
-    uint32_t* d_n = nullptr;
-    uint64_t n_cap = 0;
-    unsigned long long* d_tab = nullptr;
-    uint64_t tab_cap = 0;
-    uint32_t* d_prev = nullptr;
-    uint64_t prev_cap = 0;
+    DevBuf<unsigned long long> d_samples;
+    DevBuf<uint32_t> d_n;
+    DevBuf<unsigned long long> d_tab;
+    DevBuf<uint32_t> d_prev;
   } ovl;
   uint64_t n_overlap_calls = 0;
   uint32_t batch_epochs = GRP_EPOCH_MAX; // batches between two sweeps of the claims (GRP_BATCH_EPOCHS: tests)
@@ -219,29 +214,26 @@ struct grp_ctx
   uint64_t n_verify_tiles = 0, n_verify_queried = 0, n_verify_flagged = 0, n_verify_fallbacks = 0, n_verify_uncertified = 0, n_verify_unpatched = 0; // grp_batch_verify: tiles patched from records / queried again / patched tiles redone / calls that took the second query
   uint64_t n_direct_windows = 0, n_direct_fallbacks = 0, n_general_windows = 0, n_redo_launches = 0; // GRP_DEBUG_STATS
   uint64_t n_chunks = 0; // rank-build chunks
-  uint64_t* d_super = nullptr;
+  DevBuf<uint64_t> d_super;
   // grp_set_occupancy_hint: the phase-2 tables allocated by a helper thread while the fill runs (grp_finalize joins it)
   struct Prealloc
   {
     double occupancy = 0.0;
     bool started = false;
     std::thread worker;
-    uint4* units = nullptr;
+    DevBuf<uint4> units;        // (written by the worker, read behind its join)
     uint64_t units_buckets = 0; // capacity in 128-byte units
-    ulonglong2* far = nullptr;
-    uint64_t far_cap = 0;       // slots (a power of two)
+    DevBuf<ulonglong2> far;     // slots: a power of two
   } pre;
   double finalize_times[6] = { 0, 0, 0, 0, 0, 0 };
   bool finalized = false;
   int n_cus = 0;
   std::mutex fill_mutex; // grp_bv_insert may be called from several host threads (the reference calls insertBV under `omp parallel`)
   // --ntcard pass (grp_ntcard.inc)
-  uint32_t* d_ntc = nullptr;
+  DevBuf<uint32_t> d_ntc;
   uint32_t ntc_sbits = 0;
-  uint2* d_ntc_chunks = nullptr;
-  uint64_t ntc_chunks_cap = 0;
-  uint32_t* d_ntc_extra = nullptr;
-  uint64_t ntc_extra_cap = 0;
+  DevBuf<uint2> d_ntc_chunks;
+  DevBuf<uint32_t> d_ntc_extra;
   // query scratch: two slots so that a second window can be in flight while the
   // host commits the first (grp_classify_reads_begin / _end)
   QuerySlot slot[2];
@@ -258,39 +250,34 @@ struct grp_ctx
     uint64_t tile_off = 0;
   } carry;
   const DevBatchView* view = nullptr; // set while grp_batch_classify enqueues its window
-  grp_tile_summary* h_tiles = nullptr; // pinned staging
-  uint64_t h_tiles_cap = 0;
-  grp_id_count* h_lists = nullptr; // pinned staging of the list prefix
+  HostBuf<grp_tile_summary> h_tiles; // pinned staging
+  HostBuf<grp_id_count> h_lists; // pinned staging of the list prefix
   // small windows: kernel writes straight into mapped host memory
-  grp_tile_summary* h_small_tiles = nullptr;
-  grp_id_count* h_small_lists = nullptr;
-  grp_tile_summary* dmap_small_tiles = nullptr;
-  grp_id_count* dmap_small_lists = nullptr;
+  HostBuf<grp_tile_summary> h_small_tiles;
+  HostBuf<grp_id_count> h_small_lists;
   // insert scratch
-  unsigned long long* d_dedup = nullptr;
-  uint64_t dedup_cap = 0;
+  DevBuf<unsigned long long> d_dedup;
   uint32_t epoch = 0;
-  // whole-read insert table
-  unsigned long long* d_ir_keys = nullptr;
-  unsigned long long* d_ir_masks = nullptr;
-  unsigned long long* d_ir_locs = nullptr;
-  uint32_t* d_ir_slots = nullptr;
-  uint32_t* d_ir_counter = nullptr;
+  // whole-read insert table: one capacity (ir_cap slots) for the four tables and the two changed-slot sets
+  DevBuf<unsigned long long> d_ir_keys;
+  DevBuf<unsigned long long> d_ir_masks;
+  DevBuf<unsigned long long> d_ir_locs;
+  DevBuf<uint32_t> d_ir_slots;
+  DevBuf<uint32_t> d_ir_counter;
   uint32_t dbg_stream_lds = 0, dbg_stream_grid = 0; // developer (GRP_STREAM_DEBUG): the last streaming launch
-  uint32_t* d_fp_tab[2] = { nullptr, nullptr }; // changed-slot sets of a streaming window's last two in-launch inserts (ir_cap words each)
+  DevBuf<uint32_t> d_fp_tab[2]; // changed-slot sets of a streaming window's last two in-launch inserts (ir_cap words each)
   uint64_t ir_cap = 0;
   uint32_t ir_parity = 0;
   // RCCL communicator of a multi-GPU fill (grp_comm.inc), NULL on one GPU
   void* comm = nullptr;
   uint32_t comm_world = 1, comm_rank = 0;
   uint32_t n_comm_merges = 0; // grp_bv_merge_ranks calls that succeeded
-  double* d_delog = nullptr; // 10^(-Q/10) table for the FASTQ ingest
+  DevBuf<double> d_delog; // 10^(-Q/10) table for the FASTQ ingest
   // buffers of the FASTQ ingest, kept between chunks (round 4: a chunk used to pay seven hipMalloc / hipFree pairs,
   // 256 MiB of text among them — every hipFree waits for the device)
   struct IngestPool
   {
-    uint8_t* text[FQ_TEXT_SLOTS] = {}; // the chunk being packed, the next one (uploaded ahead) and the one after (uploading)
-    uint64_t text_cap[FQ_TEXT_SLOTS] = {};
+    DevBuf<uint8_t> text[FQ_TEXT_SLOTS]; // the chunk being packed, the next one (uploaded ahead) and the one after (uploading)
     bool text_used[FQ_TEXT_SLOTS] = {};
     int last_slot = FQ_TEXT_SLOTS - 1; // the slot handed out last (the next one takes the one after it)
     // grp_fastq_prefetch: bodies of coming chunks on their way into slots, oldest first
@@ -302,26 +289,16 @@ struct grp_ctx
     } pre[2];
     int n_pre = 0;
     uint64_t n_dropped = 0; // prefetched bodies that were not followed by their parse (uploaded for nothing)
-    uint32_t* d_counts = nullptr;
-    uint64_t counts_cap = 0;
-    uint64_t *d_base = nullptr, *d_super = nullptr, *d_total = nullptr, *d_nl = nullptr;
-    uint64_t base_cap = 0, super_cap = 0, total_cap = 0, nl_cap = 0;
-    void* d_rec = nullptr; // grp_fastq_record[]
-    uint64_t rec_bytes = 0;
-    uint64_t *d_so = nullptr, *d_wo = nullptr; // grp_fastq_pack: sequence offsets, word offsets, lengths of the selection
-    uint32_t* d_len = nullptr;
-    uint64_t so_cap = 0, wo_cap = 0, len_cap = 0;
-    hipEvent_t uploaded = nullptr; // the chunk's text has arrived (copied on the side stream, beside the fill of the chunk before)
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint64_t> d_base, d_super, d_total, d_nl;
+    DevBuf<uint8_t> d_rec; // grp_fastq_record[], in bytes
+    Event uploaded; // the chunk's text has arrived (copied on the side stream, beside the fill of the chunk before)
     // page-locked, device-mapped staging of a parse (grp_ingest.inc: ingest_stage): [0] newlines, [1] end of the last record
-    uint64_t* h_scal = nullptr;
-    uint64_t* dm_scal = nullptr;
-    uint8_t* h_front = nullptr; // the bytes in front of a prefetched body
-    uint8_t* dm_front = nullptr;
-    uint8_t* h_rec = nullptr; // the record table
-    uint8_t* dm_rec = nullptr;
-    uint64_t h_rec_bytes = 0;
-    hipEvent_t text_up[FQ_TEXT_SLOTS] = {};   // the slot's prefetched body has arrived (recorded on the copy stream)
-    hipEvent_t text_done[FQ_TEXT_SLOTS] = {}; // the main stream's last use of the slot's text (grp_fastq_free records it: the next upload into the slot waits for it, not the host)
+    HostBuf<uint64_t> h_scal;
+    HostBuf<uint8_t> h_front; // the bytes in front of a prefetched body
+    HostBuf<uint8_t> h_rec; // the record table
+    Event text_up[FQ_TEXT_SLOTS];   // the slot's prefetched body has arrived (recorded on the copy stream)
+    Event text_done[FQ_TEXT_SLOTS]; // the main stream's last use of the slot's text (grp_fastq_free records it: the next upload into the slot waits for it, not the host)
   } ingest;
   const char* reg_text = nullptr; // the caller's text buffer, page-locked by grp_fastq_pin
   size_t reg_bytes = 0;
@@ -339,20 +316,21 @@ struct grp_reads
   grp_ctx* ctx = nullptr;
   uint32_t n_reads = 0;
   uint64_t n_words = 0;
-  bool owns_packed = false;
-  uint32_t* d_packed = nullptr;
-  uint64_t* d_word_off = nullptr;
-  uint32_t* d_len = nullptr;
-  uint64_t* d_tile0 = nullptr;
-  uint32_t* d_tile_read = nullptr;
-  uint64_t* d_chunk0 = nullptr;
-  uint32_t* d_chunk_read = nullptr;
+  // what the batch owns: empty where the memory is the caller's (grp_reads_wrap_device: the bases) or a part of
+  // d_slab (grp_fastq_pack: the index arrays); `dev` has the addresses either way
+  DevBuf<uint32_t> d_packed;
+  DevBuf<uint64_t> d_word_off;
+  DevBuf<uint32_t> d_len;
+  DevBuf<uint64_t> d_tile0;
+  DevBuf<uint32_t> d_tile_read;
+  DevBuf<uint64_t> d_chunk0;
+  DevBuf<uint32_t> d_chunk_read;
   std::vector<uint64_t> tile0;  // host copy
   std::vector<uint64_t> chunk0; // host copy
   std::vector<uint32_t> len;    // host copy
   // grp_fastq_pack (round 5): one device allocation behind all index arrays, filled by asynchronous copies out of these
   // vectors — they live as long as the batch, so no call has to wait for a copy
-  void* d_slab = nullptr;
+  DevBuf<uint8_t> d_slab;
   std::vector<uint64_t> h_word_off, h_seq_off;
   std::vector<uint32_t> h_tile_read, h_chunk_read;
   DevReads dev{};
@@ -427,7 +405,7 @@ namespace {
 struct Timer
 {
   grp_ctx* c;
-  EventPair ep{};
+  EventPair ep;
   bool on = false;
   hipStream_t st;
   Timer(grp_ctx* ctx, int kind, uint64_t units, hipStream_t on_stream = nullptr)
@@ -440,12 +418,10 @@ struct Timer
       return;
     }
     if (!c->free_events.empty()) {
-      ep = c->free_events.back();
+      ep = std::move(c->free_events.back());
       c->free_events.pop_back();
-    } else {
-      if (hipEventCreate(&ep.a) != hipSuccess || hipEventCreate(&ep.b) != hipSuccess) {
-        return;
-      }
+    } else if (ep.a.create(hipEventDefault) != hipSuccess || ep.b.create(hipEventDefault) != hipSuccess) {
+      return;
     }
     ep.kind = kind;
     on = true;
@@ -455,7 +431,7 @@ struct Timer
   {
     if (on) {
       (void)hipEventRecord(ep.b, st);
-      c->pending.push_back(ep);
+      c->pending.push_back(std::move(ep));
     }
   }
 };
@@ -468,14 +444,14 @@ drain_events(grp_ctx* c)
   std::vector<EventPair> keep;
   for (auto& ep : c->pending) {
     if (hipEventQuery(ep.b) != hipSuccess) {
-      keep.push_back(ep);
+      keep.push_back(std::move(ep));
       continue;
     }
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ep.a, ep.b) == hipSuccess) {
       c->kstat[ep.kind].ms += (double)ms;
     }
-    c->free_events.push_back(ep);
+    c->free_events.push_back(std::move(ep));
   }
   c->pending.swap(keep);
 }
@@ -633,26 +609,26 @@ int
 slot_dec_alloc(grp_ctx* c, QuerySlot& sl, uint64_t cap)
 {
   static_assert(2 * sizeof(grp_read_decision) == 8 * sizeof(uint64_t), "the counters take two decision entries");
-  (void)hipFree(sl.d_dec_raw);
-  sl.d_dec_raw = sl.d_dec = nullptr;
-  if (sl.h_dec_raw) {
-    (void)hipHostFree(sl.h_dec_raw);
-    sl.h_dec_raw = sl.h_dec = nullptr;
-  }
+  clear_all(sl.d_dec_raw, sl.h_dec_raw);
+  sl.d_dec = sl.h_dec = nullptr;
   sl.h_qctr = nullptr;
-  sl.dec_cap = 0;
-  HIP_TRY(c, hipMalloc(&sl.d_dec_raw, (cap + 2) * sizeof(grp_read_decision)));
-  HIP_TRY(c, hipHostMalloc(&sl.h_dec_raw, (cap + 2) * sizeof(grp_read_decision), hipHostMallocDefault));
+  HIP_TRY(c, sl.d_dec_raw.reset(cap + 2));
+  HIP_TRY(c, sl.h_dec_raw.reset(cap + 2, hipHostMallocDefault));
   memset(sl.h_dec_raw, 0, 2 * sizeof(grp_read_decision));
   sl.d_dec = sl.d_dec_raw + 2;
   sl.h_dec = sl.h_dec_raw + 2;
-  sl.h_qctr = reinterpret_cast<uint64_t*>(sl.h_dec_raw);
-  sl.dec_cap = cap;
+  sl.h_qctr = reinterpret_cast<uint64_t*>(sl.h_dec_raw.p);
   return GRP_OK;
 }
 
+// room for `want` elements (DevBuf::ensure), a failure reported through the context
 template<typename T>
-int ensure_dev(grp_ctx* c, T*& p, uint64_t& cap, uint64_t want);
+int
+ensure_dev(grp_ctx* c, DevBuf<T>& b, uint64_t want)
+{
+  HIP_TRY(c, b.ensure(want));
+  return GRP_OK;
+}
 
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024 - 512; // gfx950, less the kernels' static shared variables
 // The kernels that stage a fill chunk or one tile beside the seed tables (fill, ntCard, insert, batch records, overlap
@@ -749,9 +725,9 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
         grp_tile_summary* a_tiles = out_tiles;
         grp_id_count* a_lists = out_lists;
         uint64_t a_lcap = list_cap;
-        unsigned long long* a_ctr = reinterpret_cast<unsigned long long*>(c->q->d_qctr);
+        unsigned long long* a_ctr = reinterpret_cast<unsigned long long*>(c->q->d_qctr.p);
         uint32_t* a_flag = (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx;
-        uint32_t a_fcap = (uint32_t)c->q->d_flag_cap, a_ds = direct_stride, a_blk0 = blk0;
+        uint32_t a_fcap = (uint32_t)c->q->d_flag_idx.cap, a_ds = direct_stride, a_blk0 = blk0;
         DevStreamCtl a_sc = *stream_ctl;
         DevBatchView a_bv{};
         uint32_t* a_gtab = nullptr;
@@ -764,7 +740,7 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
         return set_err(c, GRP_ERR_BUSY, "cooperative launch of a resumable window refused: %s", hipGetErrorString(e));
       }
     }
-    kern<<<dim3((uint32_t)n_launch), dim3(THREADS), launch_lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, d_tile_idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr), (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx, (uint32_t)c->q->d_flag_cap, direct_stride, blk0, stream_ctl ? *stream_ctl : DevStreamCtl{}, (c->view && !plain) ? *c->view : DevBatchView{}, nullptr);
+    kern<<<dim3((uint32_t)n_launch), dim3(THREADS), launch_lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, d_tile_idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx, (uint32_t)c->q->d_flag_idx.cap, direct_stride, blk0, stream_ctl ? *stream_ctl : DevStreamCtl{}, (c->view && !plain) ? *c->view : DevBatchView{}, nullptr);
     return GRP_OK;
   };
   // The synchronous forms (large windows, the two queries of a batch): two frames per lane and pass
@@ -778,7 +754,7 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
       return set_err(c, GRP_ERR_STATE, "launch_query: a global count table in a streaming / zero-copy launch");
     }
     const uint64_t words = (uint64_t)g.hist_cap + g.hist_cap / 2u;
-    if (const int rc = ensure_dev(c, c->d_gtab, c->gtab_cap, words * GT_SLICE); rc != GRP_OK) {
+    if (const int rc = ensure_dev(c, c->d_gtab, words * GT_SLICE); rc != GRP_OK) {
       return rc;
     }
     const bool ver = c->view && !plain;
@@ -796,13 +772,13 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
         if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
           return rc;
         }
-        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr), flag_out, (uint32_t)c->q->d_flag_cap, 0u, b0, DevStreamCtl{}, v, c->d_gtab);
+        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), flag_out, (uint32_t)c->q->d_flag_idx.cap, 0u, b0, DevStreamCtl{}, v, c->d_gtab);
       } else {
         auto kern = k_query<HH, 1, QWT, false, false, true>;
         if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
           return rc;
         }
-        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr), flag_out, (uint32_t)c->q->d_flag_cap, 0u, b0, DevStreamCtl{}, DevBatchView{}, c->d_gtab);
+        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), flag_out, (uint32_t)c->q->d_flag_idx.cap, 0u, b0, DevStreamCtl{}, DevBatchView{}, c->d_gtab);
       }
     }
     return GRP_OK;
@@ -1095,45 +1071,41 @@ grp_create(const grp_params* p, grp_ctx** out)
     // highest priority the parse kernels of a chunk started exactly when the copy of the chunk after next ended)
     CREATE_TRY(hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, lo));
   }
-  CREATE_TRY(hipMalloc(&c->d_seeds, sizeof(DevSeeds)));
+  CREATE_TRY(c->d_seeds.reset(1));
   CREATE_TRY(hipMemcpyAsync(c->d_seeds, &c->h_seeds, sizeof(DevSeeds), hipMemcpyHostToDevice, c->stream));
   if (p->m != 0) {
     c->f.m = p->m;
     c->f.m_inv = ~0ULL / p->m;
     // phase 1: plain bit vector (+3 zero pad words for the bucket builder)
     c->n_bv_words = (p->m + 31) / 32;
-    CREATE_TRY(hipMalloc(&c->f.bv, (c->n_bv_words + 3) * sizeof(uint32_t)));
+    CREATE_TRY(c->bv.reset(c->n_bv_words + 3));
+    c->f.bv = c->bv;
     CREATE_TRY(hipMemsetAsync(c->f.bv, 0, (c->n_bv_words + 3) * sizeof(uint32_t), c->stream));
   }
   for (QuerySlot& sl : c->slot) {
-    CREATE_TRY(hipMalloc(&sl.d_qctr, 8 * sizeof(uint64_t)));
+    CREATE_TRY(sl.d_qctr.reset(8));
     if (const int arc = slot_dec_alloc(c, sl, 1024); arc != GRP_OK) {
       return fail(arc);
     }
     CREATE_TRY(hipMemsetAsync(sl.d_qctr, 0, 8 * sizeof(uint64_t), c->stream));
-    CREATE_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&sl.qdone, hipEventDisableTiming));
-    CREATE_TRY(hipMalloc(&sl.d_abort, 256)); // [0] abort flag, [32] tile dispenser (its own 128-byte line), [48] park
+    CREATE_TRY(sl.done.create(hipEventDisableTiming));
+    CREATE_TRY(sl.qdone.create(hipEventDisableTiming));
+    CREATE_TRY(sl.d_abort.reset(64)); // (256 bytes) [0] abort flag, [32] tile dispenser (its own 128-byte line), [48] park
     CREATE_TRY(hipMemsetAsync(sl.d_abort, 0, 256, c->stream));
-    CREATE_TRY(hipHostMalloc(&sl.h_abort, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.dmap_abort), sl.h_abort, 0));
+    CREATE_TRY(sl.h_abort.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
     *sl.h_abort = 0;
-    CREATE_TRY(hipMalloc(&sl.d_sctl, SCT_WORDS * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc(&sl.d_rel, (size_t)STREAM_REL_WGS * 32u * sizeof(uint32_t)));
-    CREATE_TRY(hipHostMalloc(&sl.h_cmd, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.dmap_cmd), sl.h_cmd, 0));
-    CREATE_TRY(hipHostMalloc(&sl.h_ack, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.dmap_ack), sl.h_ack, 0));
+    CREATE_TRY(sl.d_sctl.reset(SCT_WORDS));
+    CREATE_TRY(sl.d_rel.reset((uint64_t)STREAM_REL_WGS * 32u));
+    CREATE_TRY(sl.h_cmd.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
+    CREATE_TRY(sl.h_ack.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
     memset(sl.h_cmd, 0, 64);
     memset(sl.h_ack, 0, 64);
-    CREATE_TRY(hipMalloc(&sl.d_executed, 8 * sizeof(unsigned long long)));
-    CREATE_TRY(hipHostMalloc(&sl.h_executed, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+    CREATE_TRY(sl.d_executed.reset(8));
+    CREATE_TRY(sl.h_executed.reset(8, hipHostMallocDefault));
   }
-  CREATE_TRY(hipHostMalloc(&c->h_lists, LIST_PREFIX * sizeof(grp_id_count), hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&c->h_small_tiles, SMALL_TILES * sizeof(grp_tile_summary), hipHostMallocMapped | hipHostMallocCoherent));
-  CREATE_TRY(hipHostMalloc(&c->h_small_lists, (size_t)SMALL_TILES * SMALL_STRIDE * sizeof(grp_id_count), hipHostMallocMapped | hipHostMallocCoherent));
-  CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dmap_small_tiles), c->h_small_tiles, 0));
-  CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dmap_small_lists), c->h_small_lists, 0));
+  CREATE_TRY(c->h_lists.reset(LIST_PREFIX, hipHostMallocDefault));
+  CREATE_TRY(c->h_small_tiles.reset(SMALL_TILES, hipHostMallocMapped | hipHostMallocCoherent));
+  CREATE_TRY(c->h_small_lists.reset((uint64_t)SMALL_TILES * SMALL_STRIDE, hipHostMallocMapped | hipHostMallocCoherent));
   CREATE_TRY(hipStreamSynchronize(c->stream));
 #undef CREATE_TRY
   *out = c;
@@ -1162,175 +1134,12 @@ grp_destroy(grp_ctx* c)
   if (c->pre.worker.joinable()) {
     c->pre.worker.join();
   }
-  (void)hipFree(c->pre.units);
-  (void)hipFree(c->pre.far);
   comm_release(c);
   if (c->reg_text) {
     (void)hipHostUnregister(const_cast<char*>(c->reg_text));
   }
   drain_events(c);
-  for (auto& ep : c->free_events) {
-    (void)hipEventDestroy(ep.a);
-    (void)hipEventDestroy(ep.b);
-  }
-  for (QuerySlot& sl : c->slot) {
-    (void)hipFree(sl.d_tiles);
-    (void)hipFree(sl.d_lists);
-    (void)hipFree(sl.d_qctr);
-    (void)hipFree(sl.d_flag_idx);
-    (void)hipFree(sl.d_dec_ids);
-    (void)hipFree(sl.d_dec_asg);
-    (void)hipFree(sl.d_dec_scratch);
-    (void)hipFree(sl.d_long_reads);
-    (void)hipFree(sl.d_dec_raw);
-    if (sl.h_dec_raw) {
-      (void)hipHostFree(sl.h_dec_raw);
-    }
-    if (sl.done) {
-      (void)hipEventDestroy(sl.done);
-    }
-    if (sl.qdone) {
-      (void)hipEventDestroy(sl.qdone);
-    }
-    if (sl.h_sdec) {
-      (void)hipHostFree(sl.h_sdec);
-    }
-    if (sl.h_abort) {
-      (void)hipHostFree(sl.h_abort);
-    }
-    if (sl.h_stripe_tiles) {
-      (void)hipHostFree(sl.h_stripe_tiles);
-    }
-    (void)hipFree(sl.d_stripe_tiles);
-    (void)hipFree(sl.d_abort);
-    if (sl.h_executed) {
-      (void)hipHostFree(sl.h_executed);
-    }
-    (void)hipFree(sl.d_tiles_done);
-    (void)hipFree(sl.d_executed);
-    (void)hipFree(sl.d_sctl);
-    (void)hipFree(sl.d_tile_ver);
-    (void)hipFree(sl.d_dbg);
-    (void)hipFree(sl.d_rel);
-    if (sl.h_cmd) {
-      (void)hipHostFree(sl.h_cmd);
-    }
-    if (sl.h_ack) {
-      (void)hipHostFree(sl.h_ack);
-    }
-  }
-  {
-    BatchRun& b = c->batch;
-    (void)hipFree(b.d_counters);
-    (void)hipFree(b.d_ins);
-    (void)hipFree(b.d_rec_key);
-    (void)hipFree(b.d_rec_loc);
-    (void)hipFree(b.d_rec_old);
-    (void)hipFree(b.d_rec_chain);
-    (void)hipFree(b.d_ovf_next);
-    (void)hipFree(b.d_ovf_jb);
-    (void)hipFree(b.d_chained);
-    (void)hipFree(b.d_log_keys);
-    (void)hipFree(b.d_log_head);
-    (void)hipFree(b.d_log_bits);
-    (void)hipFree(b.d_log_old);
-    (void)hipFree(b.d_log_writer);
-    (void)hipFree(b.d_log_next);
-    (void)hipFree(b.d_log_slot);
-    (void)hipFree(b.d_floor);
-    (void)hipFree(b.d_vf_stage);
-    if (b.h_vf_stage) {
-      (void)hipHostFree(b.h_vf_stage);
-    }
-    if (b.h_counters) {
-      (void)hipHostFree(b.h_counters);
-    }
-    if (b.h_ins_stage) {
-      (void)hipHostFree(b.h_ins_stage);
-    }
-  }
-  (void)hipFree(c->d_ntc);
-  (void)hipFree(c->d_ntc_chunks);
-  (void)hipFree(c->d_ntc_extra);
-  (void)hipFree(c->d_seeds);
-  (void)hipFree(c->d_gtab);
-  (void)hipFree(c->f.bv);
-  (void)hipFree(c->f.buckets);
-  (void)hipFree(c->d_super);
-  (void)hipFree(c->f.far);
-  (void)hipFree(c->f.ovf_keys);
-  (void)hipFree(c->f.ovf_ids);
-  if (c->h_tiles) {
-    (void)hipHostFree(c->h_tiles);
-  }
-  if (c->h_lists) {
-    (void)hipHostFree(c->h_lists);
-  }
-  if (c->h_small_tiles) {
-    (void)hipHostFree(c->h_small_tiles);
-  }
-  if (c->h_small_lists) {
-    (void)hipHostFree(c->h_small_lists);
-  }
-  (void)hipFree(c->d_delog);
-  (void)hipFree(c->ovl.d_samples);
-  (void)hipFree(c->ovl.d_n);
-  (void)hipFree(c->ovl.d_tab);
-  (void)hipFree(c->ovl.d_prev);
-  for (int i = 0; i < FQ_TEXT_SLOTS; ++i) {
-    (void)hipFree(c->ingest.text[i]);
-  }
-  (void)hipFree(c->ingest.d_counts);
-  (void)hipFree(c->ingest.d_base);
-  (void)hipFree(c->ingest.d_super);
-  (void)hipFree(c->ingest.d_total);
-  (void)hipFree(c->ingest.d_nl);
-  (void)hipFree(c->ingest.d_rec);
-  (void)hipFree(c->ingest.d_so);
-  (void)hipFree(c->ingest.d_wo);
-  (void)hipFree(c->ingest.d_len);
-  for (hipEvent_t& e : c->ingest.text_done) {
-    if (e) {
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
-  if (c->ingest.h_scal) {
-    (void)hipHostFree(c->ingest.h_scal);
-  }
-  if (c->ingest.h_front) {
-    (void)hipHostFree(c->ingest.h_front);
-  }
-  if (c->ingest.h_rec) {
-    (void)hipHostFree(c->ingest.h_rec);
-  }
-  for (hipEvent_t& e : c->ingest.text_up) {
-    if (e) {
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
-  if (c->ingest.uploaded) {
-    (void)hipEventDestroy(c->ingest.uploaded);
-  }
-  (void)hipFree(c->d_dedup);
-  (void)hipFree(c->d_ir_keys);
-  (void)hipFree(c->d_ir_masks);
-  (void)hipFree(c->d_ir_locs);
-  (void)hipFree(c->d_ir_slots);
-  (void)hipFree(c->d_ir_counter);
-  (void)hipFree(c->d_fp_tab[0]);
-  (void)hipFree(c->d_fp_tab[1]);
-  if (c->stream3) {
-    (void)hipStreamDestroy(c->stream3);
-  }
-  if (c->stream2) {
-    (void)hipStreamDestroy(c->stream2);
-  }
-  if (c->stream) {
-    (void)hipStreamDestroy(c->stream);
-  }
-  delete c;
+  delete c; // (the members free themselves, the streams go behind them: CtxStreams)
 }
 
 // ---- reads -------------------------------------------------------------------------
@@ -1373,19 +1182,18 @@ reads_build(grp_ctx* c, grp_reads* r, const uint64_t* word_off, const uint32_t* 
       chunk_read[j] = i;
     }
   }
-  HIP_TRY(c, hipMalloc(&r->d_word_off, ((size_t)n + 1) * 8));
-  HIP_TRY(c, hipMalloc(&r->d_len, std::max<size_t>(n, 1) * 4));
-  HIP_TRY(c, hipMalloc(&r->d_tile0, ((size_t)n + 1) * 8));
-  HIP_TRY(c, hipMalloc(&r->d_chunk0, ((size_t)n + 1) * 8));
-  HIP_TRY(c, hipMalloc(&r->d_tile_read, std::max<size_t>(t, 1) * 4));
-  HIP_TRY(c, hipMalloc(&r->d_chunk_read, std::max<size_t>(ch, 1) * 4));
+  HIP_TRY(c, r->d_word_off.reset((uint64_t)n + 1));
+  HIP_TRY(c, r->d_len.reset(std::max<uint64_t>(n, 1)));
+  HIP_TRY(c, r->d_tile0.reset((uint64_t)n + 1));
+  HIP_TRY(c, r->d_chunk0.reset((uint64_t)n + 1));
+  HIP_TRY(c, r->d_tile_read.reset(std::max<uint64_t>(t, 1)));
+  HIP_TRY(c, r->d_chunk_read.reset(std::max<uint64_t>(ch, 1)));
   HIP_TRY(c, hipMemcpy(r->d_word_off, word_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(r->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(r->d_tile0, r->tile0.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(r->d_chunk0, r->chunk0.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(r->d_tile_read, tile_read.data(), t * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(r->d_chunk_read, chunk_read.data(), ch * 4, hipMemcpyHostToDevice));
-  r->dev.packed = r->d_packed;
   r->dev.word_off = r->d_word_off;
   r->dev.len = r->d_len;
   r->dev.tile0 = r->d_tile0;
@@ -1442,17 +1250,17 @@ grp_reads_upload(grp_ctx* c, const uint32_t* packed, const uint64_t* word_off, c
   }
   HIP_TRY(c, hipSetDevice(c->device));
   grp_reads* r = new grp_reads();
-  r->owns_packed = true;
-  hipError_t e = hipMalloc(&r->d_packed, std::max<uint64_t>(word_off[n], 1) * 4 + 16);
+  hipError_t e = r->d_packed.reset(std::max<uint64_t>(word_off[n], 1) + 4);
   if (e != hipSuccess) {
     delete r;
-    return set_err(c, GRP_ERR_NOMEM, "hipMalloc(%llu words) failed: %s", (unsigned long long)word_off[n], hipGetErrorString(e));
+    return set_err(c, GRP_ERR_NOMEM, "allocating %llu words of device memory failed: %s", (unsigned long long)word_off[n], hipGetErrorString(e));
   }
   e = hipMemcpy(r->d_packed, packed, word_off[n] * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     grp_reads_free(r);
     return set_err(c, GRP_ERR_HIP, "hipMemcpy(packed) failed: %s", hipGetErrorString(e));
   }
+  r->dev.packed = r->d_packed;
   int rc = reads_build(c, r, word_off, len, n);
   if (rc != GRP_OK) {
     grp_reads_free(r);
@@ -1470,8 +1278,7 @@ grp_reads_wrap_device(grp_ctx* c, const void* d_packed, const uint64_t* word_off
   }
   HIP_TRY(c, hipSetDevice(c->device));
   grp_reads* r = new grp_reads();
-  r->owns_packed = false;
-  r->d_packed = const_cast<uint32_t*>(static_cast<const uint32_t*>(d_packed));
+  r->dev.packed = static_cast<const uint32_t*>(d_packed); // borrowed: r->d_packed stays empty
   int rc = reads_build(c, r, word_off, len, n);
   if (rc != GRP_OK) {
     grp_reads_free(r);
@@ -1502,20 +1309,6 @@ grp_reads_free(grp_reads* r)
       }
     }
   }
-  if (r->owns_packed) {
-    (void)hipFree(r->d_packed);
-  }
-  if (r->d_slab) { // the index arrays are parts of one allocation
-    (void)hipFree(r->d_slab);
-    delete r;
-    return;
-  }
-  (void)hipFree(r->d_word_off);
-  (void)hipFree(r->d_len);
-  (void)hipFree(r->d_tile0);
-  (void)hipFree(r->d_tile_read);
-  (void)hipFree(r->d_chunk0);
-  (void)hipFree(r->d_chunk_read);
   delete r;
 }
 
@@ -1579,20 +1372,18 @@ prealloc_start(grp_ctx* c)
     if ((uint64_t)free_b < need + 2 * bv_bytes + (16ull << 30)) {
       return;
     }
-    uint4* u = nullptr;
-    if (hipMalloc(&u, nb * (uint64_t)GRP_UNIT_U4 * 16) != hipSuccess) {
+    DevBuf<uint4> u;
+    if (u.reset(nb * (uint64_t)GRP_UNIT_U4) != hipSuccess) {
       (void)hipGetLastError();
       return; // grp_finalize allocates what it needs (and reports the failure if there is one)
     }
-    ulonglong2* f = nullptr;
-    if (hipMalloc(&f, fc * sizeof(ulonglong2)) != hipSuccess) {
+    DevBuf<ulonglong2> f;
+    if (f.reset(fc) != hipSuccess) {
       (void)hipGetLastError();
-      f = nullptr;
     }
-    p->units = u;
+    p->units = std::move(u);
     p->units_buckets = nb;
-    p->far = f;
-    p->far_cap = f ? fc : 0;
+    p->far = std::move(f);
   });
 }
 
@@ -1630,7 +1421,8 @@ grp_set_filter_size(grp_ctx* c, uint64_t m)
   }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint64_t words = (m + 31) / 32;
-  HIP_TRY(c, hipMalloc(&c->f.bv, (words + 3) * sizeof(uint32_t)));
+  HIP_TRY(c, c->bv.reset(words + 3));
+  c->f.bv = c->bv;
   HIP_TRY(c, hipMemsetAsync(c->f.bv, 0, (words + 3) * sizeof(uint32_t), c->stream));
   c->params.m = m;
   c->f.m = m;
@@ -1782,8 +1574,8 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   for (double& v : c->finalize_times) {
     v = 0.0;
   }
-  unsigned long long* d_scalars = nullptr; // [0] pop (popcount), [1] pop (scan), [2] overflow entries (IDs), [3] far entries (count words)
-  HIP_TRY(c, hipMalloc(&d_scalars, 4 * sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d_scalars; // [0] pop (popcount), [1] pop (scan), [2] overflow entries (IDs), [3] far entries (count words)
+  HIP_TRY(c, d_scalars.reset(4));
   HIP_TRY(c, hipMemsetAsync(d_scalars, 0, 4 * sizeof(unsigned long long), c->stream));
   Timer* t = new Timer(c, GRP_K_RANK, c->n_bv_words);
   k_popcount<<<dim3(4096), dim3(THREADS), 0, c->stream>>>(c->f.bv, c->n_bv_words, d_scalars);
@@ -1820,8 +1612,8 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
     delete t;
     return set_err(c, GRP_ERR_INVALID, "filter of %llu buckets exceeds the rank builder's launch size", (unsigned long long)c->f.n_buckets);
   }
-  uint32_t* d_chunk_sum = nullptr;
-  uint64_t* d_chunk_base = nullptr;
+  DevBuf<uint32_t> d_chunk_sum;
+  DevBuf<uint64_t> d_chunk_base;
   // a bucket is a 128-byte unit since round 5: its query line {rel, bitmap, 13 IDs} and its insert line (8 count words);
   // the count words of the ranks beyond a bucket's 8th set bit come on top (the far table below, ~5 % of the ranks x 32 B)
   const uint64_t unit_bytes = (uint64_t)GRP_UNIT_U4 * 16;
@@ -1833,29 +1625,26 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   }
   bool used_prepared = false;
   if (c->pre.units && c->pre.units_buckets >= c->f.n_buckets) {
-    c->f.buckets = c->pre.units;
-    c->pre.units = nullptr;
+    c->buckets = std::move(c->pre.units);
     used_prepared = true;
   } else {
-    if (c->pre.units) { // prepared for another geometry (the occupancy came out far above the hint): released first
-      (void)hipFree(c->pre.units);
-      c->pre.units = nullptr;
-    }
-    const hipError_t e = hipMalloc(&c->f.buckets, c->f.n_buckets * unit_bytes);
+    c->pre.units.clear(); // prepared for another geometry (the occupancy came out far above the hint): released first
+    const hipError_t e = c->buckets.reset(c->f.n_buckets * GRP_UNIT_U4);
     if (e != hipSuccess) {
       delete t;
       return set_err(c, GRP_ERR_NOMEM, "hipMalloc of %llu bucket units (%.1f GB: 128 B per %u filter bits, IDs and insert counts included) failed: %s", (unsigned long long)c->f.n_buckets, c->f.n_buckets * unit_bytes / 1e9, W,
                      hipGetErrorString(e));
     }
   }
-  HIP_TRY(c, hipMalloc(&c->d_super, c->nsb * sizeof(uint64_t)));
+  c->f.buckets = c->buckets;
+  HIP_TRY(c, c->d_super.reset(c->nsb));
   c->f.super = c->d_super;
-  HIP_TRY(c, hipMalloc(&d_chunk_sum, c->n_chunks * 4));
-  HIP_TRY(c, hipMalloc(&d_chunk_base, c->n_chunks * 8));
+  HIP_TRY(c, d_chunk_sum.reset(c->n_chunks));
+  HIP_TRY(c, d_chunk_base.reset(c->n_chunks));
   const auto t_alloc = now();
   c->finalize_times[1] = secs(t_pop, t_alloc);
   k_bucket_chunk_sums<<<dim3((uint32_t)c->n_chunks), dim3(THREADS), 0, c->stream>>>(c->f.bv, c->f.m, W, c->f.n_buckets, d_chunk_sum);
-  k_scan_chunks<<<dim3(1), dim3(1024), 0, c->stream>>>(d_chunk_sum, c->n_chunks, d_chunk_base, c->d_super, reinterpret_cast<uint64_t*>(d_scalars + 1));
+  k_scan_chunks<<<dim3(1), dim3(1024), 0, c->stream>>>(d_chunk_sum, c->n_chunks, d_chunk_base, c->d_super, reinterpret_cast<uint64_t*>(d_scalars.p + 1));
   k_bucket_write<<<dim3((uint32_t)c->n_chunks), dim3(THREADS), 0, c->stream>>>(c->f.bv, c->f.m, W, c->f.n_buckets, c->f.buckets, d_chunk_base, c->d_super, d_scalars + 2);
   delete t;
   HIP_TRY(c, hipGetLastError());
@@ -1870,11 +1659,9 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
     // behind the caller's back, but hipFree synchronises with EVERY later launch too: a parked streaming window that waits
     // for the host while the host's next HIP call waits for the free is a deadlock this engine has met before)
     const auto t_free = now();
-    (void)hipFree(c->f.bv);
+    c->bv.clear();
     c->f.bv = nullptr;
-    (void)hipFree(d_chunk_sum);
-    (void)hipFree(d_chunk_base);
-    (void)hipFree(d_scalars);
+    clear_all(d_chunk_sum, d_chunk_base, d_scalars);
     c->finalize_times[5] = secs(t_free, now());
   }
   c->f.pop = h_pop;
@@ -1883,23 +1670,19 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   {
     // the count words beyond a bucket's 8th set bit: {rank + 1, word}, open addressing at load <= 1/2, keys written now
     const uint64_t far_cap = next_pow2_64(std::max<uint64_t>(2 * h_scalars[3], 1024));
-    if (c->pre.far && c->pre.far_cap >= far_cap) {
+    if (c->pre.far.cap >= far_cap) {
       // (a prepared table larger than needed keeps its size: the load only drops)
-      c->f.far = c->pre.far;
-      c->f.far_mask = c->pre.far_cap - 1;
-      c->pre.far = nullptr;
+      c->far = std::move(c->pre.far);
     } else {
       used_prepared = false;
-      if (c->pre.far) {
-        (void)hipFree(c->pre.far);
-        c->pre.far = nullptr;
-      }
-      const hipError_t e = hipMalloc(&c->f.far, far_cap * sizeof(ulonglong2));
+      c->pre.far.clear();
+      const hipError_t e = c->far.reset(far_cap);
       if (e != hipSuccess) {
         return set_err(c, GRP_ERR_NOMEM, "hipMalloc of the far count table (%llu ranks beyond their bucket's 8th set bit, %.1f GB) failed: %s", h_scalars[3], far_cap * sizeof(ulonglong2) / 1e9, hipGetErrorString(e));
       }
-      c->f.far_mask = far_cap - 1;
     }
+    c->f.far = c->far;
+    c->f.far_mask = c->far.cap - 1;
     HIP_TRY(c, hipMemsetAsync(c->f.far, 0, (c->f.far_mask + 1) * sizeof(ulonglong2), c->stream));
     c->n_far = h_scalars[3];
     if (h_scalars[3]) {
@@ -1908,8 +1691,10 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
     }
   }
   const uint64_t ovf_cap = next_pow2_64(std::max<uint64_t>(2 * h_scalars[2], 1024));
-  HIP_TRY(c, hipMalloc(&c->f.ovf_keys, ovf_cap * sizeof(unsigned long long)));
-  HIP_TRY(c, hipMalloc(&c->f.ovf_ids, ovf_cap * sizeof(uint32_t)));
+  HIP_TRY(c, c->ovf_keys.reset(ovf_cap));
+  HIP_TRY(c, c->ovf_ids.reset(ovf_cap));
+  c->f.ovf_keys = c->ovf_keys;
+  c->f.ovf_ids = c->ovf_ids;
   HIP_TRY(c, hipMemsetAsync(c->f.ovf_keys, 0, ovf_cap * sizeof(unsigned long long), c->stream));
   HIP_TRY(c, hipMemsetAsync(c->f.ovf_ids, 0, ovf_cap * sizeof(uint32_t), c->stream));
   c->f.ovf_mask = ovf_cap - 1;
@@ -1937,17 +1722,28 @@ struct QueryRun
   uint64_t flagged = 0; // tiles redone with the worst-case geometry
 };
 
-template<typename T>
+// a slot's tile summaries, list arena and flagged-tile indices for a window of `nt` tiles
 int
-ensure_dev(grp_ctx* c, T*& p, uint64_t& cap, uint64_t want)
+slot_query_bufs(grp_ctx* c, QuerySlot& sl, uint64_t nt, uint64_t lists)
 {
-  if (want > cap) {
-    (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const uint64_t n = want + want / 4 + 64;
-    HIP_TRY(c, hipMalloc(&p, n * sizeof(T)));
-    cap = n;
+  HIP_TRY(c, sl.d_tiles.ensure(nt));
+  HIP_TRY(c, sl.d_lists.ensure(lists));
+  HIP_TRY(c, sl.d_flag_idx.ensure(nt));
+  return GRP_OK;
+}
+
+// a slot's decide scratch for a window of `nt` tiles: three arrays of one capacity
+int
+slot_dec_scratch(grp_ctx* c, QuerySlot& sl, uint64_t nt)
+{
+  if (nt + 1 > sl.d_dec_cap) {
+    clear_all(sl.d_dec_ids, sl.d_dec_asg, sl.d_dec_scratch);
+    sl.d_dec_cap = 0;
+    const uint64_t cap = nt + nt / 4 + 64;
+    HIP_TRY(c, sl.d_dec_ids.reset(cap));
+    HIP_TRY(c, sl.d_dec_asg.reset(cap));
+    HIP_TRY(c, sl.d_dec_scratch.reset(cap));
+    sl.d_dec_cap = cap;
   }
   return GRP_OK;
 }
@@ -1975,14 +1771,7 @@ enqueue_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, ui
   q.t0 = r->tile0[first];
   q.nt = r->tile0[first + count] - q.t0;
   q.probes = count_probes(c, r, first, count);
-  int rc = ensure_dev(c, c->q->d_tiles, c->q->d_tiles_cap, q.nt);
-  if (rc == GRP_OK) {
-    rc = ensure_dev(c, c->q->d_lists, c->q->d_lists_cap, std::max<uint64_t>(list_cap, 1));
-  }
-  if (rc == GRP_OK) {
-    rc = ensure_dev(c, c->q->d_flag_idx, c->q->d_flag_cap, q.nt);
-  }
-  if (rc != GRP_OK) {
+  if (const int rc = slot_query_bufs(c, *c->q, q.nt, std::max<uint64_t>(list_cap, 1)); rc != GRP_OK) {
     return rc;
   }
   if (c->q->side_used) {
@@ -2086,7 +1875,7 @@ grp_query_tiles(grp_ctx* c,
     {
       const QueryGeom g = query_geom(c, false);
       Timer t(c, GRP_K_QUERY_LAT, probes);
-      int lrc = launch_query(c, r, nt, t0, nullptr, g, (uint64_t)SMALL_TILES * SMALL_STRIDE, c->dmap_small_tiles, c->dmap_small_lists, SMALL_STRIDE);
+      int lrc = launch_query(c, r, nt, t0, nullptr, g, (uint64_t)SMALL_TILES * SMALL_STRIDE, c->h_small_tiles.dev, c->h_small_lists.dev, SMALL_STRIDE);
       if (lrc != GRP_OK) {
         return lrc;
       }
@@ -2157,15 +1946,8 @@ grp_query_tiles(grp_ctx* c,
     // a tile needs the worst-case table or a longer list: take the general path
     ++c->n_direct_fallbacks;
   }
-  if (nt > c->h_tiles_cap) {
-    if (c->h_tiles) {
-      (void)hipHostFree(c->h_tiles);
-      c->h_tiles = nullptr;
-      c->h_tiles_cap = 0;
-    }
-    const uint64_t cap = std::max<uint64_t>(nt + nt / 4, 4096);
-    HIP_TRY(c, hipHostMalloc(&c->h_tiles, cap * sizeof(grp_tile_summary), hipHostMallocDefault));
-    c->h_tiles_cap = cap;
+  if (nt > c->h_tiles.cap) {
+    HIP_TRY(c, c->h_tiles.reset(std::max<uint64_t>(nt + nt / 4, 4096), hipHostMallocDefault));
   }
   ++c->n_general_windows;
   QueryRun q;
@@ -2260,7 +2042,7 @@ classify_enqueue_decide(grp_ctx* c, QuerySlot& sl, hipStream_t st)
     }
   }
   k_decide<<<dim3(sl.count), dim3(DECIDE_THREADS), 0, st>>>(sl.reads->dev, sl.first, sl.count, sl.dp, sl.d_tiles, sl.d_lists, sl.list_cap, sl.d_dec_ids, sl.d_dec_asg, sl.d_dec_scratch, sl.d_dec, 0u, nullptr,
-                                                            longs.empty() ? 0u : 4u * LANE_TILES, reinterpret_cast<unsigned long long*>(sl.d_qctr), reinterpret_cast<unsigned long long*>(sl.d_dec_raw));
+                                                            longs.empty() ? 0u : 4u * LANE_TILES, reinterpret_cast<unsigned long long*>(sl.d_qctr.p), reinterpret_cast<unsigned long long*>(sl.d_dec_raw.p));
   HIP_TRY(c, hipGetLastError());
   if (!longs.empty()) {
     const uint32_t lds_tiles = (uint32_t)std::min<uint64_t>((most + 63) / 64 * 64, DECIDE_LDS_MAX_TILES);
@@ -2268,7 +2050,7 @@ classify_enqueue_decide(grp_ctx* c, QuerySlot& sl, hipStream_t st)
     if (const int rc = ensure_lds(c, k_decide, lds); rc != GRP_OK) {
       return rc;
     }
-    if (const int rc = ensure_dev(c, sl.d_long_reads, sl.long_reads_cap, longs.size()); rc != GRP_OK) {
+    if (const int rc = ensure_dev(c, sl.d_long_reads, longs.size()); rc != GRP_OK) {
       return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(sl.d_long_reads, longs.data(), longs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st)); // (pageable: staged before the call returns)
@@ -2359,26 +2141,15 @@ classify_setup(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, c
   }
   c->q = &sl;
   // decision buffers + scratch for reads too long for the LDS path
-  if (count > sl.dec_cap) {
+  if ((uint64_t)count + 2 > sl.h_dec_raw.cap) { // (the pinned half is allocated last: a pair that failed half-way grows again)
     if (const int rc = slot_dec_alloc(c, sl, std::max<uint64_t>((uint64_t)count + count / 4, 1024)); rc != GRP_OK) {
       return rc;
     }
   }
-  if (nt + 1 > sl.d_dec_cap) {
-    (void)hipFree(sl.d_dec_ids);
-    (void)hipFree(sl.d_dec_asg);
-    (void)hipFree(sl.d_dec_scratch);
-    sl.d_dec_ids = nullptr;
-    sl.d_dec_asg = nullptr;
-    sl.d_dec_scratch = nullptr;
-    sl.d_dec_cap = 0;
-    const uint64_t cap = nt + nt / 4 + 64;
-    HIP_TRY(c, hipMalloc(&sl.d_dec_ids, cap * 4));
-    HIP_TRY(c, hipMalloc(&sl.d_dec_asg, cap));
-    HIP_TRY(c, hipMalloc(&sl.d_dec_scratch, cap * 8));
-    sl.d_dec_cap = cap;
+  if (const int rc = slot_dec_scratch(c, sl, nt); rc != GRP_OK) {
+    return rc;
   }
-  sl.list_cap = std::max<uint64_t>(sl.d_lists_cap, 4 * nt + 4096);
+  sl.list_cap = std::max<uint64_t>(sl.d_lists.cap, 4 * nt + 4096);
   return GRP_OK;
 }
 
@@ -2494,26 +2265,18 @@ ensure_insert_table(grp_ctx* c, uint64_t max_ranks)
     return GRP_OK;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(c->d_ir_keys);
-  (void)hipFree(c->d_ir_masks);
-  (void)hipFree(c->d_ir_locs);
-  (void)hipFree(c->d_ir_slots);
-  (void)hipFree(c->d_fp_tab[0]);
-  (void)hipFree(c->d_fp_tab[1]);
-  c->d_ir_keys = c->d_ir_masks = c->d_ir_locs = nullptr;
-  c->d_ir_slots = nullptr;
-  c->d_fp_tab[0] = c->d_fp_tab[1] = nullptr;
+  clear_all(c->d_ir_keys, c->d_ir_masks, c->d_ir_locs, c->d_ir_slots, c->d_fp_tab[0], c->d_fp_tab[1]);
   c->ir_cap = 0;
-  HIP_TRY(c, hipMalloc(&c->d_fp_tab[0], want * 4));
-  HIP_TRY(c, hipMalloc(&c->d_fp_tab[1], want * 4));
-  HIP_TRY(c, hipMalloc(&c->d_ir_keys, want * 8));
-  HIP_TRY(c, hipMalloc(&c->d_ir_masks, want * 8));
-  HIP_TRY(c, hipMalloc(&c->d_ir_locs, want * 8));
-  HIP_TRY(c, hipMalloc(&c->d_ir_slots, want * 4));
+  HIP_TRY(c, c->d_fp_tab[0].reset(want));
+  HIP_TRY(c, c->d_fp_tab[1].reset(want));
+  HIP_TRY(c, c->d_ir_keys.reset(want));
+  HIP_TRY(c, c->d_ir_masks.reset(want));
+  HIP_TRY(c, c->d_ir_locs.reset(want));
+  HIP_TRY(c, c->d_ir_slots.reset(want));
   HIP_TRY(c, hipMemsetAsync(c->d_ir_keys, 0, want * 8, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_ir_masks, 0, want * 8, c->stream));
   if (!c->d_ir_counter) {
-    HIP_TRY(c, hipMalloc(&c->d_ir_counter, 2 * sizeof(uint32_t)));
+    HIP_TRY(c, c->d_ir_counter.reset(2));
     HIP_TRY(c, hipMemsetAsync(c->d_ir_counter, 0, 2 * sizeof(uint32_t), c->stream));
   }
   c->ir_cap = want;
@@ -2614,54 +2377,29 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
     // the current one still had an insert to take; the launch gave up after its idle limit).
     // Not now, then: the caller begins this window once the other one has ended.
     const QuerySlot& other = c->slot[slot ^ 1u];
-    const bool grows = count > sl.sdec_cap || std::max<uint64_t>(count, 1) > sl.tiles_done_cap || nt + 1 > sl.d_dec_cap || std::max<uint64_t>(nt, 1) > sl.d_tiles_cap ||
-                       std::max<uint64_t>(sl.d_lists_cap, (want_resumable ? 8 : 4) * nt + 4096) > sl.d_lists_cap || std::max<uint64_t>(nt, 1) > sl.d_flag_cap ||
-                       (want_resumable && std::max<uint64_t>(nt, 1) > sl.tile_ver_cap);
+    const bool grows = count > sl.h_sdec.cap || std::max<uint64_t>(count, 1) > sl.d_tiles_done.cap || nt + 1 > sl.d_dec_cap || std::max<uint64_t>(nt, 1) > sl.d_tiles.cap ||
+                       std::max<uint64_t>(sl.d_lists.cap, (want_resumable ? 8 : 4) * nt + 4096) > sl.d_lists.cap || std::max<uint64_t>(nt, 1) > sl.d_flag_idx.cap ||
+                       (want_resumable && std::max<uint64_t>(nt, 1) > sl.d_tile_ver.cap);
     if (grows && other.busy && other.streaming && other.resumable) {
       return set_err(c, GRP_ERR_BUSY, "grp_classify_stream_begin: the slot's buffers must grow while a resumable window is in flight in the other slot: begin this window when that one has ended");
     }
   }
   c->q = &sl;
-  if (count > sl.sdec_cap) {
-    if (sl.h_sdec) {
-      (void)hipHostFree(sl.h_sdec);
-      sl.h_sdec = nullptr;
-    }
-    sl.sdec_cap = 0;
-    const uint64_t cap = std::max<uint64_t>((uint64_t)count + count / 2, 1024);
-    HIP_TRY(c, hipHostMalloc(&sl.h_sdec, cap * sizeof(grp_read_decision), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.dmap_sdec), sl.h_sdec, 0));
-    sl.sdec_cap = cap;
+  if (count > sl.h_sdec.cap) {
+    HIP_TRY(c, sl.h_sdec.reset(std::max<uint64_t>((uint64_t)count + count / 2, 1024), hipHostMallocMapped | hipHostMallocCoherent));
   }
-  int rc = ensure_dev(c, sl.d_tiles_done, sl.tiles_done_cap, std::max<uint64_t>(count, 1));
+  int rc = ensure_dev(c, sl.d_tiles_done, std::max<uint64_t>(count, 1));
   if (rc != GRP_OK) {
     return rc;
   }
-  if (nt + 1 > sl.d_dec_cap) {
-    (void)hipFree(sl.d_dec_ids);
-    (void)hipFree(sl.d_dec_asg);
-    (void)hipFree(sl.d_dec_scratch);
-    sl.d_dec_ids = nullptr;
-    sl.d_dec_asg = nullptr;
-    sl.d_dec_scratch = nullptr;
-    sl.d_dec_cap = 0;
-    const uint64_t cap = nt + nt / 4 + 64;
-    HIP_TRY(c, hipMalloc(&sl.d_dec_ids, cap * 4));
-    HIP_TRY(c, hipMalloc(&sl.d_dec_asg, cap));
-    HIP_TRY(c, hipMalloc(&sl.d_dec_scratch, cap * 8));
-    sl.d_dec_cap = cap;
+  if (rc = slot_dec_scratch(c, sl, nt); rc != GRP_OK) {
+    return rc;
   }
   // (a window that keeps tiles across its inserts does not start its list arena over at each of them: twice the room)
-  sl.list_cap = std::max<uint64_t>(sl.d_lists_cap, (want_resumable ? 8 : 4) * nt + 4096);
-  rc = ensure_dev(c, sl.d_tiles, sl.d_tiles_cap, std::max<uint64_t>(nt, 1));
-  if (rc == GRP_OK) {
-    rc = ensure_dev(c, sl.d_lists, sl.d_lists_cap, sl.list_cap);
-  }
-  if (rc == GRP_OK) {
-    rc = ensure_dev(c, sl.d_flag_idx, sl.d_flag_cap, std::max<uint64_t>(nt, 1));
-  }
+  sl.list_cap = std::max<uint64_t>(sl.d_lists.cap, (want_resumable ? 8 : 4) * nt + 4096);
+  rc = slot_query_bufs(c, sl, std::max<uint64_t>(nt, 1), sl.list_cap);
   if (rc == GRP_OK && want_resumable) { // (round 6) what a window keeps across an in-launch insert: a mark per tile (DevStreamCtl::tile_ver)
-    rc = ensure_dev(c, sl.d_tile_ver, sl.tile_ver_cap, std::max<uint64_t>(nt, 1));
+    rc = ensure_dev(c, sl.d_tile_ver, std::max<uint64_t>(nt, 1));
   }
   if (rc != GRP_OK) {
     return rc;
@@ -2677,18 +2415,11 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
         n_mine += r->tile0[first + j + 1] - r->tile0[first + j];
       }
     }
-    if (n_mine > sl.stripe_tiles_cap) {
-      if (sl.h_stripe_tiles) {
-        (void)hipHostFree(sl.h_stripe_tiles);
-        sl.h_stripe_tiles = nullptr;
-      }
-      (void)hipFree(sl.d_stripe_tiles);
-      sl.d_stripe_tiles = nullptr;
-      sl.stripe_tiles_cap = 0;
+    if (n_mine > sl.d_stripe_tiles.cap) {
+      clear_all(sl.h_stripe_tiles, sl.d_stripe_tiles);
       const uint64_t cap = n_mine + n_mine / 4 + 1024;
-      HIP_TRY(c, hipHostMalloc(&sl.h_stripe_tiles, cap * sizeof(uint32_t), hipHostMallocDefault));
-      HIP_TRY(c, hipMalloc(&sl.d_stripe_tiles, cap * sizeof(uint32_t)));
-      sl.stripe_tiles_cap = cap;
+      HIP_TRY(c, sl.h_stripe_tiles.reset(cap, hipHostMallocDefault));
+      HIP_TRY(c, sl.d_stripe_tiles.reset(cap));
     }
     uint64_t w = 0;
     for (uint32_t j = 0; j < count; ++j) {
@@ -2737,7 +2468,7 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
   sl.stripe_reads = striped ? stripe_reads : 0;
   sl.n_owners = n_owners;
   sl.owner = owner;
-  __atomic_store_n(sl.h_abort, 0u, __ATOMIC_RELEASE);
+  __atomic_store_n(sl.h_abort.p, 0u, __ATOMIC_RELEASE);
   sl.reads = r;
   sl.first = first;
   sl.count = count;
@@ -2775,12 +2506,12 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
     sc.first = first;
     sc.tiles_done = sl.d_tiles_done;
     sc.abort = sl.d_abort;
-    sc.abort_host = sl.dmap_abort;
+    sc.abort_host = sl.h_abort.dev;
     sc.next_tile = sl.d_abort + 32;
     sc.park = sl.d_abort + 48;
     sc.early_park = c->env_no_early_park ? 0u : 1u; // GRP_NO_EARLY_PARK, developer hook (the engine-level API contract assumes 1)
     sc.n_tiles = (uint32_t)n_mine;
-    sc.dec = sl.dmap_sdec;
+    sc.dec = sl.h_sdec.dev;
     sc.executed = sl.d_executed;
     sc.dp = *dp;
     sc.g_ids = sl.d_dec_ids;
@@ -2791,13 +2522,13 @@ stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count
     if (sl.resumable) {
       sc.ctl = sl.d_sctl;
       sc.cmd_while_busy = striped ? 1u : 0u;
-      sc.cmd_host = sl.dmap_cmd;
-      sc.ack_host = sl.dmap_ack;
+      sc.cmd_host = sl.h_cmd.dev;
+      sc.ack_host = sl.h_ack.dev;
       sc.tb = InsertTable{ c->d_ir_keys, c->d_ir_masks, c->d_ir_locs, c->d_ir_slots, c->d_ir_counter, c->ir_cap - 1 };
       static const bool dbg_on = getenv("GRP_STREAM_DEBUG") != nullptr;
       if (dbg_on) {
         if (!sl.d_dbg) {
-          HIP_TRY(c, hipMalloc(&sl.d_dbg, 8192 * sizeof(uint32_t)));
+          HIP_TRY(c, sl.d_dbg.reset(8192));
         }
         HIP_TRY(c, hipMemsetAsync(sl.d_dbg, 0, 8192 * sizeof(uint32_t), c->stream));
         sc.dbg = sl.d_dbg;
@@ -2848,7 +2579,7 @@ grp_classify_stream_abort(grp_ctx* c, uint32_t slot)
   if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
     return set_err(c, GRP_ERR_STATE, "grp_classify_stream_abort: no streaming window in this slot");
   }
-  __atomic_store_n(c->slot[slot].h_abort, 1u, __ATOMIC_RELEASE);
+  __atomic_store_n(c->slot[slot].h_abort.p, 1u, __ATOMIC_RELEASE);
   return GRP_OK;
 }
 
@@ -3088,26 +2819,22 @@ grp_insert_tiles(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_t til
   const uint32_t nt = tile_end - tile_start;
   const uint64_t max_ranks = (uint64_t)nt * tile_frames(c) * c->params.h;
   const uint64_t want = next_pow2(max_ranks * 2);
-  if (want > c->dedup_cap) {
+  if (want > c->d_dedup.cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_dedup);
-    c->d_dedup = nullptr;
-    c->dedup_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_dedup, want * 8));
+    HIP_TRY(c, c->d_dedup.reset(want));
     HIP_TRY(c, hipMemsetAsync(c->d_dedup, 0, want * 8, c->stream));
-    c->dedup_cap = want;
     c->epoch = 0;
   }
   c->epoch += 1;
   if (c->epoch >= (1u << 24)) {
-    HIP_TRY(c, hipMemsetAsync(c->d_dedup, 0, c->dedup_cap * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_dedup, 0, c->d_dedup.cap * 8, c->stream));
     c->epoch = 1;
   }
   const unsigned long long epoch_tag = (unsigned long long)c->epoch << 40;
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   {
     Timer t(c, GRP_K_INSERT, max_ranks);
-    DISPATCH_H_SPAN(c, (k_insert<HH, WW><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->dedup_cap - 1, epoch_tag)));
+    DISPATCH_H_SPAN(c, (k_insert<HH, WW><<<dim3(nt * tile_parts(c)), dim3(THREADS), lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, read_idx, tile_start, id, c->d_dedup, c->d_dedup.cap - 1, epoch_tag)));
   }
   HIP_TRY(c, hipGetLastError());
   return GRP_OK;
@@ -3224,14 +2951,13 @@ grp_export_bits(grp_ctx* c, uint64_t* words, uint64_t n_words)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GRP_OK;
   }
-  uint32_t* d = nullptr;
-  HIP_TRY(c, hipMalloc(&d, (n_words * 2 + 3) * 4));
+  DevBuf<uint32_t> d;
+  HIP_TRY(c, d.reset(n_words * 2 + 3));
   HIP_TRY(c, hipMemsetAsync(d, 0, (n_words * 2 + 3) * 4, c->stream));
   k_export_bits<<<dim3((uint32_t)std::min<uint64_t>((c->f.n_buckets + 255) / 256, MAX_GRID_WGS)), dim3(256), 0, c->stream>>>(c->f.buckets, c->f.n_buckets, c->f.W, d);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(words, d, n_words * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d);
   return GRP_OK;
 }
 
@@ -3250,20 +2976,17 @@ grp_rank(grp_ctx* c, const uint64_t* pos, uint64_t n, uint8_t* bit, uint64_t* ra
     return GRP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  uint64_t *d_pos = nullptr, *d_rank = nullptr;
-  uint8_t* d_bit = nullptr;
-  HIP_TRY(c, hipMalloc(&d_pos, n * 8));
-  HIP_TRY(c, hipMalloc(&d_rank, n * 8));
-  HIP_TRY(c, hipMalloc(&d_bit, n));
+  DevBuf<uint64_t> d_pos, d_rank;
+  DevBuf<uint8_t> d_bit;
+  HIP_TRY(c, d_pos.reset(n));
+  HIP_TRY(c, d_rank.reset(n));
+  HIP_TRY(c, d_bit.reset(n));
   HIP_TRY(c, hipMemcpyAsync(d_pos, pos, n * 8, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_rank_positions, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->f, d_pos, n, d_bit, d_rank);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(bit, d_bit, n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(rank, d_rank, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_pos);
-  (void)hipFree(d_rank);
-  (void)hipFree(d_bit);
   return GRP_OK;
 }
 
@@ -3277,16 +3000,14 @@ grp_export_ids(grp_ctx* c, uint64_t first, uint64_t n, uint32_t* ids, uint32_t* 
     return GRP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  uint32_t *d_ids = nullptr, *d_cnt = nullptr;
-  HIP_TRY(c, hipMalloc(&d_ids, n * 4));
-  HIP_TRY(c, hipMalloc(&d_cnt, n * 4));
+  DevBuf<uint32_t> d_ids, d_cnt;
+  HIP_TRY(c, d_ids.reset(n));
+  HIP_TRY(c, d_cnt.reset(n));
   k_export_ids<<<dim3((uint32_t)std::min<uint64_t>((c->f.n_buckets + 255) / 256, MAX_GRID_WGS)), dim3(256), 0, c->stream>>>(c->f, first, n, d_ids, d_cnt);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(ids, d_ids, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(counts, d_cnt, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_ids);
-  (void)hipFree(d_cnt);
   return GRP_OK;
 }
 
@@ -3303,20 +3024,18 @@ grp_import_ids(grp_ctx* c, uint64_t first, uint64_t n, const uint32_t* ids, cons
     return GRP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  uint32_t *d_ids = nullptr, *d_cnt = nullptr;
+  DevBuf<uint32_t> d_ids, d_cnt;
   if (ids) {
-    HIP_TRY(c, hipMalloc(&d_ids, n * 4));
+    HIP_TRY(c, d_ids.reset(n));
     HIP_TRY(c, hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, c->stream));
   }
   if (counts) {
-    HIP_TRY(c, hipMalloc(&d_cnt, n * 4));
+    HIP_TRY(c, d_cnt.reset(n));
     HIP_TRY(c, hipMemcpyAsync(d_cnt, counts, n * 4, hipMemcpyHostToDevice, c->stream));
   }
   k_import_ids<<<dim3((uint32_t)std::min<uint64_t>((c->f.n_buckets + 255) / 256, MAX_GRID_WGS)), dim3(256), 0, c->stream>>>(c->f, first, n, d_ids, d_cnt);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_ids);
-  (void)hipFree(d_cnt);
   return GRP_OK;
 }
 
@@ -3336,14 +3055,13 @@ grp_debug_tile_hashes(grp_ctx* c, const grp_reads* r, uint32_t read_idx, uint32_
   if (nv > cap) {
     return set_err(c, GRP_ERR_NOMEM, "grp_debug_tile_hashes: %llu values, capacity %llu", (unsigned long long)nv, (unsigned long long)cap);
   }
-  uint64_t* d = nullptr;
-  HIP_TRY(c, hipMalloc(&d, nv * 8));
+  DevBuf<uint64_t> d;
+  HIP_TRY(c, d.reset(nv));
   const size_t lds = tab_bytes(c) + bases_bytes(tile + k + c->params.h);
   DISPATCH_H_SPAN(c, (k_debug_tile_hashes<HH, WW><<<dim3(1), dim3(THREADS), lds, c->stream>>>(r->dev, c->d_seeds, tile, read_idx, tile_idx, d, nv)));
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, d, nv * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d);
   return GRP_OK;
 }
 
@@ -3366,19 +3084,16 @@ grp_debug_locate(grp_ctx* c, const uint64_t* x, uint64_t n, uint64_t m, uint32_t
     return GRP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  uint64_t *d_x = nullptr, *d_mod = nullptr, *d_div = nullptr;
-  HIP_TRY(c, hipMalloc(&d_x, n * 8));
-  HIP_TRY(c, hipMalloc(&d_mod, n * 8));
-  HIP_TRY(c, hipMalloc(&d_div, n * 8));
+  DevBuf<uint64_t> d_x, d_mod, d_div;
+  HIP_TRY(c, d_x.reset(n));
+  HIP_TRY(c, d_mod.reset(n));
+  HIP_TRY(c, d_div.reset(n));
   HIP_TRY(c, hipMemcpyAsync(d_x, x, n * 8, hipMemcpyHostToDevice, c->stream));
   k_debug_locate<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream>>>(d_x, n, m, m_inv, W, w_magic, d_mod, d_div);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(mod_out, d_mod, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(div_out, d_div, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_x);
-  (void)hipFree(d_mod);
-  (void)hipFree(d_div);
   return GRP_OK;
 }
 
@@ -3406,62 +3121,42 @@ grp_debug_decide(grp_ctx* c, uint32_t n_reads, const uint64_t* tile0, const grp_
   }
   HIP_TRY(c, hipSetDevice(c->device));
   const uint64_t nt = tile0[n_reads];
-  uint64_t* d_tile0 = nullptr;
-  grp_tile_summary* d_tiles = nullptr;
-  grp_id_count* d_lists = nullptr;
-  uint32_t* d_ids = nullptr;
-  uint8_t* d_asg = nullptr;
-  uint64_t* d_scr = nullptr;
-  grp_read_decision* d_out = nullptr;
-  auto cleanup = [&] {
-    (void)hipFree(d_tile0);
-    (void)hipFree(d_tiles);
-    (void)hipFree(d_lists);
-    (void)hipFree(d_ids);
-    (void)hipFree(d_asg);
-    (void)hipFree(d_scr);
-    (void)hipFree(d_out);
-  };
-#define DBG_TRY(expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess) {                                                                                            \
-      cleanup();                                                                                                       \
-      return set_err(c, GRP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                                   \
-    }                                                                                                                  \
-  } while (0)
-  DBG_TRY(hipMalloc(&d_tile0, (n_reads + 1) * sizeof(uint64_t)));
-  DBG_TRY(hipMalloc(&d_tiles, std::max<uint64_t>(nt, 1) * sizeof(grp_tile_summary)));
-  DBG_TRY(hipMalloc(&d_lists, std::max<uint64_t>(n_lists, 1) * sizeof(grp_id_count)));
-  DBG_TRY(hipMalloc(&d_ids, std::max<uint64_t>(nt, 1) * 4));
-  DBG_TRY(hipMalloc(&d_asg, std::max<uint64_t>(nt, 1)));
-  DBG_TRY(hipMalloc(&d_scr, std::max<uint64_t>(nt, 1) * 8));
-  DBG_TRY(hipMalloc(&d_out, n_reads * sizeof(grp_read_decision)));
-  DBG_TRY(hipMemcpy(d_tile0, tile0, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DevBuf<uint64_t> d_tile0, d_scr;
+  DevBuf<grp_tile_summary> d_tiles;
+  DevBuf<grp_id_count> d_lists;
+  DevBuf<uint32_t> d_ids;
+  DevBuf<uint8_t> d_asg;
+  DevBuf<grp_read_decision> d_out;
+  HIP_TRY(c, d_tile0.reset((uint64_t)n_reads + 1));
+  HIP_TRY(c, d_tiles.reset(std::max<uint64_t>(nt, 1)));
+  HIP_TRY(c, d_lists.reset(std::max<uint64_t>(n_lists, 1)));
+  HIP_TRY(c, d_ids.reset(std::max<uint64_t>(nt, 1)));
+  HIP_TRY(c, d_asg.reset(std::max<uint64_t>(nt, 1)));
+  HIP_TRY(c, d_scr.reset(std::max<uint64_t>(nt, 1)));
+  HIP_TRY(c, d_out.reset(n_reads));
+  HIP_TRY(c, hipMemcpy(d_tile0, tile0, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (nt) {
-    DBG_TRY(hipMemcpy(d_tiles, tiles, nt * sizeof(grp_tile_summary), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_tiles, tiles, nt * sizeof(grp_tile_summary), hipMemcpyHostToDevice));
   }
   if (n_lists) {
-    DBG_TRY(hipMemcpy(d_lists, lists, n_lists * sizeof(grp_id_count), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_lists, lists, n_lists * sizeof(grp_id_count), hipMemcpyHostToDevice));
   }
-  DBG_TRY(hipMemset(d_ids, 0, std::max<uint64_t>(nt, 1) * 4));
-  DBG_TRY(hipMemset(d_asg, 0, std::max<uint64_t>(nt, 1)));
+  HIP_TRY(c, hipMemset(d_ids, 0, std::max<uint64_t>(nt, 1) * 4));
+  HIP_TRY(c, hipMemset(d_asg, 0, std::max<uint64_t>(nt, 1)));
   DevReads rd{};
   rd.tile0 = d_tile0;
   const uint32_t lds_tiles = decide_lds_tiles(tile0, n_reads);
-  DBG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_decide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)decide_lds_bytes(DECIDE_LDS_MAX_TILES)));
+  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_decide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)decide_lds_bytes(DECIDE_LDS_MAX_TILES)));
   k_decide<<<dim3(n_reads), dim3(DECIDE_THREADS), decide_lds_bytes(lds_tiles), c->stream>>>(rd, 0, n_reads, *dp, d_tiles, d_lists, std::max<uint64_t>(n_lists, 1), d_ids, d_asg, d_scr, d_out, lds_tiles);
-  DBG_TRY(hipGetLastError());
-  DBG_TRY(hipStreamSynchronize(c->stream));
-  DBG_TRY(hipMemcpy(out, d_out, n_reads * sizeof(grp_read_decision), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, d_out, n_reads * sizeof(grp_read_decision), hipMemcpyDeviceToHost));
   if (ids_out && nt) {
-    DBG_TRY(hipMemcpy(ids_out, d_ids, nt * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ids_out, d_ids, nt * 4, hipMemcpyDeviceToHost));
   }
   if (asg_out && nt) {
-    DBG_TRY(hipMemcpy(asg_out, d_asg, nt, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(asg_out, d_asg, nt, hipMemcpyDeviceToHost));
   }
-#undef DBG_TRY
-  cleanup();
   return GRP_OK;
 }
 
