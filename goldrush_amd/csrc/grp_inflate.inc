@@ -1,0 +1,809 @@
+// BGZF members inflated on the device (include/grpath_ingest.h: grp_bgzf_inflate).  A BGZF file is a series of
+// independent gzip members of at most 64 KiB of text; each one is a complete RFC 1951 stream, so the members of a
+// chunk are inflated side by side: ONE WAVE PER MEMBER, one wave per workgroup.
+//
+// A DEFLATE stream is serial, so the decode state (bit buffer, table look-ups, the symbol) is the same in all 64 lanes
+// — every lane executes the decoder redundantly, nothing diverges — and the lanes share the work that has a width:
+// building the Huffman tables, the match copies (out[p + j] = out[p - dist + j % dist]), the copies of stored blocks,
+// fetching the compressed bytes and flushing the text.  Everything the lanes hand to each other goes through LDS:
+//   ring      the last 32 KiB of text (the longest DEFLATE distance); flushed to HBM 16 KiB at a time as aligned dwords
+//   inw       1 KiB window of the compressed bytes, filled 512 B at a time from registers loaded one step ahead
+//   tables    a 10-bit (literal/length) and an 8-bit (distance) direct table, codes longer than that through the
+//             canonical counts; 37.8 KiB per workgroup in all: 4 workgroups (waves) per CU of 160 KiB — the decoder
+//             is bound by the latency of its dependent LDS look-ups, a wave per SIMD keeps the CU's LDS pipe in use
+// The lanes of ONE wave execute LDS operations in order, so a wavefront-scope fence (no instruction: it only keeps the
+// compiler from moving accesses across it) is all that stands between a lane's store and another lane's load.
+//
+// The decoder trusts nothing: every read of the compressed bytes is bounded by the member's payload (INF_Reader: words
+// outside it read as zero, and no more bits can be consumed than the payload has), every store by the member's
+// text_len, a distance may not reach in front of the member's first byte, every loop consumes input or produces output
+// in each iteration, no wave waits for another.  A member that is not a valid stream of exactly text_len bytes ends
+// with a status word; k_bgzf_crc then compares the CRC32 of every good member's text.
+//
+// The decoder is written against four macros so that the same text compiles as plain C++ with the 64 lanes run one
+// after the other (GRP_INFLATE_HOST: tools/dev/inflate_host_check.cpp checks the decoder against zlib under the sanitizers,
+// without a device).
+#ifndef GRP_INFLATE_HOST
+#define INF_FN __device__ __forceinline__
+#define INF_LANES for (int lane = (int)threadIdx.x, once_ = 1; once_; once_ = 0)
+#define INF_LV(x) x
+#define INF_LV_DECL(type, x) type x = 0
+#define INF_FENCE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
+#else
+#define INF_FN inline
+#define INF_LANES for (int lane = 0; lane < 64; ++lane)
+#define INF_LV(x) x[lane]
+#define INF_LV_DECL(type, x) type x[64] = {}
+#define INF_FENCE() (void)0
+#endif
+
+namespace {
+
+enum InfStatus : uint32_t
+{
+  INF_OK = 0,
+  INF_BAD_BLOCK_TYPE = 1,
+  INF_STORED_LEN = 2,
+  INF_INPUT_ENDS = 3,
+  INF_TEXT_TOO_LONG = 4,
+  INF_DIST_TOO_FAR = 5,
+  INF_TOO_MANY_SYMBOLS = 6,
+  INF_BAD_CODE_LENGTHS = 7,
+  INF_BAD_REPEAT = 8,
+  INF_NO_END_OF_BLOCK = 9,
+  INF_BAD_LITLEN_SET = 10,
+  INF_BAD_DIST_SET = 11,
+  INF_BAD_LITLEN_CODE = 12,
+  INF_BAD_DIST_CODE = 13,
+  INF_TEXT_TOO_SHORT = 14,
+  INF_BYTES_BEHIND_END = 15,
+  INF_CRC_MISMATCH = 16,
+  INF_STATUS_COUNT = 17,
+};
+
+const char* const INF_STATUS_TEXT[INF_STATUS_COUNT] = {
+  "ok",
+  "invalid block type",
+  "invalid stored block lengths",
+  "the compressed data ends inside the stream",
+  "the stream holds more text than the member's ISIZE",
+  "invalid distance too far back",
+  "too many length or distance symbols",
+  "invalid code lengths set",
+  "invalid bit length repeat",
+  "invalid code -- missing end-of-block",
+  "invalid literal/lengths set",
+  "invalid distances set",
+  "invalid literal/length code",
+  "invalid distance code",
+  "the stream holds less text than the member's ISIZE",
+  "compressed bytes behind the end of the stream",
+  "CRC32 of the text differs from the member's",
+};
+
+constexpr uint32_t INF_RING = 32768, INF_RMASK = INF_RING - 1;
+constexpr uint32_t INF_FLUSH = 16384;  // text is flushed once this much is waiting
+constexpr uint32_t INF_PIECE = 8192;   // a stored block is copied in pieces of this size
+constexpr int INF_LBITS = 10, INF_DBITS = 8, INF_CBITS = 7;
+constexpr uint32_t INF_MAX_TEXT = 65536; // ISIZE of a BGZF member
+
+struct InfLds
+{
+  uint8_t ring[INF_RING];
+  uint32_t inw[256];
+  uint16_t lit_fast[1 << INF_LBITS];
+  uint16_t dist_fast[1 << INF_DBITS];
+  uint16_t cl_fast[1 << INF_CBITS];
+  uint16_t lit_sorted[288];
+  uint16_t dist_sorted[32];
+  uint16_t cl_sorted[32];
+  uint16_t lit_count[16], dist_count[16], cl_count[16];
+  uint16_t first[16], offs[16]; // of the table being built
+  uint8_t lens[320 + 32];       // literal/length lengths, then the distance lengths; [320, 339): code length code
+};
+
+// one Huffman code: a direct table of `bits` bits ((symbol << 4) | length, 0: longer than that or no code), the symbols
+// sorted by (length, symbol) and the number of codes of every length
+struct InfHuff
+{
+  uint16_t* fast;
+  uint16_t* sorted;
+  uint16_t* count;
+  int bits;
+};
+
+// Builds `h` from n code lengths.  0, or 1: over-subscribed, or incomplete other than zlib accepts (no code at all; one
+// code of length 1 where `single_ok`).
+INF_FN int
+inf_build(InfLds& s, const InfHuff& h, const uint8_t* lens, int n, bool single_ok)
+{
+  INF_FENCE();
+  INF_LANES
+  {
+    if (lane < 16) { // lane L counts the codes of length L
+      uint32_t c = 0;
+      for (int i = 0; i < n; ++i) {
+        c += lens[i] == lane;
+      }
+      h.count[lane] = (uint16_t)(lane == 0 ? 0 : c);
+    }
+    for (int i = lane; i < (1 << h.bits); i += 64) {
+      h.fast[i] = 0;
+    }
+  }
+  INF_FENCE();
+  int left = 1, max_len = 0;
+  uint32_t code = 0, off = 0;
+  for (int l = 1; l <= 15; ++l) {
+    const uint32_t c = h.count[l];
+    left = (left << 1) - (int)c;
+    if (left < 0) {
+      return 1;
+    }
+    if (c) {
+      max_len = l;
+    }
+    s.first[l] = (uint16_t)code;
+    s.offs[l] = (uint16_t)off;
+    code = (code + c) << 1;
+    off += c;
+  }
+  if (left > 0 && max_len != 0 && !(single_ok && max_len == 1)) {
+    return 1;
+  }
+  const int total = (int)off;
+  INF_FENCE();
+  INF_LANES
+  {
+    if (lane >= 1 && lane < 16) { // lane L writes the symbols of length L in ascending order
+      uint32_t at = s.offs[lane];
+      for (int i = 0; i < n; ++i) {
+        if (lens[i] == lane) {
+          h.sorted[at++] = (uint16_t)i;
+        }
+      }
+    }
+  }
+  INF_FENCE();
+  INF_LANES
+  {
+    for (int i = lane; i < total; i += 64) {
+      const uint32_t sym = h.sorted[i];
+      const int l = lens[sym];
+      if (l <= h.bits) {
+        uint32_t c = (uint32_t)s.first[l] + (uint32_t)(i - (int)s.offs[l]), r = 0;
+        for (int b = 0; b < l; ++b) { // DEFLATE sends a code's first bit first: the table is indexed by the bits as they arrive
+          r |= ((c >> b) & 1u) << (l - 1 - b);
+        }
+        for (uint32_t k = r; k < (1u << h.bits); k += 1u << l) {
+          h.fast[k] = (uint16_t)((sym << 4) | (uint32_t)l);
+        }
+      }
+    }
+  }
+  INF_FENCE();
+  return 0;
+}
+
+// the compressed bytes of one member as a bit stream, least significant bit first
+struct InfReader
+{
+  const uint32_t* words; // the call's compressed bytes (4-byte aligned)
+  uint32_t lo, hi;       // the words that hold bytes of this member's payload: [lo, hi)
+  uint32_t di;           // the next word that goes into the bit buffer
+  uint32_t loaded_end;   // words [di, loaded_end) are in the LDS window
+  uint64_t bb;
+  int nb;                // bits in bb (bits of words outside the payload are zero)
+  int64_t avail;         // bits of the payload not consumed yet
+  bool failed;           // more bits were asked for than the payload has
+};
+
+#define INF_READER_LV INF_LV_DECL(uint32_t, in_r0); INF_LV_DECL(uint32_t, in_r1)
+
+// the registers take words [loaded_end, loaded_end + 128): used one step later, so the load's latency is not waited for
+#define INF_ISSUE(rd)                                                                                                  \
+  INF_LANES                                                                                                            \
+  {                                                                                                                    \
+    const uint32_t d0_ = (rd).loaded_end + (uint32_t)lane, d1_ = d0_ + 64;                                             \
+    INF_LV(in_r0) = (d0_ >= (rd).lo && d0_ < (rd).hi) ? (rd).words[d0_] : 0u;                                          \
+    INF_LV(in_r1) = (d1_ >= (rd).lo && d1_ < (rd).hi) ? (rd).words[d1_] : 0u;                                          \
+  }
+
+// at least 32 bits in the bit buffer
+#define INF_REFILL(rd, s)                                                                                              \
+  do {                                                                                                                 \
+    if ((rd).nb < 32) {                                                                                                \
+      if ((rd).loaded_end - (rd).di < 64) {                                                                            \
+        INF_LANES                                                                                                      \
+        {                                                                                                              \
+          (s).inw[((rd).loaded_end + (uint32_t)lane) & 255u] = INF_LV(in_r0);                                          \
+          (s).inw[((rd).loaded_end + (uint32_t)lane + 64) & 255u] = INF_LV(in_r1);                                     \
+        }                                                                                                              \
+        (rd).loaded_end += 128;                                                                                        \
+        INF_ISSUE(rd)                                                                                                  \
+        INF_FENCE();                                                                                                   \
+      }                                                                                                                \
+      (rd).bb |= (uint64_t)(s).inw[(rd).di & 255u] << (rd).nb;                                                         \
+      (rd).nb += 32;                                                                                                   \
+      (rd).di += 1;                                                                                                    \
+    }                                                                                                                  \
+  } while (0)
+
+// the stream goes on at byte `at` of the call's compressed bytes
+#define INF_SEEK(rd, s, at)                                                                                            \
+  do {                                                                                                                 \
+    (rd).di = (uint32_t)((at) >> 2);                                                                                   \
+    (rd).loaded_end = (rd).di;                                                                                         \
+    (rd).bb = 0;                                                                                                       \
+    (rd).nb = 0;                                                                                                       \
+    INF_ISSUE(rd)                                                                                                      \
+    INF_REFILL(rd, s);                                                                                                 \
+    (rd).bb >>= 8 * (int)((at) & 3);                                                                                   \
+    (rd).nb -= 8 * (int)((at) & 3);                                                                                    \
+  } while (0)
+
+// n <= 32 bits; the caller has refilled
+INF_FN uint32_t
+inf_take(InfReader& rd, int n)
+{
+  if (n > rd.avail) {
+    rd.failed = true;
+    rd.avail = 0;
+    return 0;
+  }
+  const uint32_t v = (uint32_t)(rd.bb & ((1ull << n) - 1));
+  rd.bb >>= n;
+  rd.nb -= n;
+  rd.avail -= n;
+  return v;
+}
+
+// one symbol of `h`; -1: no code of `h` starts the bits (or the payload ended).  The caller has refilled.
+INF_FN int
+inf_symbol(InfReader& rd, const InfHuff& h)
+{
+  const uint32_t e = h.fast[(uint32_t)rd.bb & ((1u << h.bits) - 1)];
+  if (e) {
+    (void)inf_take(rd, (int)(e & 15u));
+    return rd.failed ? -1 : (int)(e >> 4);
+  }
+  // a longer code: canonical decoding, a bit at a time
+  int code = 0, first = 0, index = 0;
+  for (int l = 1; l <= 15; ++l) {
+    code |= (int)((rd.bb >> (l - 1)) & 1u);
+    const int c = h.count[l];
+    if (code - c < first) {
+      (void)inf_take(rd, l);
+      return rd.failed ? -1 : (int)h.sorted[index + (code - first)];
+    }
+    index += c;
+    first = (first + c) << 1;
+    code <<= 1;
+  }
+  return -1;
+}
+
+// text [a, b) of the member leaves the ring: bytes up to the first 4-byte boundary of the destination, dwords, bytes
+INF_FN void
+inf_flush(InfLds& s, char* out, uint32_t a, uint32_t b)
+{
+  INF_FENCE();
+  const uint32_t n = b - a;
+  uint32_t head = (uint32_t)((4 - ((uintptr_t)(out + a) & 3)) & 3);
+  head = head < n ? head : n;
+  const uint32_t n4 = (n - head) >> 2, tail0 = a + head + 4 * n4;
+  INF_LANES
+  {
+    if ((uint32_t)lane < head) {
+      out[a + (uint32_t)lane] = (char)s.ring[(a + (uint32_t)lane) & INF_RMASK];
+    }
+    uint32_t* o4 = reinterpret_cast<uint32_t*>(out + a + head);
+    for (uint32_t i = (uint32_t)lane; i < n4; i += 64) {
+      const uint32_t q = a + head + 4 * i;
+      o4[i] = (uint32_t)s.ring[q & INF_RMASK] | (uint32_t)s.ring[(q + 1) & INF_RMASK] << 8 | (uint32_t)s.ring[(q + 2) & INF_RMASK] << 16 | (uint32_t)s.ring[(q + 3) & INF_RMASK] << 24;
+    }
+    if (tail0 + (uint32_t)lane < b) { // (fewer than 4)
+      out[tail0 + (uint32_t)lane] = (char)s.ring[(tail0 + (uint32_t)lane) & INF_RMASK];
+    }
+  }
+  INF_FENCE();
+}
+
+// Inflates one member: payload = comp[comp_off, comp_off + comp_len), text to out[0, text_len).  Returns its status.
+INF_FN uint32_t
+inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len, char* out, uint32_t text_len)
+{
+  const InfHuff lit{ s.lit_fast, s.lit_sorted, s.lit_count, INF_LBITS };
+  const InfHuff dist{ s.dist_fast, s.dist_sorted, s.dist_count, INF_DBITS };
+  const InfHuff cl{ s.cl_fast, s.cl_sorted, s.cl_count, INF_CBITS };
+  INF_READER_LV;
+  InfReader rd;
+  rd.words = reinterpret_cast<const uint32_t*>(comp);
+  rd.lo = (uint32_t)(comp_off >> 2);
+  rd.hi = (uint32_t)((comp_off + comp_len + 3) >> 2);
+  rd.avail = (int64_t)comp_len * 8;
+  rd.failed = false;
+  INF_SEEK(rd, s, comp_off);
+  uint32_t p = 0, flushed = 0; // text produced, text that has left the ring
+
+  for (;;) { // a block per iteration: its header consumes three bits
+    INF_REFILL(rd, s);
+    const uint32_t last = inf_take(rd, 1), type = inf_take(rd, 2);
+    if (rd.failed) {
+      return INF_INPUT_ENDS;
+    }
+    if (type == 3) {
+      return INF_BAD_BLOCK_TYPE;
+    }
+    if (type == 0) {
+      (void)inf_take(rd, (int)(rd.avail & 7)); // to the byte boundary (the payload starts on one)
+      INF_REFILL(rd, s);
+      const uint32_t len = inf_take(rd, 16), nlen = inf_take(rd, 16);
+      if (rd.failed) {
+        return INF_INPUT_ENDS;
+      }
+      if ((len ^ 0xffffu) != nlen) {
+        return INF_STORED_LEN;
+      }
+      if ((int64_t)len * 8 > rd.avail) {
+        return INF_INPUT_ENDS;
+      }
+      if (len > text_len - p) {
+        return INF_TEXT_TOO_LONG;
+      }
+      uint64_t at = comp_off + comp_len - (uint64_t)(rd.avail >> 3); // the block's bytes inside comp
+      rd.avail -= (int64_t)len * 8;
+      for (uint32_t left = len; left != 0;) { // every piece produces text
+        const uint32_t piece = left < INF_PIECE ? left : INF_PIECE;
+        INF_LANES
+        {
+          for (uint32_t j = (uint32_t)lane; j < piece; j += 64) {
+            s.ring[(p + j) & INF_RMASK] = comp[at + j];
+          }
+        }
+        p += piece;
+        at += piece;
+        left -= piece;
+        if (p - flushed >= INF_FLUSH) {
+          inf_flush(s, out, flushed, p);
+          flushed = p;
+        }
+      }
+      INF_FENCE();
+      INF_SEEK(rd, s, at);
+    } else {
+      if (type == 1) {
+        INF_LANES
+        {
+          for (int i = lane; i < 288; i += 64) {
+            s.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+          }
+          if (lane < 32) {
+            s.lens[288 + lane] = 5;
+          }
+        }
+        (void)inf_build(s, lit, s.lens, 288, false);
+        (void)inf_build(s, dist, s.lens + 288, 32, false);
+      } else {
+        INF_REFILL(rd, s);
+        const uint32_t n_lit = inf_take(rd, 5) + 257, n_dist = inf_take(rd, 5) + 1, n_cl = inf_take(rd, 4) + 4;
+        if (rd.failed) {
+          return INF_INPUT_ENDS;
+        }
+        if (n_lit > 286 || n_dist > 30) {
+          return INF_TOO_MANY_SYMBOLS;
+        }
+        INF_LANES
+        {
+          if (lane < 19) {
+            s.lens[320 + lane] = 0;
+          }
+        }
+        INF_FENCE();
+        for (uint32_t i = 0; i < n_cl; ++i) {
+          // the order the code length code's lengths are sent in: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
+          const uint32_t slot = i < 3 ? 16 + i : i == 3 ? 0 : (i & 1) ? 8 - ((i - 3) >> 1) : 8 + ((i - 4) >> 1);
+          INF_REFILL(rd, s);
+          s.lens[320 + slot] = (uint8_t)inf_take(rd, 3);
+        }
+        if (rd.failed) {
+          return INF_INPUT_ENDS;
+        }
+        if (inf_build(s, cl, s.lens + 320, 19, false)) {
+          return INF_BAD_CODE_LENGTHS;
+        }
+        // the literal/length and the distance lengths are one sequence: a repeat may run from the first into the second
+        const uint32_t n_all = n_lit + n_dist;
+        for (uint32_t i = 0; i < n_all;) { // every iteration sets at least one length
+          INF_REFILL(rd, s);
+          const int sym = inf_symbol(rd, cl);
+          if (sym < 0) {
+            return rd.failed ? INF_INPUT_ENDS : INF_BAD_CODE_LENGTHS;
+          }
+          if (sym < 16) {
+            s.lens[i++] = (uint8_t)sym;
+            continue;
+          }
+          uint32_t rep, val = 0;
+          if (sym == 16) {
+            if (i == 0) {
+              return INF_BAD_REPEAT;
+            }
+            INF_FENCE();
+            val = s.lens[i - 1];
+            rep = 3 + inf_take(rd, 2);
+          } else if (sym == 17) {
+            rep = 3 + inf_take(rd, 3);
+          } else {
+            rep = 11 + inf_take(rd, 7);
+          }
+          if (rd.failed) {
+            return INF_INPUT_ENDS;
+          }
+          if (i + rep > n_all) {
+            return INF_BAD_REPEAT;
+          }
+          for (uint32_t j = 0; j < rep; ++j) {
+            s.lens[i++] = (uint8_t)val;
+          }
+        }
+        INF_FENCE();
+        if (s.lens[256] == 0) {
+          return INF_NO_END_OF_BLOCK;
+        }
+        // the distance lengths move behind the literal/length table's 288 entries, so that both can be built in place
+        INF_LANES
+        {
+          uint8_t v = 0;
+          if ((uint32_t)lane < n_dist) {
+            v = s.lens[n_lit + (uint32_t)lane];
+          }
+          if (lane < 32) {
+            s.lens[320 + lane] = (uint32_t)lane < n_dist ? v : (uint8_t)0;
+          }
+        }
+        INF_FENCE();
+        if (inf_build(s, lit, s.lens, (int)n_lit, true)) {
+          return INF_BAD_LITLEN_SET;
+        }
+        if (inf_build(s, dist, s.lens + 320, (int)n_dist, true)) {
+          return INF_BAD_DIST_SET;
+        }
+      }
+      for (;;) { // a symbol per iteration: it consumes at least one bit
+        INF_REFILL(rd, s);
+        int sym = inf_symbol(rd, lit);
+        if (sym < 0) {
+          return rd.failed ? INF_INPUT_ENDS : INF_BAD_LITLEN_CODE;
+        }
+        if (sym < 256) {
+          if (p >= text_len) {
+            return INF_TEXT_TOO_LONG;
+          }
+          s.ring[p & INF_RMASK] = (uint8_t)sym;
+          p += 1;
+        } else if (sym == 256) {
+          break;
+        } else {
+          sym -= 257;
+          if (sym >= 29) {
+            return INF_BAD_LITLEN_CODE;
+          }
+          uint32_t len;
+          if (sym < 8) {
+            len = 3 + (uint32_t)sym;
+          } else if (sym == 28) {
+            len = 258;
+          } else {
+            const int xb = (sym - 4) >> 2;
+            len = ((4u + ((uint32_t)sym & 3u)) << xb) + 3 + inf_take(rd, xb);
+          }
+          INF_REFILL(rd, s);
+          const int ds = inf_symbol(rd, dist);
+          if (ds < 0) {
+            return rd.failed ? INF_INPUT_ENDS : INF_BAD_DIST_CODE;
+          }
+          if (ds >= 30) {
+            return INF_BAD_DIST_CODE;
+          }
+          uint32_t d;
+          if (ds < 4) {
+            d = 1 + (uint32_t)ds;
+          } else {
+            const int xb = (ds >> 1) - 1;
+            d = ((2u + ((uint32_t)ds & 1u)) << xb) + 1 + inf_take(rd, xb);
+          }
+          if (rd.failed) {
+            return INF_INPUT_ENDS;
+          }
+          if (d > p) { // BGZF members share no history
+            return INF_DIST_TOO_FAR;
+          }
+          if (len > text_len - p) {
+            return INF_TEXT_TOO_LONG;
+          }
+          // every source lies in front of p: written before this copy, whatever the overlap
+          INF_FENCE();
+          for (uint32_t j0 = 0; j0 < len; j0 += 64) { // 64 bytes at a time: all of them read, then all of them written
+            INF_LANES
+            {
+              const uint32_t j = j0 + (uint32_t)lane;
+              if (j < len) {
+                const uint32_t k = d >= len ? j : j % d;
+                s.ring[(p + j) & INF_RMASK] = s.ring[(p - d + k) & INF_RMASK];
+              }
+            }
+          }
+          INF_FENCE();
+          p += len;
+        }
+        if (p - flushed >= INF_FLUSH) {
+          inf_flush(s, out, flushed, p);
+          flushed = p;
+        }
+      }
+    }
+    if (last) {
+      break;
+    }
+  }
+  if (p != text_len) {
+    return INF_TEXT_TOO_SHORT;
+  }
+  if (rd.avail >= 8) {
+    return INF_BYTES_BEHIND_END;
+  }
+  if (p != flushed) {
+    inf_flush(s, out, flushed, p);
+  }
+  return INF_OK;
+}
+
+// ---- CRC32 (the gzip polynomial, reflected: 0xedb88320) of a member's text by one wave --------------------------------
+// The text is cut into 64 runs of a multiple of 4 bytes; every lane takes the remainder of its run (slicing by 4 with
+// tables in LDS where the addresses are aligned), moves it behind the runs after it — a multiplication by x^(8 * bytes)
+// modulo the polynomial — and the 64 results are XORed: a CRC is linear.
+constexpr uint32_t CRC_POLY = 0xedb88320u;
+
+INF_FN uint32_t
+crc_mulmod(uint32_t a, uint32_t b)
+{
+  uint32_t p = 0;
+  for (uint32_t m = 1u << 31; m != 0; m >>= 1) {
+    if (a & m) {
+      p ^= b;
+    }
+    b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
+  }
+  return p;
+}
+
+struct CrcLds
+{
+  uint32_t t[4 * 256 + 32]; // slicing tables t[256 * slice + byte], then x^(2^k) modulo the polynomial at t[1024 + k]
+  uint32_t part[64];
+};
+
+// tables: tab[4][256] then x2n[32] (crc_tables() on the host)
+INF_FN uint32_t
+crc_member(CrcLds& s, const uint32_t* tables, const char* text, uint32_t n)
+{
+  INF_FENCE();
+  INF_LANES
+  {
+    for (int i = lane; i < 1024 + 32; i += 64) {
+      s.t[i] = tables[i];
+    }
+  }
+  INF_FENCE();
+  const uint32_t per = (((n + 63) >> 6) + 3) & ~3u;
+  INF_LANES
+  {
+    const uint32_t a = (uint32_t)lane * per < n ? (uint32_t)lane * per : n;
+    const uint32_t b = a + per < n ? a + per : n;
+    uint32_t c = lane == 0 ? 0xffffffffu : 0u;
+    uint32_t i = a;
+    const uint8_t* t = reinterpret_cast<const uint8_t*>(text);
+    for (; i < b && ((uintptr_t)(t + i) & 3) != 0; ++i) {
+      c = s.t[(c ^ t[i]) & 0xff] ^ (c >> 8);
+    }
+    for (; i + 4 <= b; i += 4) {
+      c ^= *reinterpret_cast<const uint32_t*>(t + i);
+      c = s.t[768 + (c & 0xff)] ^ s.t[512 + ((c >> 8) & 0xff)] ^ s.t[256 + ((c >> 16) & 0xff)] ^ s.t[c >> 24];
+    }
+    for (; i < b; ++i) {
+      c = s.t[(c ^ t[i]) & 0xff] ^ (c >> 8);
+    }
+    // c * x^(8 * (n - b))
+    uint32_t shift = 1u << 31; // x^0
+    uint32_t bytes = n - b;
+    for (int k = 3; bytes != 0; bytes >>= 1, ++k) {
+      if (bytes & 1u) {
+        shift = crc_mulmod(s.t[1024 + (k & 31)], shift);
+      }
+    }
+    s.part[lane] = crc_mulmod(c, shift);
+  }
+  INF_FENCE();
+  uint32_t c = 0;
+  for (int i = 0; i < 64; ++i) {
+    c ^= s.part[i];
+  }
+  return c ^ 0xffffffffu;
+}
+
+#ifndef GRP_INFLATE_HOST
+// one workgroup of one wave per member; toff[i]: where member i's text starts in `text`
+__global__ void __launch_bounds__(64)
+k_bgzf_inflate(const uint8_t* __restrict__ comp, const grp_bgzf_block* __restrict__ blocks, const uint64_t* __restrict__ toff, uint32_t n_blocks, char* __restrict__ text, uint32_t* __restrict__ status)
+{
+  __shared__ InfLds s;
+  const uint32_t i = blockIdx.x;
+  if (i >= n_blocks) {
+    return;
+  }
+  const uint32_t st = inf_member(s, comp, blocks[i].comp_off, blocks[i].comp_len, text + toff[i], blocks[i].text_len);
+  if (threadIdx.x == 0) {
+    status[i] = st;
+  }
+}
+
+__global__ void __launch_bounds__(64)
+k_bgzf_crc(const grp_bgzf_block* __restrict__ blocks, const uint64_t* __restrict__ toff, uint32_t n_blocks, const char* __restrict__ text, const uint32_t* __restrict__ tables, uint32_t* __restrict__ status)
+{
+  __shared__ CrcLds s;
+  const uint32_t i = blockIdx.x;
+  if (i >= n_blocks || status[i] != INF_OK) {
+    return;
+  }
+  const uint32_t c = crc_member(s, tables, text + toff[i], blocks[i].text_len);
+  if (threadIdx.x == 0 && c != blocks[i].crc32) {
+    status[i] = INF_CRC_MISMATCH;
+  }
+}
+#endif
+
+// tab[4][256] (slicing by 4) and x2n[32] of the reflected gzip polynomial
+inline void
+crc_tables(uint32_t* out)
+{
+  for (uint32_t i = 0; i < 256; ++i) {
+    uint32_t c = i;
+    for (int k = 0; k < 8; ++k) {
+      c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
+    }
+    out[i] = c;
+  }
+  for (uint32_t i = 0; i < 256; ++i) {
+    for (int t = 1; t < 4; ++t) {
+      const uint32_t prev = out[(t - 1) * 256 + i];
+      out[t * 256 + i] = (prev >> 8) ^ out[prev & 0xff];
+    }
+  }
+  uint32_t p = 1u << 30; // x^1
+  out[1024] = p;
+  for (int k = 1; k < 32; ++k) {
+    uint32_t a = p, b = p, r = 0;
+    for (uint32_t m = 1u << 31; m != 0; m >>= 1) {
+      if (a & m) {
+        r ^= b;
+      }
+      b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    out[1024 + k] = p = r;
+  }
+}
+
+} // namespace
+
+#ifndef GRP_INFLATE_HOST
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+extern "C" int
+grp_bgzf_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block)
+{
+  if (!c) {
+    return GRP_ERR_INVALID;
+  }
+  if (bad_block) {
+    *bad_block = UINT32_MAX;
+  }
+  if ((!comp && n_comp) || (!blocks && n_blocks) || n_comp > (1ull << 32) || n_blocks > MAX_GRID_WGS) {
+    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: bad argument (at most 4 GiB of compressed bytes and 2^22 blocks per call)");
+  }
+  // the table is checked before anything is launched
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    const grp_bgzf_block& b = blocks[i];
+    const char* why = b.comp_off > n_comp || b.comp_len > n_comp - b.comp_off ? "its payload does not lie inside the compressed bytes" : b.text_len > INF_MAX_TEXT ? "more than 65536 bytes of text" : nullptr;
+    if (why) {
+      if (bad_block) {
+        *bad_block = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u: %s (payload [%llu, +%u) of %llu, text %u)", i, why, (unsigned long long)b.comp_off, b.comp_len, (unsigned long long)n_comp, b.text_len);
+    }
+    total += b.text_len;
+  }
+  if (total > text_cap || (total && !text_out)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: the blocks hold %llu bytes of text, the caller's buffer %llu", (unsigned long long)total, (unsigned long long)text_cap);
+  }
+  if (n_blocks == 0) {
+    return GRP_OK;
+  }
+  auto& bp = c->bgzf;
+  hipStream_t st = c->stream2; // (a fill queued on the main stream keeps running beside this)
+  if (!bp.d_tab.p) {
+    std::vector<uint32_t> tab(4 * 256 + 32);
+    crc_tables(tab.data());
+    HIP_TRY(c, bp.d_tab.reset(tab.size()));
+    HIP_TRY(c, hipMemcpy(bp.d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, bp.ev0.create(hipEventDefault));
+    HIP_TRY(c, bp.ev1.create(hipEventDefault));
+  }
+  // grown, never shrunk (like the ingest's buffers); the kernels read whole words: 8 bytes of padding behind each
+  HIP_TRY(c, bp.d_comp.ensure(n_comp + 8));
+  HIP_TRY(c, bp.d_text.ensure(total + 8));
+  HIP_TRY(c, bp.d_blocks.ensure(n_blocks));
+  HIP_TRY(c, bp.d_toff.ensure(n_blocks));
+  HIP_TRY(c, bp.d_status.ensure(n_blocks));
+  if (bp.h_blocks.cap < n_blocks) {
+    const uint64_t cap = (uint64_t)n_blocks + n_blocks / 4 + 64;
+    HIP_TRY(c, bp.h_blocks.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, bp.h_toff.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, bp.h_status.reset(cap, hipHostMallocDefault));
+  }
+  memcpy(bp.h_blocks.p, blocks, (size_t)n_blocks * sizeof(grp_bgzf_block));
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    bp.h_toff.p[i] = off;
+    off += blocks[i].text_len;
+  }
+  if (n_comp) {
+    HIP_TRY(c, hipMemcpyAsync(bp.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemsetAsync(bp.d_comp + n_comp, 0, 8, st));
+  HIP_TRY(c, hipMemcpyAsync(bp.d_blocks, bp.h_blocks.p, (size_t)n_blocks * sizeof(grp_bgzf_block), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(bp.d_toff, bp.h_toff.p, (size_t)n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(bp.ev0, st));
+  k_bgzf_inflate<<<n_blocks, 64, 0, st>>>(bp.d_comp, bp.d_blocks, bp.d_toff, n_blocks, reinterpret_cast<char*>(bp.d_text.p), bp.d_status);
+  k_bgzf_crc<<<n_blocks, 64, 0, st>>>(bp.d_blocks, bp.d_toff, n_blocks, reinterpret_cast<const char*>(bp.d_text.p), bp.d_tab, bp.d_status);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(bp.ev1, st));
+  HIP_TRY(c, hipMemcpyAsync(bp.h_status.p, bp.d_status, (size_t)n_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (total) {
+    HIP_TRY(c, hipMemcpyAsync(text_out, bp.d_text, total, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, bp.ev0, bp.ev1) == hipSuccess) {
+    bp.kernel_us += (double)ms * 1000.0;
+  }
+  bp.n_blocks += n_blocks;
+  bp.n_comp += n_comp;
+  bp.n_text += total;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    const uint32_t s = bp.h_status.p[i];
+    if (s != INF_OK) {
+      if (bad_block) {
+        *bad_block = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u is not a valid DEFLATE stream of %u bytes with CRC32 %08x: %s", i, blocks[i].text_len, blocks[i].crc32, s < INF_STATUS_COUNT ? INF_STATUS_TEXT[s] : "unknown status");
+    }
+  }
+  return GRP_OK;
+}
+
+extern "C" int
+grp_debug_bgzf_stats(const grp_ctx* c, uint64_t out[4])
+{
+  if (!c || !out) {
+    return GRP_ERR_INVALID;
+  }
+  out[0] = c->bgzf.n_blocks;
+  out[1] = c->bgzf.n_comp;
+  out[2] = c->bgzf.n_text;
+  out[3] = (uint64_t)c->bgzf.kernel_us;
+  return GRP_OK;
+}
+#endif

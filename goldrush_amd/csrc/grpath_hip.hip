@@ -1,7 +1,7 @@
 // libgrpath_hip.so — hand-written gfx950 (CDNA4) kernels + the C ABI of
 // include/grpath.h.  Integer / bit-vector work, HBM-transaction bound: no MFMA.
 // This file: context, launch logic and the exported functions; the kernels live in
-// grp_kernels.inc (hot path), grp_ingest.inc (FASTQ), grp_ntcard.inc (--ntcard).
+// grp_kernels.inc (hot path), grp_ingest.inc (FASTQ), grp_inflate.inc (BGZF input), grp_ntcard.inc (--ntcard).
 //
 // Kernels
 //   k_fill        spaced-seed ntHash of every read position + test-and-set of
@@ -23,6 +23,7 @@
 #include "host/gr_tiles_core.hpp"
 
 #include "../../include/grpath.h"
+#include "../../include/grpath_ingest.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -300,6 +301,22 @@ struct grp_ctx : CtxStreams
     Event text_up[FQ_TEXT_SLOTS];   // the slot's prefetched body has arrived (recorded on the copy stream)
     Event text_done[FQ_TEXT_SLOTS]; // the main stream's last use of the slot's text (grp_fastq_free records it: the next upload into the slot waits for it, not the host)
   } ingest;
+  // grp_bgzf_inflate (grp_inflate.inc): the compressed bytes, the block table with the text offsets, the text and the
+  // per-block status words of one call; grown, never shrunk
+  struct BgzfPool
+  {
+    DevBuf<uint8_t> d_comp, d_text;
+    DevBuf<grp_bgzf_block> d_blocks;
+    DevBuf<uint64_t> d_toff;
+    DevBuf<uint32_t> d_status;
+    DevBuf<uint32_t> d_tab; // CRC32 slicing tables and x^(2^k)
+    HostBuf<grp_bgzf_block> h_blocks; // page-locked staging
+    HostBuf<uint64_t> h_toff;
+    HostBuf<uint32_t> h_status;
+    Event ev0, ev1; // around the two kernels
+    uint64_t n_blocks = 0, n_comp = 0, n_text = 0; // grp_debug_bgzf_stats
+    double kernel_us = 0.0;
+  } bgzf;
   const char* reg_text = nullptr; // the caller's text buffer, page-locked by grp_fastq_pin
   size_t reg_bytes = 0;
   uint32_t timing_mask = (1u << GRP_K_FILL) | (1u << GRP_K_RANK) | (1u << GRP_K_QUERY) | (1u << GRP_K_DECIDE) | (1u << GRP_K_QUERY_LAT) | (1u << GRP_K_VERIFY) | (1u << GRP_K_BATCH);
@@ -3230,6 +3247,7 @@ grp_dev_hooks(void)
 #include "grp_batch.inc"
 #include "grp_verify.inc"
 #include "grp_ingest.inc"
+#include "grp_inflate.inc"
 #include "grp_ntcard.inc"
 #include "grp_comm.inc"
 #ifdef GRP_DEV_HOOKS // priced-and-rejected prototypes, measurement only (make DEV=1; include/grpath_dev.h)

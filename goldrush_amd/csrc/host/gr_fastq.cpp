@@ -43,6 +43,19 @@ InputFile::InputFile(const std::string& path)
   opened_ = f != nullptr;
 }
 
+InputFile::InputFile(const std::string& path, int gz_fd)
+{
+  path_ = path;
+  gzFile f = gzdopen(gz_fd, "rb");
+  if (f) {
+    gzbuffer(f, 1u << 20);
+  } else {
+    ::close(gz_fd);
+  }
+  f_ = f;
+  opened_ = f != nullptr;
+}
+
 InputFile::~InputFile()
 {
   if (f_) {

@@ -25,6 +25,9 @@ class InputFile
 {
 public:
   explicit InputFile(const std::string& path);
+  // the rest of `path` from where the descriptor stands, through zlib (the descriptor becomes the object's): what is left
+  // of a file whose BGZF members end in front of a plain gzip member
+  InputFile(const std::string& path, int gz_fd);
   ~InputFile();
   InputFile(const InputFile&) = delete;
   InputFile& operator=(const InputFile&) = delete;

@@ -96,5 +96,10 @@ int
 main(int argc, char** argv)
 {
   const grp_engine_vt vt = hip_engine();
-  return gr_path_main(argc, argv, &vt);
+  grp_engine_ext ext{};
+  ext.struct_size = sizeof(ext);
+  ext.bgzf_inflate = [](void* c, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n, char* text, uint64_t cap, uint32_t* bad) {
+    return grp_bgzf_inflate(static_cast<grp_ctx*>(c), comp, n_comp, blocks, n, text, cap, bad);
+  };
+  return gr_path_main_ext(argc, argv, &vt, &ext);
 }

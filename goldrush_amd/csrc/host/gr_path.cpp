@@ -5,6 +5,7 @@
 // Same flags, same stderr messages, same output files (<prefix>_<n>.fq in
 // --silver_path mode, <prefix>.fa otherwise), same exit codes.
 #include "../../../include/grpath_host.h"
+#include "gr_bgzf.hpp"
 #include "gr_classifier.hpp"
 #include "gr_fastq.hpp"
 #include "gr_opts.hpp"
@@ -12,7 +13,9 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cerrno>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <fstream>
 #include <functional>
@@ -69,6 +72,7 @@ struct PathRun
 {
   Opts opt;
   grp_engine_vt vt{};
+  grp_engine_ext ext{}; // the optional entry points behind the table's 48 (gr_path_main_ext)
   void* ctx = nullptr;
   std::vector<std::string> seeds;
   std::unordered_set<std::string> filter_out_reads;
@@ -206,6 +210,12 @@ private:
 // or classify — so a pass costs max(read, GPU) per chunk instead of their sum.  Four slots in ONE
 // page-locked buffer; every slot has room in front of the bytes read for the unconsumed tail of
 // the chunk before it (a partial record), which is copied there before the parse.
+// A BGZF-compressed file (gr_bgzf.hpp) whose members the engine can inflate (grp_engine_ext::bgzf_inflate; GRP_BGZF=off:
+// no) takes the same road: the reader thread reads COMPRESSED bytes and walks the members' headers; a slot is filled with
+// whole members until its text, its compressed bytes or its block table is full; the consumer has the engine inflate
+// them into the slot's text before that text is handed to fastq_prefetch / fastq_parse.  Everything behind that — the
+// carried tail, parse, pack, stats — does not know.  Plain gzip is one serial stream and stays with zlib; from a member
+// in mid-file that is not BGZF on (bgzip output followed by gzip output) zlib reads the rest.
 class GpuSource : public RecordSource
 {
 public:
@@ -214,11 +224,37 @@ public:
     , in_(run.opt.input)
   {
     chunk_ = std::max<size_t>(ingest_chunk_bytes(), 64);
+    {
+      const char* e = getenv("GRP_BGZF");
+      if (run_.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
+        // is the first member a complete BGZF member?  (a member is at most 64 KiB; a pipe cannot be pread: zlib)
+        const int fd = ::open(run.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
+        if (fd >= 0) {
+          std::vector<unsigned char> head(BGZF_MAX_MEMBER);
+          const ssize_t k = pread(fd, head.data(), head.size(), 0);
+          grp_bgzf_block b;
+          if (k > 0 && bgzf_scan(head.data(), (size_t)k, &b, 1, nullptr, nullptr) == 1) {
+            bgzf_ = true;
+            zfd_ = fd;
+          } else {
+            ::close(fd);
+          }
+        }
+      }
+    }
+    if (bgzf_) {
+      chunk_ = std::max<size_t>(chunk_, BGZF_MAX_TEXT); // a tiny GRP_INGEST_CHUNK still holds one member
+      comp_cap_ = std::max<size_t>(chunk_ / 2, BGZF_MAX_MEMBER);
+      tab_cap_ = std::max<size_t>(chunk_ / 4096, 64);
+      for (Slot& sl : slot_) {
+        sl.blocks.resize(tab_cap_);
+      }
+    }
     if (in_.plain_size() != 0) { // a small file: one slot holds it all, no 2 x 256 MiB to allocate and page-lock
       chunk_ = std::min<size_t>(chunk_, std::max<size_t>((size_t)in_.plain_size() + 1, size_t(1) << 16));
     }
     front_ = std::min<size_t>(std::max<size_t>(chunk_ / 16, 4096), (size_t)GRP_FASTQ_PREFETCH_FRONT); // (what a prefetched body may have in front of it, grpath_ingest.h)
-    buf_.resize((size_t)kSlots * (front_ + chunk_));
+    buf_.resize((size_t)kSlots * (front_ + chunk_ + comp_cap_)); // (the compressed bytes of the slots behind their texts: one page-locked buffer)
     const char* pin_min = getenv("GRP_PIN_MIN_BYTES"); // tests: page-lock small buffers too
     if (run_.vt.fastq_pin && run_.vt.fastq_unpin && buf_.size() >= (pin_min ? (size_t)atoll(pin_min) : (size_t(8) << 20))) {
       pinned_ = run_.vt.fastq_pin(run_.ctx, buf_.data(), buf_.size()) == GRP_OK;
@@ -240,7 +276,10 @@ public:
     }
     if (getenv("GRP_TRACE_INGEST")) {
       std::cerr << "GRP_TRACE_INGEST source: " << n_pre_[0] << " chunks, next chunk not ready at " << n_pre_[1] << ", uploads started ahead " << n_pre_[2] << "; seconds waiting for the reader " << t_tr_[0]
-                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << std::endl;
+                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << n_bgzf_blocks_ << std::endl;
+    }
+    if (zfd_ >= 0) {
+      ::close(zfd_);
     }
     if (pinned_) {
       run_.vt.fastq_unpin(run_.ctx); // before the buffer goes away: the engine cannot know when the host frees memory
@@ -271,6 +310,10 @@ public:
         sl = &slot_[take_];
         held_ = take_;
         take_ = (take_ + 1) % kSlots;
+      }
+      if (!inflate_slot(held_)) { // (the failure is noted: the run ends with an error behind this pass)
+        done_ = true;
+        break;
       }
       const bool eof = sl->eof;
       char* data = slot_data(held_);
@@ -365,6 +408,9 @@ public:
       if (slot_[j].uploaded || n == 0) {
         continue;
       }
+      if (!inflate_slot(j)) {
+        return;
+      }
       const double tq0 = now_s();
       const int qrc = run_.vt.fastq_prefetch(run_.ctx, slot_data(j), n);
       t_tr_[2] += now_s() - tq0;
@@ -407,8 +453,123 @@ private:
     uint64_t file_off = 0; // stream offset of the first of them
     bool eof = false;      // the data ends with this chunk
     bool uploaded = false; // consumer's: the engine has been handed the body ahead of its parse (prefetch_next)
+    // BGZF: the n bytes are the text of these members, inflated by the consumer before their first use
+    std::vector<grp_bgzf_block> blocks; // tab_cap_ entries; comp_off inside the slot's compressed bytes
+    size_t n_blocks = 0, comp_n = 0;
+    uint64_t comp_file_off = 0;         // where the slot's compressed bytes begin in the file
+    bool inflated = false, bad = false; // consumer's
   };
   char* slot_data(int i) { return buf_.data() + (size_t)i * (front_ + chunk_) + front_; }
+  unsigned char* slot_comp(int i) { return reinterpret_cast<unsigned char*>(buf_.data()) + (size_t)kSlots * (front_ + chunk_) + (size_t)i * comp_cap_; }
+  // the slot's members inflated into its text (once); false: the engine refused one of them
+  bool inflate_slot(int j)
+  {
+    Slot& sl = slot_[j];
+    if (sl.n_blocks == 0 || sl.inflated) {
+      return !sl.bad;
+    }
+    sl.inflated = true;
+    uint32_t bad = UINT32_MAX;
+    if (run_.ext.bgzf_inflate(run_.ctx, slot_comp(j), sl.comp_n, sl.blocks.data(), (uint32_t)sl.n_blocks, slot_data(j), chunk_, &bad) != GRP_OK) {
+      sl.bad = true;
+      uint64_t at = sl.comp_file_off; // the members of a slot follow each other
+      if (bad != UINT32_MAX && bad > 0 && bad < sl.n_blocks) {
+        at += sl.blocks[bad - 1].comp_off + sl.blocks[bad - 1].comp_len + 8;
+      }
+      note_input_failure("reading " + run_.opt.input + " failed: BGZF member " + (bad != UINT32_MAX ? "at byte " + std::to_string(at) : "in the chunk at byte " + std::to_string(at)) + ": " +
+                         (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
+      return false;
+    }
+    n_bgzf_blocks_ += sl.n_blocks;
+    return true;
+  }
+  // The reader's side of a BGZF file: whole members into slot i until its text (chunk_), its compressed bytes
+  // (comp_cap_) or its table (tab_cap_) is full.  Returns the bytes of text the members hold.  A member that is not BGZF
+  // hands the rest of the file to zlib (ztail_); a file that ends inside a member is an error, one that ends without
+  // the empty end-of-file member is not (zlib accepts it too).
+  size_t read_bgzf(int i, bool& eof)
+  {
+    constexpr size_t kPiece = size_t(16) << 20;
+    Slot& sl = slot_[i];
+    unsigned char* comp = slot_comp(i);
+    for (;;) { // (again only behind a table full of empty members)
+      size_t have = 0, pos = 0, text = 0, nb = 0;
+      bool full = false, file_end = false, other = false;
+      sl.comp_file_off = zoff_;
+      while (!full) {
+        if (!file_end && have < comp_cap_ && have - pos < BGZF_MAX_MEMBER) {
+          const size_t want = std::min(comp_cap_ - have, kPiece);
+          size_t k = 0;
+          while (k < want) {
+            const ssize_t r = pread(zfd_, comp + have + k, want - k, (off_t)(zoff_ + have + k));
+            if (r < 0 && errno == EINTR) {
+              continue;
+            }
+            if (r < 0) {
+              note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(zoff_ + have + k) + ": " + strerror(errno));
+            }
+            if (r <= 0) {
+              file_end = true;
+              break;
+            }
+            k += (size_t)r;
+          }
+          have += k;
+        }
+        int why = 1;
+        const size_t base = pos;
+        const size_t got = bgzf_scan(comp + base, have - base, &sl.blocks[nb], tab_cap_ - nb, nullptr, &why);
+        for (size_t t = 0; t < got; ++t) {
+          grp_bgzf_block& b = sl.blocks[nb]; // (comp_off: inside what was scanned)
+          if (text + b.text_len > chunk_) {
+            full = true;
+            break;
+          }
+          b.comp_off += base;
+          text += b.text_len;
+          pos = (size_t)b.comp_off + b.comp_len + 8;
+          ++nb;
+        }
+        if (full) {
+          break;
+        }
+        if (nb == tab_cap_) {
+          full = true;
+        } else if (why == 2) {
+          other = true;
+          break;
+        } else if (file_end) { // (why 0: bytes of a member are missing; 1: the members end with the file)
+          if (have > pos) {
+            note_input_failure("reading " + run_.opt.input + " failed: the file ends inside the BGZF member at byte " + std::to_string(zoff_ + pos) + " (truncated)");
+          }
+          eof = true;
+          break;
+        } else if (have == comp_cap_) {
+          full = true;
+        }
+      }
+      zoff_ += pos;
+      sl.n_blocks = nb;
+      sl.comp_n = pos;
+      if (other) {
+        // from this member on zlib reads, from a descriptor of its own that stands there
+        const int fd = ::open(run_.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
+        if (fd >= 0 && lseek(fd, (off_t)zoff_, SEEK_SET) == (off_t)zoff_) {
+          ztail_.reset(new InputFile(run_.opt.input, fd));
+        } else if (fd >= 0) {
+          ::close(fd);
+        }
+        if (!ztail_ || !ztail_->ok()) {
+          note_input_failure("reading " + run_.opt.input + " failed: cannot read on behind the BGZF members at byte " + std::to_string(zoff_));
+          ztail_.reset();
+          eof = true;
+        }
+      }
+      if (text != 0 || eof || other) {
+        return text;
+      }
+    }
+  }
   void read_loop()
   {
     uint64_t off = 0;
@@ -422,12 +583,21 @@ private:
       }
       size_t got = 0;
       bool eof = false;
-      while (!eof && got < chunk_) {
-        const size_t k = in_.read(slot_data(i) + got, chunk_ - got);
-        if (k == 0) {
-          eof = true;
+      slot_[i].n_blocks = slot_[i].comp_n = 0; // (a FREE slot is the reader's)
+      slot_[i].inflated = slot_[i].bad = false;
+      if (bgzf_ && !ztail_) {
+        got = read_bgzf(i, eof);
+      }
+      if (got == 0 && !eof && (!bgzf_ || ztail_)) {
+        slot_[i].n_blocks = slot_[i].comp_n = 0; // (empty members in front of the part zlib reads)
+        InputFile& in = ztail_ ? *ztail_ : in_;
+        while (!eof && got < chunk_) {
+          const size_t k = in.read(slot_data(i) + got, chunk_ - got);
+          if (k == 0) {
+            eof = true;
+          }
+          got += k;
         }
-        got += k;
       }
       {
         std::lock_guard<std::mutex> g(mu_);
@@ -458,6 +628,14 @@ private:
   std::vector<char> carry_; // unconsumed tail of the chunk before
   std::vector<char> big_;
   size_t chunk_ = 0, front_ = 0;
+  // a BGZF file: the reader's descriptor and how far it has come, the capacities of a slot beside its text, what
+  // follows the BGZF members (through zlib)
+  bool bgzf_ = false;
+  int zfd_ = -1;
+  uint64_t zoff_ = 0;
+  size_t comp_cap_ = 0, tab_cap_ = 0;
+  std::unique_ptr<InputFile> ztail_;
+  uint64_t n_bgzf_blocks_ = 0; // (developer trace)
   bool pinned_ = false;
   std::thread reader_;
   std::mutex mu_;
@@ -1002,9 +1180,18 @@ rollover_sink(void* user, uint64_t new_path)
 extern "C" int
 gr_path_main(int argc, char** argv, const grp_engine_vt* vt)
 {
+  return gr_path_main_ext(argc, argv, vt, nullptr);
+}
+
+extern "C" int
+gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engine_ext* ext)
+{
   using namespace gr;
   PathRun run;
   run.vt = *vt;
+  if (ext && ext->struct_size >= offsetof(grp_engine_ext, bgzf_inflate) + sizeof(ext->bgzf_inflate)) {
+    run.ext.bgzf_inflate = ext->bgzf_inflate;
+  }
   Opts& opt = run.opt;
   // Several GPUs of one node: one process per GPU (GRP_WORLD / GRP_RANK, or the launcher's
   // WORLD_SIZE / RANK; LOCAL_RANK picks the device).  Every rank runs the whole program on

@@ -100,6 +100,14 @@ class grp_engine_vt(C.Structure):
     _fields_ = VT_TYPES
 
 
+# the optional entry points behind the table's 48 (include/grpath_host.h)
+BGZF_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32))
+
+
+class grp_engine_ext(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN)]
+
+
 COMMIT_FN = C.CFUNCTYPE(C.c_double, _vp, C.POINTER(gr_commit))
 ROLLOVER_FN = C.CFUNCTYPE(None, _vp, C.c_uint64)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp)
@@ -139,6 +147,8 @@ SIGNATURES = {
     "gr_classifier_error": (C.c_char_p, [_vp]),
     "gr_classifier_get_state": (None, [_vp, C.POINTER(gr_classifier_state)]),
     "gr_path_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(grp_engine_vt)]),
+    "gr_path_main_ext": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(grp_engine_vt), C.POINTER(grp_engine_ext)]),
+    "gr_bgzf_scan": (C.c_size_t, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gr_input_read": (C.c_uint64, [C.c_char_p, C.c_uint64, _vp, C.c_uint64]),
 }
 
@@ -247,6 +257,24 @@ def eval_flanks(ls, le, ids):
     ts, te = C.c_size_t(), C.c_size_t()
     g = load().gr_eval_flanks(ls, le, _p(a), a.size, C.byref(ts), C.byref(te))
     return bool(g), ts.value, te.value
+
+
+def bgzf_scan(buf: bytes, cap: int = 1 << 16):
+    """gr_bgzf_scan -> ([(payload offset, payload length, ISIZE, CRC32)], consumed, why)"""
+    blocks = np.zeros(max(cap, 1), dtype=native.bgzf_block_dtype)
+    consumed, why = C.c_size_t(), C.c_int()
+    raw = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+    n = load().gr_bgzf_scan(_p(raw), len(buf), _p(blocks), cap, C.byref(consumed), C.byref(why))
+    return [(int(b["comp_off"]), int(b["comp_len"]), int(b["text_len"]), int(b["crc32"])) for b in blocks[:n]], consumed.value, why.value
+
+
+def hip_engine_ext() -> grp_engine_ext:
+    """The second table filled with the symbols of libgrpath_hip.so."""
+    lib = native.load()
+    ext = grp_engine_ext()
+    ext.struct_size = C.sizeof(grp_engine_ext)
+    ext.bgzf_inflate = C.cast(lib.grp_bgzf_inflate, BGZF_INFLATE_FN)
+    return ext
 
 
 def hip_engine_vt() -> grp_engine_vt:

@@ -129,6 +129,8 @@ SIGNATURES = {
     "grp_debug_tile_hashes": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "grp_debug_tile_states": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "grp_debug_locate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
+    "grp_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "grp_debug_bgzf_stats": (C.c_int, [_vp, _vp]),
     "grp_dev_hooks": (C.c_int, []),
     "grp_set_timing": (C.c_int, [_vp, C.c_int]),
     "grp_get_kernel_stats": (C.c_int, [_vp, C.POINTER(grp_kernel_stat)]),
@@ -153,6 +155,9 @@ SIGNATURES.update({
 
 fastq_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("id_len", "<u4"), ("seq_len", "<u4"),
                               ("qual_len", "<u4"), ("flags", "<u4"), ("phred_sum", "<f8"), ("phred_first", "<f8")])
+
+# grp_bgzf_block (include/grpath_ingest.h): a BGZF member's DEFLATE payload inside the compressed bytes, ISIZE and CRC32 of its trailer
+bgzf_block_dtype = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 
 # include/grpath_ingest.h
 SIGNATURES.update({
@@ -373,6 +378,31 @@ class Engine:
         if n_rec.value:
             self._check(self.lib.grp_fastq_records(out, _ptr(rec)))
         return out, rec, used.value, bool(stopped.value)
+
+    # -- BGZF members inflated on the device (include/grpath_ingest.h)
+    def bgzf_inflate(self, comp, blocks, text_cap: "int | None" = None) -> bytes:
+        """grp_bgzf_inflate: comp = the compressed bytes, blocks = bgzf_block_dtype records (or (comp_off, comp_len, text_len,
+        crc32) tuples); returns the text.  A refused block raises GrpError with .bad_block set."""
+        buf = np.frombuffer(comp, dtype=np.uint8) if len(comp) else np.zeros(1, dtype=np.uint8)
+        if not isinstance(blocks, np.ndarray):
+            blocks = np.array([tuple(b) + (0,) for b in blocks], dtype=bgzf_block_dtype)
+        blocks = np.ascontiguousarray(blocks, dtype=bgzf_block_dtype)
+        total = int(blocks["text_len"].astype(np.uint64).sum())
+        cap = total if text_cap is None else text_cap
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        bad = C.c_uint32(0xFFFFFFFF)
+        rc = self.lib.grp_bgzf_inflate(self._h, _ptr(buf), len(comp), _ptr(blocks) if len(blocks) else None, len(blocks), _ptr(out), cap, C.byref(bad))
+        if rc != GRP_OK:
+            e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
+            e.bad_block = None if bad.value == 0xFFFFFFFF else bad.value
+            raise e
+        return out[:total].tobytes()
+
+    def bgzf_stats(self) -> dict:
+        """blocks, compressed bytes, text bytes and kernel microseconds of all bgzf_inflate calls of this engine"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.grp_debug_bgzf_stats(self._h, _ptr(out)))
+        return dict(zip(("blocks", "comp_bytes", "text_bytes", "kernel_us"), (int(v) for v in out)))
 
     # -- phase 0 (--ntcard)
     def ntcard_begin(self, sbits: int = 7):

@@ -614,6 +614,12 @@ int grp_debug_verify_stats(const grp_ctx* ctx, uint64_t out[12]);
  * full), [7] inserts that kept; [0] resumable windows whose cooperative launch was refused */
 int grp_debug_stream_stats(const grp_ctx* ctx, uint64_t out[8]);
 
+/* BGZF members inflated on the device: documented in grpath_ingest.h, which holds the struct; named here because this
+ * header is the list of every function the engine exports */
+typedef struct grp_bgzf_block grp_bgzf_block;
+int grp_bgzf_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block);
+int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
+
 /* 1: the library was built with GRP_DEV_HOOKS (make DEV=1): the measurement-only prototypes of include/grpath_dev.h are
  * compiled in; 0: the product build (they are not exported) */
 int grp_dev_hooks(void);

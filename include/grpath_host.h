@@ -269,8 +269,25 @@ void gr_classifier_get_state(const gr_classifier* c, gr_classifier_state* out);
  * CLI's chunk reader. */
 uint64_t gr_input_read(const char* path, uint64_t request_bytes, char* dst, uint64_t cap);
 
+/* ---- BGZF input (csrc/host/gr_bgzf.cpp) ----------------------------------------------------------------------------
+ * walk the gzip members in [buf, buf+n): fills blocks (payload offset/len, ISIZE, CRC32) while they are BGZF
+ * members (FEXTRA with a 'B','C',SLEN=2 subfield, CM=8) that lie completely inside the buffer; returns their
+ * number, *consumed = bytes they span, *why = 0 more data needed / 1 end of buffer (or `cap` blocks found) / 2 a member
+ * that is not BGZF (other flags than FEXTRA, no BC subfield, an ISIZE above 65536: zlib's business) */
+size_t gr_bgzf_scan(const unsigned char* buf, size_t n, grp_bgzf_block* blocks, size_t cap, size_t* consumed, int* why);
+
+/* ---- optional engine entry points that came after grp_engine_vt was frozen at 48 members: a second table, every member
+ * optional (NULL, or a struct_size that ends in front of it: the host takes the path it took without it) */
+typedef struct
+{
+  uint32_t struct_size;
+  /* grp_bgzf_inflate: with it, a BGZF-compressed input is inflated on the device (GRP_BGZF=off: through zlib as before) */
+  int (*bgzf_inflate)(void* ctx, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block);
+} grp_engine_ext;
+
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */
-int gr_path_main(int argc, char** argv, const grp_engine_vt* vt);
+int gr_path_main(int argc, char** argv, const grp_engine_vt* vt); /* = gr_path_main_ext(argc, argv, vt, NULL) */
+int gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engine_ext* ext);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,35 @@ void grp_fastq_free(grp_fastq* fq);
 int grp_fastq_pin(grp_ctx* ctx, const char* buffer, uint64_t n_bytes);
 int grp_fastq_unpin(grp_ctx* ctx);
 
+/*
+ * ---- BGZF-compressed FASTQ: the inflate in front of the ingest ------------------------------------------------
+ * A BGZF file (what bgzip and the htslib tools write) is a series of independent gzip members of at most 64 KiB of
+ * text, each of which says its compressed size in its header: the members of a chunk are inflated side by side on the
+ * device (csrc/grp_inflate.inc: one wave per member, a complete RFC 1951 decoder; then the CRC32 of every member's
+ * text), where one zlib thread inflates a plain gzip stream serially.  The caller finds the members (the host's
+ * gr_bgzf_scan) and hands over their table; the text comes back to host memory, where it is FASTQ text like any other
+ * (grp_fastq_prefetch / grp_fastq_parse).
+ */
+struct grp_bgzf_block
+{
+  uint64_t comp_off;  /* first byte of the member's DEFLATE payload inside `comp` */
+  uint32_t comp_len;  /* payload bytes (BSIZE + 1 - 12 - XLEN - 8) */
+  uint32_t text_len;  /* ISIZE of the member's trailer, <= 65536 */
+  uint32_t crc32;     /* CRC32 of the trailer */
+  uint32_t reserved;
+}; /* (the typedef is in grpath.h, which lists every function the engine exports) */
+
+/* Inflate n_blocks independent raw-DEFLATE payloads on the device; the text of block i goes to
+ * text_out + sum(text_len[0..i)).  Synchronous.  GRP_ERR_INVALID with *bad_block = the first block that
+ * is not a valid stream of exactly text_len bytes with that CRC32 (and a reason in grp_last_error); text_out
+ * is then unspecified.  The table is checked before anything is launched (ranges inside comp, text_len <= 65536, the
+ * sum of the texts <= text_cap: GRP_ERR_INVALID, *bad_block = the entry).  Pinned memory (grp_fastq_pin) makes both
+ * copies one DMA each.  The work runs on the side stream: a fill queued on the main stream keeps running beside it.
+ * Same threading / stream rules as grp_fastq_parse. */
+int grp_bgzf_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block);
+/* blocks, compressed bytes, text bytes, kernel microseconds (HIP events around the two kernels) since grp_create */
+int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,15 @@ geometry, ~5 GB of text) and runs goldrush-path on it the way bin/goldrush does 
 (--silver_path -M 5 -r 0.9 -m 20000, bin/goldrush:253-260) and process #2 (golden path on the
 silver reads, :240-248) — with the reads kept on the device between the passes (default) and with
 the second parse (GRP_RESIDENT=off); every run twice, the faster one counts.  Wall time, the program's own phase timers, reads/s
-FASTQ-inclusive; bench.py on the same geometry beside it."""
+FASTQ-inclusive; bench.py on the same geometry beside it.
+
+  tools/cli_end_to_end.py --bgzf <out.json> [reads] [genome]
+
+The same file BGZF-compressed (a writer of its own: zlib level 1, members of 65280 bytes of text, at most 16 processes):
+the rate of the inflate kernels alone (grp_debug_bgzf_stats: text bytes / kernel time, the file's members in calls of one
+ingest chunk of text), and process #1 end to end, three runs each, all kept — this tree on the BGZF file (the device
+inflates), the same with GRP_BGZF=off (zlib), the binary named by CLI_E2E_PARENT on the BGZF file (the parent commit:
+zlib), this tree and the parent on the plain file (the floor, and what the plain path pays)."""
 import json
 import os
 import re
@@ -32,7 +40,108 @@ def run_cli(args, env=None):
     return {"rc": r.returncode, "wall_s": dt, "phase_timers_s": ins, "visited": int(visited[-1]) if visited else None, "stderr_tail": r.stderr[-300:] if r.returncode else ""}
 
 
+def _bgzf_piece(job):
+    import struct
+    import zlib
+
+    path, off, n = job
+    with open(path, "rb") as fh:
+        fh.seek(off)
+        text = fh.read(n)
+    out = []
+    for a in range(0, len(text), 65280):
+        t = text[a:a + 65280]
+        c = zlib.compressobj(1, zlib.DEFLATED, -15)
+        p = c.compress(t) + c.flush()
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(p) + 25) + p + struct.pack("<II", zlib.crc32(t), len(t)))
+    return b"".join(out)
+
+
+def write_bgzf(fq, gz):
+    """BGZF of `fq`: pieces of 255 members compressed by up to 16 processes, written in order; then the empty end-of-file member"""
+    from multiprocessing import Pool
+
+    size, piece = os.path.getsize(fq), 255 * 65280
+    jobs = [(fq, off, piece) for off in range(0, size, piece)]
+    with Pool(min(16, len(os.sched_getaffinity(0)))) as pool, open(gz, "wb") as dst:
+        for blob in pool.imap(_bgzf_piece, jobs, chunksize=1):
+            dst.write(blob)
+        dst.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+
+
+def bgzf_mode(out, fq, n_reads, genome, res):
+    import numpy as np
+
+    from goldrush_amd import host, native
+
+    tmp = os.path.dirname(fq)
+    gz = fq + ".gz"
+    t0 = time.perf_counter()
+    write_bgzf(fq, gz)
+    res["bgzf_bytes"] = os.path.getsize(gz)
+    res["bgzf_written_s"] = time.perf_counter() - t0
+    # the kernels alone: the file's members in calls of one ingest chunk (256 MiB) of text each
+    chunk = 256 << 20
+    eng = native.Engine(22, 3, 1000, 1 << 20, [SEED[:11] + "0" * i + SEED[11:] for i in range(3)])
+    calls, t0 = 0, time.perf_counter()
+    with open(gz, "rb") as fh:
+        carry = b""
+        while True:
+            buf = carry + fh.read(64 << 20)
+            if not buf:
+                break
+            blocks, consumed, why = host.bgzf_scan(buf, 1 << 16)
+            assert blocks or not buf, "not a BGZF file"
+            text = 0
+            keep = []
+            for b in blocks:
+                if text + b[2] > chunk:
+                    break
+                keep.append(b)
+                text += b[2]
+            consumed = keep[-1][0] + keep[-1][1] + 8
+            eng.bgzf_inflate(np.frombuffer(buf, dtype=np.uint8)[:consumed], keep)
+            calls += 1
+            carry = buf[consumed:]
+    st = eng.bgzf_stats()
+    eng.close()
+    res["inflate_kernels"] = dict(st, calls=calls, text_GB_per_s=st["text_bytes"] / max(st["kernel_us"], 1) / 1e3, wall_s_with_copies_and_python=time.perf_counter() - t0,
+                                  fill_pass_needs_text_GB_per_s=29.0)
+    assert st["text_bytes"] == res["fastq_bytes"], (st, res["fastq_bytes"])
+    base = ["-k22", "-w16", "-t1000", "-u5", "-a1", "-o0.1", "-h3", "-j16", "-P10", "-d5", "-x10", "-s" + SEED, "-g%d" % genome, "-b10", "--verbose"]
+    pdir = os.path.join(tmp, "cli_e2e_out")
+    os.makedirs(pdir, exist_ok=True)
+    parent = os.environ.get("CLI_E2E_PARENT")
+    global CLI
+    this = CLI
+    runs = [("this_tree/bgzf_device", this, gz, {}), ("this_tree/bgzf_zlib", this, gz, {"GRP_BGZF": "off"}), ("this_tree/plain", this, fq, {})]
+    if parent:
+        runs += [("parent/bgzf_zlib", parent, gz, {}), ("parent/plain", parent, fq, {})]
+    outputs = {}
+    for name, binary, path, env in runs:
+        CLI = binary
+        tag = name.replace("/", "_")
+        three = [run_cli(base + ["-r0.9", "--silver_path", "-M5", "-m20000", "-i", path, "-p", os.path.join(pdir, tag)], dict(env, GRP_TRACE_INGEST="1")) for _ in range(3)]
+        r = min(three, key=lambda x: x["wall_s"])
+        r["wall_s_all"] = [round(x["wall_s"], 3) for x in three]
+        r["text_GB_per_s_end_to_end"] = res["fastq_bytes"] / r["wall_s"] / 1e9
+        res["runs"][name] = r
+        import hashlib
+
+        outputs[name] = {f: hashlib.sha256(open(os.path.join(pdir, f), "rb").read()).hexdigest() for f in sorted(os.listdir(pdir)) if f.startswith(tag + "_")}
+        outputs[name] = sorted((f[len(tag):], h) for f, h in outputs[name].items())
+    CLI = this
+    res["outputs_identical"] = all(o == outputs["this_tree/plain"] and o for o in outputs.values())
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res, indent=1))
+    os.remove(fq)
+    os.remove(gz)
+
+
 def main():
+    bgzf = "--bgzf" in sys.argv
+    if bgzf:
+        sys.argv.remove("--bgzf")
     out = sys.argv[1]
     n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
     genome = int(float(sys.argv[3])) if len(sys.argv) > 3 else 100_000_000
@@ -59,6 +168,8 @@ def main():
                     done += 1
     size = os.path.getsize(fq)
     res = {"fastq_bytes": size, "reads": n_reads, "genome": genome, "fastq_written_s": time.perf_counter() - t0, "fastq_generator": generator, "runs": {}}
+    if bgzf:
+        return bgzf_mode(out, fq, n_reads, genome, res)
     base = ["-k22", "-w16", "-t1000", "-u5", "-a1", "-o0.1", "-h3", "-j16", "-P10", "-d5", "-x10", "-s" + SEED, "-g%d" % genome, "-b10", "--verbose"]
     pdir = os.path.join(tmp, "cli_e2e_out")
     os.makedirs(pdir, exist_ok=True)
