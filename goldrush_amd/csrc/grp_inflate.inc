@@ -58,7 +58,9 @@ enum InfStatus : uint32_t
   INF_TEXT_TOO_SHORT = 14,
   INF_BYTES_BEHIND_END = 15,
   INF_CRC_MISMATCH = 16,
-  INF_STATUS_COUNT = 17,
+  INF_FINAL_INSIDE = 17, // (segments only)
+  INF_NO_FINAL = 18,
+  INF_STATUS_COUNT = 19,
 };
 
 const char* const INF_STATUS_TEXT[INF_STATUS_COUNT] = {
@@ -79,6 +81,8 @@ const char* const INF_STATUS_TEXT[INF_STATUS_COUNT] = {
   "the stream holds less text than the member's ISIZE",
   "compressed bytes behind the end of the stream",
   "CRC32 of the text differs from the member's",
+  "a final block inside a segment that does not end its member",
+  "the segment ends its member, its bits end in front of a final block",
 };
 
 constexpr uint32_t INF_RING = 32768, INF_RMASK = INF_RING - 1;
@@ -309,21 +313,62 @@ inf_flush(InfLds& s, char* out, uint32_t a, uint32_t b)
   INF_FENCE();
 }
 
-// Inflates one member: payload = comp[comp_off, comp_off + comp_len), text to out[0, text_len).  Returns its status.
+// Inflates one stream, text to out[0, text_len), and returns its status.  Two forms, chosen at compile time:
+//   a member (SEG false)   the payload is the BYTES comp[start, start + length), it has no history and ends with its final
+//                          block; at most 64 KiB of text (the host checks that)
+//   a segment (SEG true)   start and length are BITS, comp_bit and n_bits below: a run of whole blocks out of the middle of a serial stream (include/grpath_ingest.h:
+//                          grp_gzip_inflate): it starts at BIT comp_bit, which need not lie on a byte; the dict_len <= 32768
+//                          bytes of text in front of it are put into the ring in front of text position 0, and a distance
+//                          may reach p + dict_len back; it ends at the block boundary where exactly n_bits are consumed —
+//                          behind a final block if and only if seg_flags says that it ends its member.  A stored block
+//                          aligns to a byte of the FILE, so the padding and the block's address come from the absolute
+//                          bit position comp_bit + n_bits - avail.  text_len is any 32-bit number.
+template <bool SEG>
 INF_FN uint32_t
-inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len, char* out, uint32_t text_len)
+inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, const uint8_t* dict, uint32_t dict_len, uint32_t seg_flags, char* out, uint32_t text_len)
 {
+  const uint64_t comp_bit = start, n_bits = length;    // (a segment's)
+  const uint64_t comp_off = SEG ? start >> 3 : start;  // a member's payload; a segment's first byte
+  const uint32_t comp_len = SEG ? 0u : (uint32_t)length;
   const InfHuff lit{ s.lit_fast, s.lit_sorted, s.lit_count, INF_LBITS };
   const InfHuff dist{ s.dist_fast, s.dist_sorted, s.dist_count, INF_DBITS };
   const InfHuff cl{ s.cl_fast, s.cl_sorted, s.cl_count, INF_CBITS };
   INF_READER_LV;
   InfReader rd;
   rd.words = reinterpret_cast<const uint32_t*>(comp);
-  rd.lo = (uint32_t)(comp_off >> 2);
-  rd.hi = (uint32_t)((comp_off + comp_len + 3) >> 2);
-  rd.avail = (int64_t)comp_len * 8;
   rd.failed = false;
-  INF_SEEK(rd, s, comp_off);
+  if constexpr (SEG) {
+    rd.lo = (uint32_t)(comp_bit >> 5);
+    rd.hi = (uint32_t)((comp_bit + n_bits + 31) >> 5);
+    rd.avail = (int64_t)n_bits;
+    INF_SEEK(rd, s, comp_off);
+    rd.bb >>= (int)(comp_bit & 7); // (the seek leaves at least 8 bits)
+    rd.nb -= (int)(comp_bit & 7);
+    // the history: ring position (q - dict_len) & INF_RMASK for its byte q, as if it were text [-dict_len, 0)
+    if (((dict_len | (uint32_t)(uintptr_t)dict) & 3u) == 0) {
+      INF_LANES
+      {
+        uint32_t* r4 = reinterpret_cast<uint32_t*>(s.ring);
+        const uint32_t* d4 = reinterpret_cast<const uint32_t*>(dict);
+        for (uint32_t j = (uint32_t)lane; j < dict_len / 4; j += 64) {
+          r4[((INF_RING - dict_len) / 4 + j) & (INF_RMASK / 4)] = d4[j];
+        }
+      }
+    } else {
+      INF_LANES
+      {
+        for (uint32_t j = (uint32_t)lane; j < dict_len; j += 64) {
+          s.ring[(INF_RING - dict_len + j) & INF_RMASK] = dict[j];
+        }
+      }
+    }
+    INF_FENCE();
+  } else {
+    rd.lo = (uint32_t)(comp_off >> 2);
+    rd.hi = (uint32_t)((comp_off + comp_len + 3) >> 2);
+    rd.avail = (int64_t)comp_len * 8;
+    INF_SEEK(rd, s, comp_off);
+  }
   uint32_t p = 0, flushed = 0; // text produced, text that has left the ring
 
   for (;;) { // a block per iteration: its header consumes three bits
@@ -336,7 +381,11 @@ inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len,
       return INF_BAD_BLOCK_TYPE;
     }
     if (type == 0) {
-      (void)inf_take(rd, (int)(rd.avail & 7)); // to the byte boundary (the payload starts on one)
+      if constexpr (SEG) {
+        (void)inf_take(rd, (int)((0 - (comp_bit + n_bits - (uint64_t)rd.avail)) & 7)); // to the byte boundary of the file
+      } else {
+        (void)inf_take(rd, (int)(rd.avail & 7)); // to the byte boundary (the payload starts on one)
+      }
       INF_REFILL(rd, s);
       const uint32_t len = inf_take(rd, 16), nlen = inf_take(rd, 16);
       if (rd.failed) {
@@ -351,7 +400,7 @@ inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len,
       if (len > text_len - p) {
         return INF_TEXT_TOO_LONG;
       }
-      uint64_t at = comp_off + comp_len - (uint64_t)(rd.avail >> 3); // the block's bytes inside comp
+      uint64_t at = SEG ? (comp_bit + n_bits - (uint64_t)rd.avail) >> 3 : comp_off + comp_len - (uint64_t)(rd.avail >> 3); // the block's bytes inside comp
       rd.avail -= (int64_t)len * 8;
       for (uint32_t left = len; left != 0;) { // every piece produces text
         const uint32_t piece = left < INF_PIECE ? left : INF_PIECE;
@@ -516,7 +565,7 @@ inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len,
           if (rd.failed) {
             return INF_INPUT_ENDS;
           }
-          if (d > p) { // BGZF members share no history
+          if (SEG ? (d > p && d - p > dict_len) : d > p) { // BGZF members share no history, a segment has dict_len bytes of it
             return INF_DIST_TOO_FAR;
           }
           if (len > text_len - p) {
@@ -543,20 +592,47 @@ inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len,
         }
       }
     }
-    if (last) {
-      break;
+    if constexpr (SEG) {
+      if (last) {
+        if (!(seg_flags & 1u)) {
+          return INF_FINAL_INSIDE;
+        }
+        break;
+      }
+      if (rd.avail == 0) { // the block boundary the segment ends at
+        if (seg_flags & 1u) {
+          return INF_NO_FINAL;
+        }
+        break;
+      }
+    } else {
+      if (last) {
+        break;
+      }
     }
   }
   if (p != text_len) {
     return INF_TEXT_TOO_SHORT;
   }
-  if (rd.avail >= 8) {
+  if (SEG ? rd.avail != 0 : rd.avail >= 8) {
     return INF_BYTES_BEHIND_END;
   }
   if (p != flushed) {
     inf_flush(s, out, flushed, p);
   }
   return INF_OK;
+}
+
+INF_FN uint32_t
+inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len, char* out, uint32_t text_len)
+{
+  return inf_stream<false>(s, comp, comp_off, comp_len, nullptr, 0, 0, out, text_len);
+}
+
+INF_FN uint32_t
+inf_segment(InfLds& s, const uint8_t* comp, const uint8_t* dict, const grp_gzip_segment& g, char* out)
+{
+  return inf_stream<true>(s, comp, g.comp_bit, g.n_bits, dict + g.dict_off, g.dict_len, g.flags, out, g.text_len);
 }
 
 // ---- CRC32 (the gzip polynomial, reflected: 0xedb88320) of a member's text by one wave --------------------------------
@@ -658,6 +734,35 @@ k_bgzf_crc(const grp_bgzf_block* __restrict__ blocks, const uint64_t* __restrict
   }
   const uint32_t c = crc_member(s, tables, text + toff[i], blocks[i].text_len);
   if (threadIdx.x == 0 && c != blocks[i].crc32) {
+    status[i] = INF_CRC_MISMATCH;
+  }
+}
+
+// the segment forms: one workgroup of one wave per segment of a serial stream
+__global__ void __launch_bounds__(64)
+k_gzip_inflate(const uint8_t* __restrict__ comp, const uint8_t* __restrict__ dict, const grp_gzip_segment* __restrict__ segs, const uint64_t* __restrict__ toff, uint32_t n_segs, char* __restrict__ text, uint32_t* __restrict__ status)
+{
+  __shared__ InfLds s;
+  const uint32_t i = blockIdx.x;
+  if (i >= n_segs) {
+    return;
+  }
+  const uint32_t st = inf_segment(s, comp, dict, segs[i], text + toff[i]);
+  if (threadIdx.x == 0) {
+    status[i] = st;
+  }
+}
+
+__global__ void __launch_bounds__(64)
+k_gzip_crc(const grp_gzip_segment* __restrict__ segs, const uint64_t* __restrict__ toff, uint32_t n_segs, const char* __restrict__ text, const uint32_t* __restrict__ tables, uint32_t* __restrict__ status)
+{
+  __shared__ CrcLds s;
+  const uint32_t i = blockIdx.x;
+  if (i >= n_segs || status[i] != INF_OK) {
+    return;
+  }
+  const uint32_t c = crc_member(s, tables, text + toff[i], segs[i].text_len);
+  if (threadIdx.x == 0 && c != segs[i].crc32) {
     status[i] = INF_CRC_MISMATCH;
   }
 }
@@ -804,6 +909,129 @@ grp_debug_bgzf_stats(const grp_ctx* c, uint64_t out[4])
   out[1] = c->bgzf.n_comp;
   out[2] = c->bgzf.n_text;
   out[3] = (uint64_t)c->bgzf.kernel_us;
+  return GRP_OK;
+}
+
+extern "C" int
+grp_gzip_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg)
+{
+  if (!c) {
+    return GRP_ERR_INVALID;
+  }
+  if (bad_seg) {
+    *bad_seg = UINT32_MAX;
+  }
+  if ((!comp && n_comp) || (!dict && n_dict) || (!segs && n_segs) || n_comp > (1ull << 32) || n_dict > (1ull << 32) || n_segs > MAX_GRID_WGS) {
+    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: bad argument (at most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 segments per call)");
+  }
+  // the table is checked before anything is launched
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_segs; ++i) {
+    const grp_gzip_segment& g = segs[i];
+    const char* why = g.comp_bit > n_comp * 8 || g.n_bits > n_comp * 8 - g.comp_bit ? "its bits do not lie inside the compressed bytes"
+                      : g.dict_len > INF_RING                                        ? "a history of more than 32768 bytes"
+                      : g.dict_off > n_dict || g.dict_len > n_dict - g.dict_off      ? "its history does not lie inside the histories"
+                      : g.flags & ~GRP_GZIP_SEG_FINAL                                ? "an unknown flag"
+                      : g.text_len > 0xffff0000u                                     ? "more than 4 GiB - 64 KiB of text"
+                                                                                     : nullptr;
+    if (why) {
+      if (bad_seg) {
+        *bad_seg = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u: %s (bits [%llu, +%llu) of %llu bytes, history [%llu, +%u) of %llu, text %u, flags %u)", i, why, (unsigned long long)g.comp_bit,
+                     (unsigned long long)g.n_bits, (unsigned long long)n_comp, (unsigned long long)g.dict_off, g.dict_len, (unsigned long long)n_dict, g.text_len, g.flags);
+    }
+    total += g.text_len;
+  }
+  if (total > text_cap || (total && !text_out)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: the segments hold %llu bytes of text, the caller's buffer %llu", (unsigned long long)total, (unsigned long long)text_cap);
+  }
+  if (n_segs == 0) {
+    return GRP_OK;
+  }
+  auto& gp = c->gzip;
+  auto& bp = c->bgzf; // (the CRC32 tables are shared)
+  hipStream_t st = c->stream2;
+  if (!bp.d_tab.p) {
+    std::vector<uint32_t> tab(4 * 256 + 32);
+    crc_tables(tab.data());
+    HIP_TRY(c, bp.d_tab.reset(tab.size()));
+    HIP_TRY(c, hipMemcpy(bp.d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, bp.ev0.create(hipEventDefault));
+    HIP_TRY(c, bp.ev1.create(hipEventDefault));
+  }
+  if (!gp.ev0.e) {
+    HIP_TRY(c, gp.ev0.create(hipEventDefault));
+    HIP_TRY(c, gp.ev1.create(hipEventDefault));
+  }
+  // grown, never shrunk; the kernel reads whole words: 8 bytes of padding behind the compressed bytes and the histories
+  HIP_TRY(c, gp.d_comp.ensure(n_comp + 8));
+  HIP_TRY(c, gp.d_dict.ensure(n_dict + 8));
+  HIP_TRY(c, gp.d_text.ensure(total + 8));
+  HIP_TRY(c, gp.d_segs.ensure(n_segs));
+  HIP_TRY(c, gp.d_toff.ensure(n_segs));
+  HIP_TRY(c, gp.d_status.ensure(n_segs));
+  if (gp.h_segs.cap < n_segs) {
+    const uint64_t cap = (uint64_t)n_segs + n_segs / 4 + 64;
+    HIP_TRY(c, gp.h_segs.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, gp.h_toff.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, gp.h_status.reset(cap, hipHostMallocDefault));
+  }
+  memcpy(gp.h_segs.p, segs, (size_t)n_segs * sizeof(grp_gzip_segment));
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n_segs; ++i) {
+    gp.h_toff.p[i] = off;
+    off += segs[i].text_len;
+  }
+  if (n_comp) {
+    HIP_TRY(c, hipMemcpyAsync(gp.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemsetAsync(gp.d_comp + n_comp, 0, 8, st));
+  if (n_dict) {
+    HIP_TRY(c, hipMemcpyAsync(gp.d_dict, dict, n_dict, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(gp.d_segs, gp.h_segs.p, (size_t)n_segs * sizeof(grp_gzip_segment), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(gp.d_toff, gp.h_toff.p, (size_t)n_segs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(gp.ev0, st));
+  k_gzip_inflate<<<n_segs, 64, 0, st>>>(gp.d_comp, gp.d_dict, gp.d_segs, gp.d_toff, n_segs, reinterpret_cast<char*>(gp.d_text.p), gp.d_status);
+  k_gzip_crc<<<n_segs, 64, 0, st>>>(gp.d_segs, gp.d_toff, n_segs, reinterpret_cast<const char*>(gp.d_text.p), bp.d_tab, gp.d_status);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(gp.ev1, st));
+  HIP_TRY(c, hipMemcpyAsync(gp.h_status.p, gp.d_status, (size_t)n_segs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (total) {
+    HIP_TRY(c, hipMemcpyAsync(text_out, gp.d_text, total, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, gp.ev0, gp.ev1) == hipSuccess) {
+    gp.kernel_us += (double)ms * 1000.0;
+  }
+  gp.n_segs += n_segs;
+  gp.n_comp += n_comp;
+  gp.n_text += total;
+  for (uint32_t i = 0; i < n_segs; ++i) {
+    const uint32_t s = gp.h_status.p[i];
+    if (s != INF_OK) {
+      if (bad_seg) {
+        *bad_seg = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u is not %llu bits of valid DEFLATE blocks that hold %u bytes of text with CRC32 %08x: %s", i, (unsigned long long)segs[i].n_bits, segs[i].text_len, segs[i].crc32,
+                     s < INF_STATUS_COUNT ? INF_STATUS_TEXT[s] : "unknown status");
+    }
+  }
+  return GRP_OK;
+}
+
+extern "C" int
+grp_debug_gzip_stats(const grp_ctx* c, uint64_t out[4])
+{
+  if (!c || !out) {
+    return GRP_ERR_INVALID;
+  }
+  out[0] = c->gzip.n_segs;
+  out[1] = c->gzip.n_comp;
+  out[2] = c->gzip.n_text;
+  out[3] = (uint64_t)c->gzip.kernel_us;
   return GRP_OK;
 }
 #endif

@@ -317,6 +317,20 @@ struct grp_ctx : CtxStreams
     uint64_t n_blocks = 0, n_comp = 0, n_text = 0; // grp_debug_bgzf_stats
     double kernel_us = 0.0;
   } bgzf;
+  // grp_gzip_inflate: the same for the segments of a serial stream, with their histories
+  struct GzipPool
+  {
+    DevBuf<uint8_t> d_comp, d_dict, d_text;
+    DevBuf<grp_gzip_segment> d_segs;
+    DevBuf<uint64_t> d_toff;
+    DevBuf<uint32_t> d_status;
+    HostBuf<grp_gzip_segment> h_segs; // page-locked staging
+    HostBuf<uint64_t> h_toff;
+    HostBuf<uint32_t> h_status;
+    Event ev0, ev1; // around the two kernels
+    uint64_t n_segs = 0, n_comp = 0, n_text = 0; // grp_debug_gzip_stats
+    double kernel_us = 0.0;
+  } gzip;
   const char* reg_text = nullptr; // the caller's text buffer, page-locked by grp_fastq_pin
   size_t reg_bytes = 0;
   uint32_t timing_mask = (1u << GRP_K_FILL) | (1u << GRP_K_RANK) | (1u << GRP_K_QUERY) | (1u << GRP_K_DECIDE) | (1u << GRP_K_QUERY_LAT) | (1u << GRP_K_VERIFY) | (1u << GRP_K_BATCH);

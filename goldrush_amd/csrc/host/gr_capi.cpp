@@ -7,6 +7,7 @@
 #include <sstream>
 #include "gr_tiles.hpp"
 #include "gr_fastq.hpp"
+#include "gr_gzidx.hpp"
 
 #include <cstddef>
 #include <cstring>
@@ -286,6 +287,83 @@ gr_input_read(const char* path, uint64_t request_bytes, char* dst, uint64_t cap)
     got += k;
   }
   return got;
+}
+
+struct gr_gzidx
+{
+  std::unique_ptr<gr::GzIndexReader> rd;
+  std::unique_ptr<gr::GzIndex> idx; // the complete index, else rd->partial()
+  uint64_t n_text = 0;
+  const gr::GzIndex* get() const { return idx ? idx.get() : rd->partial(); }
+};
+
+gr_gzidx*
+gr_gzidx_build(const char* path, uint64_t span, uint64_t max_bytes, uint64_t stop_after, char* text_out, uint64_t text_cap)
+{
+  std::unique_ptr<gr_gzidx> h(new (std::nothrow) gr_gzidx);
+  if (!h) {
+    return nullptr;
+  }
+  h->rd.reset(new gr::GzIndexReader(path ? path : "", span, max_bytes));
+  if (!h->rd->ok()) {
+    return nullptr;
+  }
+  std::vector<char> piece(size_t(1) << 16);
+  for (;;) {
+    if (stop_after && h->n_text >= stop_after) {
+      break;
+    }
+    const bool direct = text_out && h->n_text < text_cap;
+    const size_t k = direct ? h->rd->read(text_out + h->n_text, (size_t)std::min<uint64_t>(text_cap - h->n_text, piece.size())) : h->rd->read(piece.data(), piece.size());
+    if (k == 0) {
+      break;
+    }
+    h->n_text += k;
+  }
+  h->idx = h->rd->take();
+  return h.release();
+}
+
+void
+gr_gzidx_info(const gr_gzidx* h, uint64_t out[8])
+{
+  const gr::GzIndex* ix = h->get();
+  out[0] = h->idx != nullptr;
+  out[1] = ix ? ix->segs.size() : 0;
+  out[2] = h->n_text;
+  out[3] = ix ? ix->bytes() : 0;
+  out[4] = h->rd->dropped() && !h->idx;
+  out[5] = h->rd->failed();
+  out[6] = ix ? ix->max_text : 0;
+  out[7] = ix ? ix->file_size : 0;
+}
+
+int
+gr_gzidx_segment(const gr_gzidx* h, uint64_t i, grp_gzip_segment* seg, unsigned char* dict)
+{
+  const gr::GzIndex* ix = h->get();
+  if (!ix || i >= ix->segs.size() || !seg) {
+    return -1;
+  }
+  const gr::GzSegment& g = ix->segs[(size_t)i];
+  *seg = grp_gzip_segment{ g.comp_bit, g.n_bits, 0, g.dict_len, g.text_len, g.crc32, g.flags };
+  if (dict && g.dict_len) {
+    std::memcpy(dict, ix->dict(g), g.dict_len);
+  }
+  return 0;
+}
+
+int
+gr_gzidx_matches(const gr_gzidx* h, const char* path)
+{
+  const gr::GzIndex* ix = h->get();
+  return ix && path && ix->matches(path) ? 1 : 0;
+}
+
+void
+gr_gzidx_free(gr_gzidx* h)
+{
+  delete h;
 }
 
 } // extern "C"

@@ -101,5 +101,8 @@ main(int argc, char** argv)
   ext.bgzf_inflate = [](void* c, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n, char* text, uint64_t cap, uint32_t* bad) {
     return grp_bgzf_inflate(static_cast<grp_ctx*>(c), comp, n_comp, blocks, n, text, cap, bad);
   };
+  ext.gzip_inflate = [](void* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n, char* text, uint64_t cap, uint32_t* bad) {
+    return grp_gzip_inflate(static_cast<grp_ctx*>(c), comp, n_comp, dict, n_dict, segs, n, text, cap, bad);
+  };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

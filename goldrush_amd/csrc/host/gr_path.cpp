@@ -8,6 +8,7 @@
 #include "gr_bgzf.hpp"
 #include "gr_classifier.hpp"
 #include "gr_fastq.hpp"
+#include "gr_gzidx.hpp"
 #include "gr_opts.hpp"
 #include "gr_params.hpp"
 
@@ -84,6 +85,9 @@ struct PathRun
   bool merge_rccl = false;   // ... merged by RCCL inside the engine (else staged through host memory and /dev/shm)
   void* shm = nullptr;       // gr_shm_allgather handle
   int32_t device = -1;       // HIP device ordinal of this rank
+  // a plain gzip input: the restart points the first complete pass over it wrote down (gr_gzidx.hpp); the passes behind
+  // it inflate its segments on the device
+  std::shared_ptr<GzIndex> gzidx;
 
   int fail_engine(const char* what)
   {
@@ -216,6 +220,12 @@ private:
 // them into the slot's text before that text is handed to fastq_prefetch / fastq_parse.  Everything behind that — the
 // carried tail, parse, pack, stats — does not know.  Plain gzip is one serial stream and stays with zlib; from a member
 // in mid-file that is not BGZF on (bgzip output followed by gzip output) zlib reads the rest.
+// A file that is gzip from its first byte and not taken by the BGZF form (grp_engine_ext::gzip_inflate; GRP_GZIP_INDEX=off:
+// no): the first pass that reads it to its end does so through GzIndexReader — zlib as before, on the reader thread — and
+// leaves the index of its restart points in the run; in every pass behind it the reader thread preads whole SEGMENTS
+// into a slot until its text, its compressed bytes, its histories or its table is full, and the consumer has the engine
+// inflate them, exactly like the members of a BGZF file.  A pass that ends early (the Phred median) leaves no index, a
+// file that changed between two passes drops it, an index with a segment larger than a slot is not used.
 class GpuSource : public RecordSource
 {
 public:
@@ -242,6 +252,37 @@ public:
         }
       }
     }
+    if (!bgzf_ && run_.ext.gzip_inflate && gzip_index_enabled()) {
+      if (run_.gzidx && !run_.gzidx->matches(run.opt.input)) {
+        run_.gzidx.reset(); // the file was written since: this pass builds a new one
+      }
+      const int fd = ::open(run.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
+      struct stat st;
+      unsigned char magic[2] = { 0, 0 };
+      const bool gz = fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+      if (gz && run_.gzidx) {
+        if (run_.gzidx->max_text <= chunk_) { // (else the whole pass goes through zlib)
+          gzseg_ = true;
+          zfd_ = fd;
+        }
+      } else if (gz) {
+        gzbuild_.reset(new GzIndexReader(run.opt.input, gzip_index_span(), gzip_index_max_bytes()));
+        if (!gzbuild_->ok()) {
+          gzbuild_.reset();
+        }
+      }
+      if (fd >= 0 && zfd_ != fd) {
+        ::close(fd);
+      }
+    }
+    if (gzseg_) {
+      comp_cap_ = std::max<size_t>(chunk_ / 2, (size_t)run_.gzidx->max_comp + 8);
+      dict_cap_ = chunk_ / 8 + 32768; // (32 KiB per 256 KiB of text at the default span)
+      tab_cap_ = std::max<size_t>(chunk_ / 4096, 64);
+      for (Slot& sl : slot_) {
+        sl.segs.resize(tab_cap_);
+      }
+    }
     if (bgzf_) {
       chunk_ = std::max<size_t>(chunk_, BGZF_MAX_TEXT); // a tiny GRP_INGEST_CHUNK still holds one member
       comp_cap_ = std::max<size_t>(chunk_ / 2, BGZF_MAX_MEMBER);
@@ -254,7 +295,7 @@ public:
       chunk_ = std::min<size_t>(chunk_, std::max<size_t>((size_t)in_.plain_size() + 1, size_t(1) << 16));
     }
     front_ = std::min<size_t>(std::max<size_t>(chunk_ / 16, 4096), (size_t)GRP_FASTQ_PREFETCH_FRONT); // (what a prefetched body may have in front of it, grpath_ingest.h)
-    buf_.resize((size_t)kSlots * (front_ + chunk_ + comp_cap_)); // (the compressed bytes of the slots behind their texts: one page-locked buffer)
+    buf_.resize((size_t)kSlots * (front_ + chunk_ + comp_cap_ + dict_cap_)); // (the compressed bytes of the slots behind their texts, the histories behind those: one page-locked buffer)
     const char* pin_min = getenv("GRP_PIN_MIN_BYTES"); // tests: page-lock small buffers too
     if (run_.vt.fastq_pin && run_.vt.fastq_unpin && buf_.size() >= (pin_min ? (size_t)atoll(pin_min) : (size_t(8) << 20))) {
       pinned_ = run_.vt.fastq_pin(run_.ctx, buf_.data(), buf_.size()) == GRP_OK;
@@ -276,7 +317,8 @@ public:
     }
     if (getenv("GRP_TRACE_INGEST")) {
       std::cerr << "GRP_TRACE_INGEST source: " << n_pre_[0] << " chunks, next chunk not ready at " << n_pre_[1] << ", uploads started ahead " << n_pre_[2] << "; seconds waiting for the reader " << t_tr_[0]
-                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << n_bgzf_blocks_ << std::endl;
+                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << n_bgzf_blocks_
+                << ", gzip segments inflated on the device " << n_gzip_segs_ << std::endl;
     }
     if (zfd_ >= 0) {
       ::close(zfd_);
@@ -458,18 +500,33 @@ private:
     size_t n_blocks = 0, comp_n = 0;
     uint64_t comp_file_off = 0;         // where the slot's compressed bytes begin in the file
     bool inflated = false, bad = false; // consumer's
+    // a gzip index: the n bytes are the text of these segments (comp_bit inside the slot's compressed bytes, dict_off inside its histories)
+    std::vector<grp_gzip_segment> segs;
+    size_t n_segs = 0, dict_n = 0;
   };
+  unsigned char* slot_dict(int i) { return reinterpret_cast<unsigned char*>(buf_.data()) + (size_t)kSlots * (front_ + chunk_ + comp_cap_) + (size_t)i * dict_cap_; }
   char* slot_data(int i) { return buf_.data() + (size_t)i * (front_ + chunk_) + front_; }
   unsigned char* slot_comp(int i) { return reinterpret_cast<unsigned char*>(buf_.data()) + (size_t)kSlots * (front_ + chunk_) + (size_t)i * comp_cap_; }
   // the slot's members inflated into its text (once); false: the engine refused one of them
   bool inflate_slot(int j)
   {
     Slot& sl = slot_[j];
-    if (sl.n_blocks == 0 || sl.inflated) {
+    if ((sl.n_blocks == 0 && sl.n_segs == 0) || sl.inflated) {
       return !sl.bad;
     }
     sl.inflated = true;
     uint32_t bad = UINT32_MAX;
+    if (sl.n_segs != 0) {
+      if (run_.ext.gzip_inflate(run_.ctx, slot_comp(j), sl.comp_n, slot_dict(j), sl.dict_n, sl.segs.data(), (uint32_t)sl.n_segs, slot_data(j), chunk_, &bad) != GRP_OK) {
+        sl.bad = true;
+        const uint64_t bit = sl.comp_file_off * 8 + (bad < sl.n_segs ? sl.segs[bad].comp_bit : 0);
+        note_input_failure("reading " + run_.opt.input + " failed: gzip segment " + (bad < sl.n_segs ? "" : "in the chunk ") + "at byte " + std::to_string(bit >> 3) + " (bit " + std::to_string(bit & 7) + "): " +
+                           (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
+        return false;
+      }
+      n_gzip_segs_ += sl.n_segs;
+      return true;
+    }
     if (run_.ext.bgzf_inflate(run_.ctx, slot_comp(j), sl.comp_n, sl.blocks.data(), (uint32_t)sl.n_blocks, slot_data(j), chunk_, &bad) != GRP_OK) {
       sl.bad = true;
       uint64_t at = sl.comp_file_off; // the members of a slot follow each other
@@ -570,6 +627,57 @@ private:
       }
     }
   }
+  // The reader's side of an indexed gzip file: whole segments into slot i until its text (chunk_), its compressed bytes
+  // (comp_cap_), its histories (dict_cap_) or its table (tab_cap_) is full; the compressed bytes of a slot are one range
+  // of the file (with the trailers and headers between two members in it).  Returns the bytes of text they hold.
+  size_t read_gzseg(int i, bool& eof)
+  {
+    const GzIndex& ix = *run_.gzidx;
+    Slot& sl = slot_[i];
+    if (gz_next_ >= ix.segs.size()) {
+      eof = true;
+      return 0;
+    }
+    const uint64_t byte0 = ix.segs[gz_next_].first_byte();
+    uint64_t end = byte0;
+    size_t text = 0, ns = 0, nd = 0;
+    while (gz_next_ + ns < ix.segs.size() && ns < tab_cap_) {
+      const GzSegment& g = ix.segs[gz_next_ + ns];
+      if (text + g.text_len > chunk_ || g.end_byte() - byte0 > comp_cap_ || nd + g.dict_len > dict_cap_) {
+        break; // (never the slot's first: the constructor has seen to that)
+      }
+      sl.segs[ns] = grp_gzip_segment{ g.comp_bit - byte0 * 8, g.n_bits, nd, g.dict_len, g.text_len, g.crc32, g.flags };
+      if (g.dict_len) {
+        memcpy(slot_dict(i) + nd, ix.dict(g), g.dict_len);
+      }
+      nd = (nd + g.dict_len + 3) & ~size_t(3);
+      text += g.text_len;
+      end = g.end_byte();
+      ++ns;
+    }
+    unsigned char* comp = slot_comp(i);
+    const size_t want = (size_t)(end - byte0);
+    size_t k = 0;
+    while (k < want) {
+      const ssize_t r = pread(zfd_, comp + k, want - k, (off_t)(byte0 + k));
+      if (r < 0 && errno == EINTR) {
+        continue;
+      }
+      if (r <= 0) {
+        note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(byte0 + k) + ": " + (r < 0 ? strerror(errno) : "the file ends in front of a segment of its index (it was written during the run)"));
+        eof = true;
+        return 0;
+      }
+      k += (size_t)r;
+    }
+    sl.comp_file_off = byte0;
+    sl.comp_n = want;
+    sl.n_segs = ns;
+    sl.dict_n = std::min(nd, dict_cap_);
+    gz_next_ += ns;
+    eof = gz_next_ == ix.segs.size();
+    return text;
+  }
   void read_loop()
   {
     uint64_t off = 0;
@@ -585,18 +693,24 @@ private:
       bool eof = false;
       slot_[i].n_blocks = slot_[i].comp_n = 0; // (a FREE slot is the reader's)
       slot_[i].inflated = slot_[i].bad = false;
+      slot_[i].n_segs = slot_[i].dict_n = 0;
       if (bgzf_ && !ztail_) {
         got = read_bgzf(i, eof);
+      } else if (gzseg_) {
+        got = read_gzseg(i, eof);
       }
-      if (got == 0 && !eof && (!bgzf_ || ztail_)) {
+      if (got == 0 && !eof && !gzseg_ && (!bgzf_ || ztail_)) {
         slot_[i].n_blocks = slot_[i].comp_n = 0; // (empty members in front of the part zlib reads)
         InputFile& in = ztail_ ? *ztail_ : in_;
         while (!eof && got < chunk_) {
-          const size_t k = in.read(slot_data(i) + got, chunk_ - got);
+          const size_t k = gzbuild_ ? gzbuild_->read(slot_data(i) + got, chunk_ - got) : in.read(slot_data(i) + got, chunk_ - got);
           if (k == 0) {
             eof = true;
           }
           got += k;
+        }
+        if (eof && gzbuild_ && gzbuild_->complete()) {
+          run_.gzidx = gzbuild_->take(); // (read by the next pass's source, which begins behind this thread's end)
         }
       }
       {
@@ -636,6 +750,11 @@ private:
   size_t comp_cap_ = 0, tab_cap_ = 0;
   std::unique_ptr<InputFile> ztail_;
   uint64_t n_bgzf_blocks_ = 0; // (developer trace)
+  // a plain gzip file: this pass builds the index (zlib on the reader thread), or it reads the segments of the run's index
+  std::unique_ptr<GzIndexReader> gzbuild_;
+  bool gzseg_ = false;
+  size_t gz_next_ = 0, dict_cap_ = 0;
+  uint64_t n_gzip_segs_ = 0;
   bool pinned_ = false;
   std::thread reader_;
   std::mutex mu_;
@@ -1191,6 +1310,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   run.vt = *vt;
   if (ext && ext->struct_size >= offsetof(grp_engine_ext, bgzf_inflate) + sizeof(ext->bgzf_inflate)) {
     run.ext.bgzf_inflate = ext->bgzf_inflate;
+  }
+  if (ext && ext->struct_size >= offsetof(grp_engine_ext, gzip_inflate) + sizeof(ext->gzip_inflate)) {
+    run.ext.gzip_inflate = ext->gzip_inflate;
   }
   Opts& opt = run.opt;
   // Several GPUs of one node: one process per GPU (GRP_WORLD / GRP_RANK, or the launcher's

@@ -104,8 +104,11 @@ class grp_engine_vt(C.Structure):
 BGZF_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32))
 
 
+GZIP_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32))
+
+
 class grp_engine_ext(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN)]
+    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN)]
 
 
 COMMIT_FN = C.CFUNCTYPE(C.c_double, _vp, C.POINTER(gr_commit))
@@ -150,6 +153,11 @@ SIGNATURES = {
     "gr_path_main_ext": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(grp_engine_vt), C.POINTER(grp_engine_ext)]),
     "gr_bgzf_scan": (C.c_size_t, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gr_input_read": (C.c_uint64, [C.c_char_p, C.c_uint64, _vp, C.c_uint64]),
+    "gr_gzidx_build": (_vp, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    "gr_gzidx_info": (None, [_vp, _vp]),
+    "gr_gzidx_segment": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
+    "gr_gzidx_matches": (C.c_int, [_vp, C.c_char_p]),
+    "gr_gzidx_free": (None, [_vp]),
 }
 
 _lib = None
@@ -268,12 +276,41 @@ def bgzf_scan(buf: bytes, cap: int = 1 << 16):
     return [(int(b["comp_off"]), int(b["comp_len"]), int(b["text_len"]), int(b["crc32"])) for b in blocks[:n]], consumed.value, why.value
 
 
+def gzip_index(path, span: int = 256 << 10, max_bytes: int = 16 << 30, stop_after: int = 0, text_cap: int = 0) -> dict:
+    """gr_gzidx_build: the host program's first pass over a plain gzip file.  Returns complete / dropped / failed, the
+    bytes of text read (and the text itself up to text_cap), the bytes the index holds, whether the file still matches,
+    and the segments: dicts of comp_bit (from the file's first bit), n_bits, dict (the history), text_len, crc32, flags."""
+    lib = load()
+    text = np.zeros(max(text_cap, 1), dtype=np.uint8)
+    h = lib.gr_gzidx_build(os.fsencode(str(path)), span, max_bytes, stop_after, _p(text) if text_cap else None, text_cap)
+    if not h:
+        raise OSError("gr_gzidx_build: cannot open %s" % path)
+    try:
+        info = np.zeros(8, dtype=np.uint64)
+        lib.gr_gzidx_info(h, _p(info))
+        segs = []
+        seg = np.zeros(1, dtype=native.gzip_segment_dtype)
+        hist = np.zeros(32768, dtype=np.uint8)
+        for i in range(int(info[1])):
+            if lib.gr_gzidx_segment(h, i, _p(seg), _p(hist)) != 0:
+                raise RuntimeError("gr_gzidx_segment(%d) failed" % i)
+            g = seg[0]
+            segs.append(dict(comp_bit=int(g["comp_bit"]), n_bits=int(g["n_bits"]), dict=hist[:int(g["dict_len"])].tobytes(), text_len=int(g["text_len"]),
+                             crc32=int(g["crc32"]), flags=int(g["flags"])))
+        return dict(complete=bool(info[0]), segments=segs, n_text=int(info[2]), index_bytes=int(info[3]), dropped=bool(info[4]), failed=bool(info[5]),
+                    max_text=int(info[6]), file_size=int(info[7]), matches=bool(lib.gr_gzidx_matches(h, os.fsencode(str(path)))),
+                    text=text[:min(int(info[2]), text_cap)].tobytes())
+    finally:
+        lib.gr_gzidx_free(h)
+
+
 def hip_engine_ext() -> grp_engine_ext:
     """The second table filled with the symbols of libgrpath_hip.so."""
     lib = native.load()
     ext = grp_engine_ext()
     ext.struct_size = C.sizeof(grp_engine_ext)
     ext.bgzf_inflate = C.cast(lib.grp_bgzf_inflate, BGZF_INFLATE_FN)
+    ext.gzip_inflate = C.cast(lib.grp_gzip_inflate, GZIP_INFLATE_FN)
     return ext
 
 

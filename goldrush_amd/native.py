@@ -131,6 +131,8 @@ SIGNATURES = {
     "grp_debug_locate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp]),
     "grp_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
     "grp_debug_bgzf_stats": (C.c_int, [_vp, _vp]),
+    "grp_gzip_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "grp_debug_gzip_stats": (C.c_int, [_vp, _vp]),
     "grp_dev_hooks": (C.c_int, []),
     "grp_set_timing": (C.c_int, [_vp, C.c_int]),
     "grp_get_kernel_stats": (C.c_int, [_vp, C.POINTER(grp_kernel_stat)]),
@@ -158,6 +160,8 @@ fastq_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off
 
 # grp_bgzf_block (include/grpath_ingest.h): a BGZF member's DEFLATE payload inside the compressed bytes, ISIZE and CRC32 of its trailer
 bgzf_block_dtype = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
+# grp_gzip_segment: a run of whole DEFLATE blocks out of a serial stream, from bit comp_bit on, with dict_len bytes of history
+gzip_segment_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_off", "<u8"), ("dict_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("flags", "<u4")])
 
 # include/grpath_ingest.h
 SIGNATURES.update({
@@ -403,6 +407,33 @@ class Engine:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.grp_debug_bgzf_stats(self._h, _ptr(out)))
         return dict(zip(("blocks", "comp_bytes", "text_bytes", "kernel_us"), (int(v) for v in out)))
+
+    # -- segments of a plain gzip stream inflated on the device (include/grpath_ingest.h)
+    def gzip_inflate(self, comp, dict_bytes, segs, text_cap: "int | None" = None) -> bytes:
+        """grp_gzip_inflate: comp = the compressed bytes, dict_bytes = the histories, segs = gzip_segment_dtype records (or
+        (comp_bit, n_bits, dict_off, dict_len, text_len, crc32, flags) tuples); returns the text.  A refused segment raises
+        GrpError with .bad_seg set."""
+        buf = np.frombuffer(comp, dtype=np.uint8) if len(comp) else np.zeros(1, dtype=np.uint8)
+        dic = np.frombuffer(dict_bytes, dtype=np.uint8) if len(dict_bytes) else np.zeros(1, dtype=np.uint8)
+        if not isinstance(segs, np.ndarray):
+            segs = np.array([tuple(g) for g in segs], dtype=gzip_segment_dtype)
+        segs = np.ascontiguousarray(segs, dtype=gzip_segment_dtype)
+        total = int(segs["text_len"].astype(np.uint64).sum())
+        cap = total if text_cap is None else text_cap
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        bad = C.c_uint32(0xFFFFFFFF)
+        rc = self.lib.grp_gzip_inflate(self._h, _ptr(buf), len(comp), _ptr(dic), len(dict_bytes), _ptr(segs) if len(segs) else None, len(segs), _ptr(out), cap, C.byref(bad))
+        if rc != GRP_OK:
+            e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
+            e.bad_seg = None if bad.value == 0xFFFFFFFF else bad.value
+            raise e
+        return out[:total].tobytes()
+
+    def gzip_stats(self) -> dict:
+        """segments, compressed bytes, text bytes and kernel microseconds of all gzip_inflate calls of this engine"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.grp_debug_gzip_stats(self._h, _ptr(out)))
+        return dict(zip(("segments", "comp_bytes", "text_bytes", "kernel_us"), (int(v) for v in out)))
 
     # -- phase 0 (--ntcard)
     def ntcard_begin(self, sbits: int = 7):

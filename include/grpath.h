@@ -619,6 +619,10 @@ int grp_debug_stream_stats(const grp_ctx* ctx, uint64_t out[8]);
 typedef struct grp_bgzf_block grp_bgzf_block;
 int grp_bgzf_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block);
 int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
+/* ... and the segments of a plain gzip stream (grpath_ingest.h) */
+typedef struct grp_gzip_segment grp_gzip_segment;
+int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
+int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
 
 /* 1: the library was built with GRP_DEV_HOOKS (make DEV=1): the measurement-only prototypes of include/grpath_dev.h are
  * compiled in; 0: the product build (they are not exported) */

@@ -276,6 +276,22 @@ uint64_t gr_input_read(const char* path, uint64_t request_bytes, char* dst, uint
  * that is not BGZF (other flags than FEXTRA, no BC subfield, an ISIZE above 65536: zlib's business) */
 size_t gr_bgzf_scan(const unsigned char* buf, size_t n, grp_bgzf_block* blocks, size_t cap, size_t* consumed, int* why);
 
+/* ---- plain gzip input (csrc/host/gr_gzidx.cpp): the restart points the first pass over a .gz file writes down -------------
+ * gr_gzidx_build reads `path` as the host program's first pass does (zlib, Z_BLOCK), with a point every `span` bytes of
+ * text and the index dropped beyond max_bytes; stop_after != 0: it stops once that much text has come out (the index is
+ * then incomplete, like the Phred pass's).  The text goes to text_out[0, text_cap) if given.  NULL: the file cannot be
+ * opened.  _info: [0] the index is complete, [1] segments, [2] bytes of text read, [3] bytes the index holds,
+ * [4] it was dropped (the cap, bytes behind the last member), [5] the read failed (grp_last_error has no part in this: the
+ * failure is the host program's input failure), [6] the longest segment's text, [7] the file's size.
+ * _segment: segment i with comp_bit counted from the FILE's first bit and dict_off 0; its dict_len bytes of history go
+ * to dict (32768 bytes of room).  _matches: the file at `path` still has the size and time the index was built from. */
+typedef struct gr_gzidx gr_gzidx;
+gr_gzidx* gr_gzidx_build(const char* path, uint64_t span, uint64_t max_bytes, uint64_t stop_after, char* text_out, uint64_t text_cap);
+void gr_gzidx_info(const gr_gzidx* h, uint64_t out[8]);
+int gr_gzidx_segment(const gr_gzidx* h, uint64_t i, grp_gzip_segment* seg, unsigned char* dict);
+int gr_gzidx_matches(const gr_gzidx* h, const char* path);
+void gr_gzidx_free(gr_gzidx* h);
+
 /* ---- optional engine entry points that came after grp_engine_vt was frozen at 48 members: a second table, every member
  * optional (NULL, or a struct_size that ends in front of it: the host takes the path it took without it) */
 typedef struct
@@ -283,6 +299,9 @@ typedef struct
   uint32_t struct_size;
   /* grp_bgzf_inflate: with it, a BGZF-compressed input is inflated on the device (GRP_BGZF=off: through zlib as before) */
   int (*bgzf_inflate)(void* ctx, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block);
+  /* grp_gzip_inflate: with it, the passes over a plain gzip input behind the first inflate the segments of the first
+   * pass's index on the device (GRP_GZIP_INDEX=off: every pass through zlib as before) */
+  int (*gzip_inflate)(void* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
 } grp_engine_ext;
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */

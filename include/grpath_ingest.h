@@ -111,6 +111,39 @@ int grp_bgzf_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const g
 /* blocks, compressed bytes, text bytes, kernel microseconds (HIP events around the two kernels) since grp_create */
 int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
 
+/*
+ * ---- plain gzip FASTQ: segments of a serial stream ---------------------------------------------------------------
+ * An ordinary .gz file is one serial DEFLATE stream (per member) with no block table: only a pass through zlib finds its
+ * block boundaries.  The host's first pass over such a file goes through zlib anyway and writes down exact restart
+ * points in the manner of zlib's zran example (csrc/host/gr_gzidx.hpp): a block boundary with its bit position, the up to
+ * 32 KiB of text in front of it and the CRC32 of the text up to the next point.  Every later pass then has a table of
+ * independent segments, as a BGZF file has a table of members, and the same decoder inflates them one wave per segment.
+ * A segment differs from a member in that it starts at a bit, starts with a history, ends at a block boundary that need
+ * not follow a final block, and may hold any amount of text.
+ */
+struct grp_gzip_segment
+{
+  uint64_t comp_bit;   /* first bit of the segment inside `comp` (bit 0 = LSB of byte 0) */
+  uint64_t n_bits;     /* its length; it ends on a block boundary */
+  uint64_t dict_off;   /* its history inside `dict` */
+  uint32_t dict_len;   /* 0 .. 32768 */
+  uint32_t text_len;
+  uint32_t crc32;      /* of its text_len bytes of text */
+  uint32_t flags;      /* 1: the segment ends with a member's final block */
+}; /* (the typedef is in grpath.h) */
+#define GRP_GZIP_SEG_FINAL 1u
+
+/* Inflate n_segs segments on the device; the text of segment i goes to text_out + sum(text_len[0..i)).  The contract of
+ * grp_bgzf_inflate: synchronous, on the side stream; the table is checked before anything is launched (the bits inside
+ * comp, the history inside dict, dict_len <= 32768, no flag but 1, the sum of the texts <= text_cap: GRP_ERR_INVALID,
+ * *bad_seg = the entry); every segment that is not exactly text_len bytes of valid DEFLATE with that CRC32 — whole blocks
+ * that consume exactly n_bits, the last of them a final block if and only if flag 1 is set, no distance that reaches in
+ * front of the history — is refused: GRP_ERR_INVALID, *bad_seg = the first such segment, the reason in grp_last_error,
+ * text_out unspecified.  At most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 segments per call. */
+int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
+/* segments, compressed bytes, text bytes, kernel microseconds (HIP events around the two kernels) since grp_create */
+int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

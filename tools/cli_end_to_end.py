@@ -16,7 +16,19 @@ The same file BGZF-compressed (a writer of its own: zlib level 1, members of 652
 the rate of the inflate kernels alone (grp_debug_bgzf_stats: text bytes / kernel time, the file's members in calls of one
 ingest chunk of text), and process #1 end to end, three runs each, all kept — this tree on the BGZF file (the device
 inflates), the same with GRP_BGZF=off (zlib), the binary named by CLI_E2E_PARENT on the BGZF file (the parent commit:
-zlib), this tree and the parent on the plain file (the floor, and what the plain path pays)."""
+zlib), this tree and the parent on the plain file (the floor, and what the plain path pays).
+
+  tools/cli_end_to_end.py --gzip <out.json> [reads] [genome]
+
+The same file as ONE gzip member at zlib level 6 (written by up to 16 processes the way pigz -i does: pieces of 64 MiB
+compressed on their own and joined by sync flushes; the blocks are what gzip -6 cuts, 30 to 36 KB of text each).  The
+first pass over it goes through zlib and writes down restart points (csrc/host/gr_gzidx.cpp), the passes behind it inflate
+the segments on the device.  Recorded: the rate of the segment kernels alone (grp_debug_gzip_stats over the segments of
+the file's first GiB of text, in calls of one ingest chunk), the index's size, and process #1 end to end, three runs
+each, all kept, with the program's phase timers and its GRP_TRACE_INGEST lines (one per pass: the seconds the pass waited
+for its reader, the segments the device inflated) — this tree at the default span and at the spans in CLI_E2E_SPANS, this
+tree with GRP_GZIP_INDEX=off, this tree on the plain and the BGZF file, and the binary named by CLI_E2E_PARENT (the parent
+commit) on all three."""
 import json
 import os
 import re
@@ -37,7 +49,12 @@ def run_cli(args, env=None):
     dt = time.perf_counter() - t0
     ins = [float(x) for x in re.findall(r"^in ([0-9.]+)$", r.stderr, re.M)]
     visited = re.findall(r"Visited (\d+) reads", r.stderr)
-    return {"rc": r.returncode, "wall_s": dt, "phase_timers_s": ins, "visited": int(visited[-1]) if visited else None, "stderr_tail": r.stderr[-300:] if r.returncode else ""}
+    res = {"rc": r.returncode, "wall_s": dt, "phase_timers_s": ins, "visited": int(visited[-1]) if visited else None, "stderr_tail": r.stderr[-300:] if r.returncode else ""}
+    trace = [l for l in r.stderr.splitlines() if l.startswith("GRP_TRACE_INGEST source")]
+    if trace:  # one line per pass over the input
+        res["passes"] = [{"waiting_for_reader_s": float(re.search(r"waiting for the reader ([0-9.e+-]+)", l).group(1)), "bgzf_blocks": int(re.search(r"BGZF blocks inflated on the device (\d+)", l).group(1)),
+                          "gzip_segments": int(m.group(1)) if (m := re.search(r"gzip segments inflated on the device (\d+)", l)) else None} for l in trace]
+    return res
 
 
 def _bgzf_piece(job):
@@ -138,7 +155,125 @@ def bgzf_mode(out, fq, n_reads, genome, res):
     os.remove(gz)
 
 
+def _gzip_piece(job):
+    import zlib
+
+    path, off, n, last = job
+    with open(path, "rb") as fh:
+        fh.seek(off)
+        text = fh.read(n)
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    return c.compress(text) + c.flush(zlib.Z_FINISH if last else zlib.Z_SYNC_FLUSH), zlib.crc32(text), len(text)
+
+
+def write_gzip(fq, gz):
+    """one gzip member at level 6: pieces of 64 MiB compressed by up to 16 processes, each ended by a sync flush, the last
+    by the final block; the member's CRC32 is that of the file read once more"""
+    import struct
+    import zlib
+    from multiprocessing import Pool
+
+    size, piece = os.path.getsize(fq), 64 << 20
+    jobs = [(fq, off, piece, off + piece >= size) for off in range(0, size, piece)]
+    with Pool(min(16, len(os.sched_getaffinity(0)))) as pool, open(gz, "wb") as dst:
+        dst.write(b"\x1f\x8b\x08\0\0\0\0\0\0\x03")
+        for blob, _, _ in pool.imap(_gzip_piece, jobs, chunksize=1):
+            dst.write(blob)
+        crc = 0
+        with open(fq, "rb") as fh:
+            while True:
+                buf = fh.read(64 << 20)
+                if not buf:
+                    break
+                crc = zlib.crc32(buf, crc)
+        dst.write(struct.pack("<II", crc, size & 0xffffffff))
+
+
+def gzip_mode(out, fq, n_reads, genome, res):
+    import hashlib
+
+    import numpy as np
+
+    from goldrush_amd import host, native
+
+    tmp = os.path.dirname(fq)
+    gz, bg = fq + ".gz", fq + ".bgzf.gz"
+    t0 = time.perf_counter()
+    write_gzip(fq, gz)
+    res["gzip_bytes"] = os.path.getsize(gz)
+    res["gzip_written_s"] = time.perf_counter() - t0
+    write_bgzf(fq, bg)
+    res["bgzf_bytes"] = os.path.getsize(bg)
+    # the kernels alone: the segments of the first GiB of text at the default span, in calls of one ingest chunk of text
+    span, chunk = 256 << 10, 256 << 20
+    t0 = time.perf_counter()
+    ix = host.gzip_index(gz, span, stop_after=1 << 30)
+    res["index_first_GiB"] = {"span": span, "segments": len(ix["segments"]), "index_bytes": ix["index_bytes"], "text_bytes": sum(g["text_len"] for g in ix["segments"]),
+                              "max_segment_text": ix["max_text"], "built_s_zlib_and_python": time.perf_counter() - t0}
+    eng = native.Engine(22, 3, 1000, 1 << 20, [SEED[:11] + "0" * i + SEED[11:] for i in range(3)])
+    comp_all = np.fromfile(gz, dtype=np.uint8, count=(ix["segments"][-1]["comp_bit"] + ix["segments"][-1]["n_bits"] + 7) // 8 if ix["segments"] else 0)
+    calls, i, t0 = 0, 0, time.perf_counter()
+    segs = ix["segments"]
+    while i < len(segs):
+        j, text = i, 0
+        while j < len(segs) and text + segs[j]["text_len"] <= chunk:
+            text += segs[j]["text_len"]
+            j += 1
+        b0 = segs[i]["comp_bit"] // 8
+        b1 = (segs[j - 1]["comp_bit"] + segs[j - 1]["n_bits"] + 7) // 8
+        hist, table = bytearray(), []
+        for g in segs[i:j]:
+            table.append((g["comp_bit"] - 8 * b0, g["n_bits"], len(hist), len(g["dict"]), g["text_len"], g["crc32"], g["flags"]))
+            hist += g["dict"]
+        eng.gzip_inflate(comp_all[b0:b1], bytes(hist), table)
+        calls += 1
+        i = j
+    st = eng.gzip_stats()
+    eng.close()
+    res["inflate_kernels"] = dict(st, calls=calls, text_GB_per_s=st["text_bytes"] / max(st["kernel_us"], 1) / 1e3, wall_s_with_copies_and_python=time.perf_counter() - t0, bgzf_kernels_text_GB_per_s=8.4,
+                                  fill_pass_needs_text_GB_per_s=29.0)
+    del comp_all, ix, segs
+    base = ["-k22", "-w16", "-t1000", "-u5", "-a1", "-o0.1", "-h3", "-j16", "-P10", "-d5", "-x10", "-s" + SEED, "-g%d" % genome, "-b10", "--verbose"]
+    pdir = os.path.join(tmp, "cli_e2e_out")
+    os.makedirs(pdir, exist_ok=True)
+    parent = os.environ.get("CLI_E2E_PARENT")
+    global CLI
+    this = CLI
+    runs = []
+    if parent:  # (first: how much of its time falls in the passes behind the first bounds the gain)
+        runs += [("parent/gzip_zlib", parent, gz, {}, 3)]
+    runs += [("this_tree/gzip_device", this, gz, {}, 3), ("this_tree/gzip_zlib", this, gz, {"GRP_GZIP_INDEX": "off"}, 3)]
+    runs += [("this_tree/gzip_device_span_%d" % int(v), this, gz, {"GRP_GZIP_SPAN": str(int(v))}, 2) for v in os.environ.get("CLI_E2E_SPANS", "").split(",") if v]
+    runs += [("this_tree/plain", this, fq, {}, 3), ("this_tree/bgzf", this, bg, {}, 3)]
+    if parent:
+        runs += [("parent/plain", parent, fq, {}, 3), ("parent/bgzf", parent, bg, {}, 3)]
+    only = [v for v in os.environ.get("CLI_E2E_ONLY", "").split(",") if v]  # (a second look at some of the runs; the plain file is the reference of the outputs)
+    runs = [r for r in runs if not only or r[0] in only or r[0] == "this_tree/plain"]
+    outputs = {}
+    for name, binary, path, env, times in runs:
+        CLI = binary
+        tag = name.replace("/", "_")
+        many = [run_cli(base + ["-r0.9", "--silver_path", "-M5", "-m20000", "-i", path, "-p", os.path.join(pdir, tag)], dict(env, GRP_TRACE_INGEST="1")) for _ in range(times)]
+        r = min(many, key=lambda x: x["wall_s"])
+        r["wall_s_all"] = [round(x["wall_s"], 3) for x in many]
+        r["phase_timers_s_all"] = [x["phase_timers_s"] for x in many]
+        r["waiting_for_reader_s_all"] = [[p["waiting_for_reader_s"] for p in x.get("passes", [])] for x in many]
+        r["text_GB_per_s_end_to_end"] = res["fastq_bytes"] / r["wall_s"] / 1e9
+        res["runs"][name] = r
+        outputs[name] = sorted((f[len(tag):], hashlib.sha256(open(os.path.join(pdir, f), "rb").read()).hexdigest()) for f in sorted(os.listdir(pdir)) if f.startswith(tag + "_"))
+        json.dump(res, open(out, "w"), indent=1)  # (what there is so far survives a time limit)
+    CLI = this
+    res["outputs_identical"] = all(o == outputs["this_tree/plain"] and o for o in outputs.values())
+    json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res, indent=1))
+    for f in (fq, gz, bg):
+        os.remove(f)
+
+
 def main():
+    gzip_m = "--gzip" in sys.argv
+    if gzip_m:
+        sys.argv.remove("--gzip")
     bgzf = "--bgzf" in sys.argv
     if bgzf:
         sys.argv.remove("--bgzf")
@@ -170,6 +305,8 @@ def main():
     res = {"fastq_bytes": size, "reads": n_reads, "genome": genome, "fastq_written_s": time.perf_counter() - t0, "fastq_generator": generator, "runs": {}}
     if bgzf:
         return bgzf_mode(out, fq, n_reads, genome, res)
+    if gzip_m:
+        return gzip_mode(out, fq, n_reads, genome, res)
     base = ["-k22", "-w16", "-t1000", "-u5", "-a1", "-o0.1", "-h3", "-j16", "-P10", "-d5", "-x10", "-s" + SEED, "-g%d" % genome, "-b10", "--verbose"]
     pdir = os.path.join(tmp, "cli_e2e_out")
     os.makedirs(pdir, exist_ok=True)
