@@ -18,7 +18,7 @@
 // outside it read as zero, and no more bits can be consumed than the payload has), every store by the member's
 // text_len, a distance may not reach in front of the member's first byte, every loop consumes input or produces output
 // in each iteration, no wave waits for another.  A member that is not a valid stream of exactly text_len bytes ends
-// with a status word; k_bgzf_crc then compares the CRC32 of every good member's text.
+// with a status word; k_inflate_crc then compares the CRC32 of every good member's text.
 //
 // The decoder is written against four macros so that the same text compiles as plain C++ with the 64 lanes run one
 // after the other (GRP_INFLATE_HOST: tools/dev/inflate_host_check.cpp checks the decoder against zlib under the sanitizers,
@@ -623,14 +623,16 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
   return INF_OK;
 }
 
+// how an entry of either table decodes: a BGZF member is a whole stream at a byte (it has no history: `dict` is not
+// looked at), a segment starts at a bit, behind its history
 INF_FN uint32_t
-inf_member(InfLds& s, const uint8_t* comp, uint64_t comp_off, uint32_t comp_len, char* out, uint32_t text_len)
+inf_entry(InfLds& s, const uint8_t* comp, const uint8_t*, const grp_bgzf_block& b, char* out)
 {
-  return inf_stream<false>(s, comp, comp_off, comp_len, nullptr, 0, 0, out, text_len);
+  return inf_stream<false>(s, comp, b.comp_off, b.comp_len, nullptr, 0, 0, out, b.text_len);
 }
 
 INF_FN uint32_t
-inf_segment(InfLds& s, const uint8_t* comp, const uint8_t* dict, const grp_gzip_segment& g, char* out)
+inf_entry(InfLds& s, const uint8_t* comp, const uint8_t* dict, const grp_gzip_segment& g, char* out)
 {
   return inf_stream<true>(s, comp, g.comp_bit, g.n_bits, dict + g.dict_off, g.dict_len, g.flags, out, g.text_len);
 }
@@ -709,60 +711,34 @@ crc_member(CrcLds& s, const uint32_t* tables, const char* text, uint32_t n)
 }
 
 #ifndef GRP_INFLATE_HOST
-// one workgroup of one wave per member; toff[i]: where member i's text starts in `text`
+// one workgroup of one wave per entry (Entry: grp_bgzf_block, a member; grp_gzip_segment, a segment of a serial stream);
+// toff[i]: where entry i's text starts in `text`
+template <class Entry>
 __global__ void __launch_bounds__(64)
-k_bgzf_inflate(const uint8_t* __restrict__ comp, const grp_bgzf_block* __restrict__ blocks, const uint64_t* __restrict__ toff, uint32_t n_blocks, char* __restrict__ text, uint32_t* __restrict__ status)
+k_inflate(const uint8_t* __restrict__ comp, const uint8_t* __restrict__ dict, const Entry* __restrict__ entries, const uint64_t* __restrict__ toff, uint32_t n_entries, char* __restrict__ text, uint32_t* __restrict__ status)
 {
   __shared__ InfLds s;
   const uint32_t i = blockIdx.x;
-  if (i >= n_blocks) {
+  if (i >= n_entries) {
     return;
   }
-  const uint32_t st = inf_member(s, comp, blocks[i].comp_off, blocks[i].comp_len, text + toff[i], blocks[i].text_len);
+  const uint32_t st = inf_entry(s, comp, dict, entries[i], text + toff[i]);
   if (threadIdx.x == 0) {
     status[i] = st;
   }
 }
 
+template <class Entry>
 __global__ void __launch_bounds__(64)
-k_bgzf_crc(const grp_bgzf_block* __restrict__ blocks, const uint64_t* __restrict__ toff, uint32_t n_blocks, const char* __restrict__ text, const uint32_t* __restrict__ tables, uint32_t* __restrict__ status)
+k_inflate_crc(const Entry* __restrict__ entries, const uint64_t* __restrict__ toff, uint32_t n_entries, const char* __restrict__ text, const uint32_t* __restrict__ tables, uint32_t* __restrict__ status)
 {
   __shared__ CrcLds s;
   const uint32_t i = blockIdx.x;
-  if (i >= n_blocks || status[i] != INF_OK) {
+  if (i >= n_entries || status[i] != INF_OK) {
     return;
   }
-  const uint32_t c = crc_member(s, tables, text + toff[i], blocks[i].text_len);
-  if (threadIdx.x == 0 && c != blocks[i].crc32) {
-    status[i] = INF_CRC_MISMATCH;
-  }
-}
-
-// the segment forms: one workgroup of one wave per segment of a serial stream
-__global__ void __launch_bounds__(64)
-k_gzip_inflate(const uint8_t* __restrict__ comp, const uint8_t* __restrict__ dict, const grp_gzip_segment* __restrict__ segs, const uint64_t* __restrict__ toff, uint32_t n_segs, char* __restrict__ text, uint32_t* __restrict__ status)
-{
-  __shared__ InfLds s;
-  const uint32_t i = blockIdx.x;
-  if (i >= n_segs) {
-    return;
-  }
-  const uint32_t st = inf_segment(s, comp, dict, segs[i], text + toff[i]);
-  if (threadIdx.x == 0) {
-    status[i] = st;
-  }
-}
-
-__global__ void __launch_bounds__(64)
-k_gzip_crc(const grp_gzip_segment* __restrict__ segs, const uint64_t* __restrict__ toff, uint32_t n_segs, const char* __restrict__ text, const uint32_t* __restrict__ tables, uint32_t* __restrict__ status)
-{
-  __shared__ CrcLds s;
-  const uint32_t i = blockIdx.x;
-  if (i >= n_segs || status[i] != INF_OK) {
-    return;
-  }
-  const uint32_t c = crc_member(s, tables, text + toff[i], segs[i].text_len);
-  if (threadIdx.x == 0 && c != segs[i].crc32) {
+  const uint32_t c = crc_member(s, tables, text + toff[i], entries[i].text_len);
+  if (threadIdx.x == 0 && c != entries[i].crc32) {
     status[i] = INF_CRC_MISMATCH;
   }
 }
@@ -805,6 +781,182 @@ crc_tables(uint32_t* out)
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+namespace {
+
+// What the launcher has to know of a format beside inf_entry: the check of one table entry against the caller's buffers
+// (a reason, or nullptr) and the words of its messages.
+template <class Entry>
+struct InfFormat;
+
+template <>
+struct InfFormat<grp_bgzf_block>
+{
+  static constexpr const char* fn = "grp_bgzf_inflate";
+  static constexpr const char* nouns = "blocks";
+  static constexpr const char* limits = "at most 4 GiB of compressed bytes and 2^22 blocks per call";
+
+  static const char* check_entry(const grp_bgzf_block& b, uint64_t n_comp, uint64_t)
+  {
+    return b.comp_off > n_comp || b.comp_len > n_comp - b.comp_off ? "its payload does not lie inside the compressed bytes" : b.text_len > INF_MAX_TEXT ? "more than 65536 bytes of text" : nullptr;
+  }
+  static int refuse_entry(grp_ctx* c, uint32_t i, const char* why, const grp_bgzf_block& b, uint64_t n_comp, uint64_t)
+  {
+    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u: %s (payload [%llu, +%u) of %llu, text %u)", i, why, (unsigned long long)b.comp_off, b.comp_len, (unsigned long long)n_comp, b.text_len);
+  }
+  static int refuse_stream(grp_ctx* c, uint32_t i, const grp_bgzf_block& b, const char* status)
+  {
+    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u is not a valid DEFLATE stream of %u bytes with CRC32 %08x: %s", i, b.text_len, b.crc32, status);
+  }
+};
+
+template <>
+struct InfFormat<grp_gzip_segment>
+{
+  static constexpr const char* fn = "grp_gzip_inflate";
+  static constexpr const char* nouns = "segments";
+  static constexpr const char* limits = "at most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 segments per call";
+
+  static const char* check_entry(const grp_gzip_segment& g, uint64_t n_comp, uint64_t n_dict)
+  {
+    return g.comp_bit > n_comp * 8 || g.n_bits > n_comp * 8 - g.comp_bit    ? "its bits do not lie inside the compressed bytes"
+           : g.dict_len > INF_RING                                          ? "a history of more than 32768 bytes"
+           : g.dict_off > n_dict || g.dict_len > n_dict - g.dict_off        ? "its history does not lie inside the histories"
+           : g.flags & ~GRP_GZIP_SEG_FINAL                                  ? "an unknown flag"
+           : g.text_len > 0xffff0000u                                       ? "more than 4 GiB - 64 KiB of text"
+                                                                            : nullptr;
+  }
+  static int refuse_entry(grp_ctx* c, uint32_t i, const char* why, const grp_gzip_segment& g, uint64_t n_comp, uint64_t n_dict)
+  {
+    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u: %s (bits [%llu, +%llu) of %llu bytes, history [%llu, +%u) of %llu, text %u, flags %u)", i, why, (unsigned long long)g.comp_bit, (unsigned long long)g.n_bits,
+                   (unsigned long long)n_comp, (unsigned long long)g.dict_off, g.dict_len, (unsigned long long)n_dict, g.text_len, g.flags);
+  }
+  static int refuse_stream(grp_ctx* c, uint32_t i, const grp_gzip_segment& g, const char* status)
+  {
+    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u is not %llu bits of valid DEFLATE blocks that hold %u bytes of text with CRC32 %08x: %s", i, (unsigned long long)g.n_bits, g.text_len, g.crc32, status);
+  }
+};
+
+// the CRC32 tables of both formats, made on the first call of either
+int
+inflate_crc_tables(grp_ctx* c)
+{
+  if (!c->d_crc_tab.p) {
+    std::vector<uint32_t> tab(4 * 256 + 32);
+    crc_tables(tab.data());
+    HIP_TRY(c, c->d_crc_tab.reset(tab.size()));
+    HIP_TRY(c, hipMemcpy(c->d_crc_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  return GRP_OK;
+}
+
+// grp_bgzf_inflate and grp_gzip_inflate (a BGZF call has no histories: dict == nullptr, n_dict == 0)
+template <class Entry>
+int
+inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const Entry* entries, uint32_t n, char* text_out, uint64_t text_cap, uint32_t* bad)
+{
+  using F = InfFormat<Entry>;
+  if ((!comp && n_comp) || (!dict && n_dict) || (!entries && n) || n_comp > (1ull << 32) || n_dict > (1ull << 32) || n > MAX_GRID_WGS) {
+    return set_err(c, GRP_ERR_INVALID, "%s: bad argument (%s)", F::fn, F::limits);
+  }
+  // the table is checked before anything is launched
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (const char* why = F::check_entry(entries[i], n_comp, n_dict)) {
+      if (bad) {
+        *bad = i;
+      }
+      return F::refuse_entry(c, i, why, entries[i], n_comp, n_dict);
+    }
+    total += entries[i].text_len;
+  }
+  if (total > text_cap || (total && !text_out)) {
+    return set_err(c, GRP_ERR_INVALID, "%s: the %s hold %llu bytes of text, the caller's buffer %llu", F::fn, F::nouns, (unsigned long long)total, (unsigned long long)text_cap);
+  }
+  if (n == 0) {
+    return GRP_OK;
+  }
+  hipStream_t st = c->stream2; // (a fill queued on the main stream keeps running beside this)
+  if (const int rc = inflate_crc_tables(c)) {
+    return rc;
+  }
+  if (!p.ev0.e) {
+    HIP_TRY(c, p.ev0.create(hipEventDefault));
+    HIP_TRY(c, p.ev1.create(hipEventDefault));
+  }
+  // grown, never shrunk (like the ingest's buffers); the kernels read whole words: 8 bytes of padding behind the
+  // compressed bytes, the histories and the text
+  HIP_TRY(c, p.d_comp.ensure(n_comp + 8));
+  HIP_TRY(c, p.d_dict.ensure(n_dict + 8));
+  HIP_TRY(c, p.d_text.ensure(total + 8));
+  HIP_TRY(c, p.d_entries.ensure(n));
+  HIP_TRY(c, p.d_toff.ensure(n));
+  HIP_TRY(c, p.d_status.ensure(n));
+  if (p.h_entries.cap < n) {
+    const uint64_t cap = (uint64_t)n + n / 4 + 64;
+    HIP_TRY(c, p.h_entries.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, p.h_toff.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, p.h_status.reset(cap, hipHostMallocDefault));
+  }
+  memcpy(p.h_entries.p, entries, (size_t)n * sizeof(Entry));
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    p.h_toff.p[i] = off;
+    off += entries[i].text_len;
+  }
+  if (n_comp) {
+    HIP_TRY(c, hipMemcpyAsync(p.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemsetAsync(p.d_comp + n_comp, 0, 8, st));
+  if (n_dict) {
+    HIP_TRY(c, hipMemcpyAsync(p.d_dict, dict, n_dict, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(p.d_entries, p.h_entries.p, (size_t)n * sizeof(Entry), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(p.d_toff, p.h_toff.p, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(p.ev0, st));
+  k_inflate<Entry><<<n, 64, 0, st>>>(p.d_comp, p.d_dict, p.d_entries, p.d_toff, n, reinterpret_cast<char*>(p.d_text.p), p.d_status);
+  k_inflate_crc<Entry><<<n, 64, 0, st>>>(p.d_entries, p.d_toff, n, reinterpret_cast<const char*>(p.d_text.p), c->d_crc_tab, p.d_status);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(p.ev1, st));
+  HIP_TRY(c, hipMemcpyAsync(p.h_status.p, p.d_status, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (total) {
+    HIP_TRY(c, hipMemcpyAsync(text_out, p.d_text, total, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, p.ev0, p.ev1) == hipSuccess) {
+    p.kernel_us += (double)ms * 1000.0;
+  }
+  p.n_entries += n;
+  p.n_comp += n_comp;
+  p.n_text += total;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t s = p.h_status.p[i];
+    if (s != INF_OK) {
+      if (bad) {
+        *bad = i;
+      }
+      return F::refuse_stream(c, i, entries[i], s < INF_STATUS_COUNT ? INF_STATUS_TEXT[s] : "unknown status");
+    }
+  }
+  return GRP_OK;
+}
+
+template <class Pool>
+int
+inflate_stats(const Pool* p, uint64_t out[4])
+{
+  if (!p || !out) {
+    return GRP_ERR_INVALID;
+  }
+  out[0] = p->n_entries;
+  out[1] = p->n_comp;
+  out[2] = p->n_text;
+  out[3] = (uint64_t)p->kernel_us;
+  return GRP_OK;
+}
+
+} // namespace
+
 extern "C" int
 grp_bgzf_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const grp_bgzf_block* blocks, uint32_t n_blocks, char* text_out, uint64_t text_cap, uint32_t* bad_block)
 {
@@ -814,102 +966,7 @@ grp_bgzf_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const grp_bgz
   if (bad_block) {
     *bad_block = UINT32_MAX;
   }
-  if ((!comp && n_comp) || (!blocks && n_blocks) || n_comp > (1ull << 32) || n_blocks > MAX_GRID_WGS) {
-    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: bad argument (at most 4 GiB of compressed bytes and 2^22 blocks per call)");
-  }
-  // the table is checked before anything is launched
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n_blocks; ++i) {
-    const grp_bgzf_block& b = blocks[i];
-    const char* why = b.comp_off > n_comp || b.comp_len > n_comp - b.comp_off ? "its payload does not lie inside the compressed bytes" : b.text_len > INF_MAX_TEXT ? "more than 65536 bytes of text" : nullptr;
-    if (why) {
-      if (bad_block) {
-        *bad_block = i;
-      }
-      return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u: %s (payload [%llu, +%u) of %llu, text %u)", i, why, (unsigned long long)b.comp_off, b.comp_len, (unsigned long long)n_comp, b.text_len);
-    }
-    total += b.text_len;
-  }
-  if (total > text_cap || (total && !text_out)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: the blocks hold %llu bytes of text, the caller's buffer %llu", (unsigned long long)total, (unsigned long long)text_cap);
-  }
-  if (n_blocks == 0) {
-    return GRP_OK;
-  }
-  auto& bp = c->bgzf;
-  hipStream_t st = c->stream2; // (a fill queued on the main stream keeps running beside this)
-  if (!bp.d_tab.p) {
-    std::vector<uint32_t> tab(4 * 256 + 32);
-    crc_tables(tab.data());
-    HIP_TRY(c, bp.d_tab.reset(tab.size()));
-    HIP_TRY(c, hipMemcpy(bp.d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, bp.ev0.create(hipEventDefault));
-    HIP_TRY(c, bp.ev1.create(hipEventDefault));
-  }
-  // grown, never shrunk (like the ingest's buffers); the kernels read whole words: 8 bytes of padding behind each
-  HIP_TRY(c, bp.d_comp.ensure(n_comp + 8));
-  HIP_TRY(c, bp.d_text.ensure(total + 8));
-  HIP_TRY(c, bp.d_blocks.ensure(n_blocks));
-  HIP_TRY(c, bp.d_toff.ensure(n_blocks));
-  HIP_TRY(c, bp.d_status.ensure(n_blocks));
-  if (bp.h_blocks.cap < n_blocks) {
-    const uint64_t cap = (uint64_t)n_blocks + n_blocks / 4 + 64;
-    HIP_TRY(c, bp.h_blocks.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, bp.h_toff.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, bp.h_status.reset(cap, hipHostMallocDefault));
-  }
-  memcpy(bp.h_blocks.p, blocks, (size_t)n_blocks * sizeof(grp_bgzf_block));
-  uint64_t off = 0;
-  for (uint32_t i = 0; i < n_blocks; ++i) {
-    bp.h_toff.p[i] = off;
-    off += blocks[i].text_len;
-  }
-  if (n_comp) {
-    HIP_TRY(c, hipMemcpyAsync(bp.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipMemsetAsync(bp.d_comp + n_comp, 0, 8, st));
-  HIP_TRY(c, hipMemcpyAsync(bp.d_blocks, bp.h_blocks.p, (size_t)n_blocks * sizeof(grp_bgzf_block), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(bp.d_toff, bp.h_toff.p, (size_t)n_blocks * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(bp.ev0, st));
-  k_bgzf_inflate<<<n_blocks, 64, 0, st>>>(bp.d_comp, bp.d_blocks, bp.d_toff, n_blocks, reinterpret_cast<char*>(bp.d_text.p), bp.d_status);
-  k_bgzf_crc<<<n_blocks, 64, 0, st>>>(bp.d_blocks, bp.d_toff, n_blocks, reinterpret_cast<const char*>(bp.d_text.p), bp.d_tab, bp.d_status);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(bp.ev1, st));
-  HIP_TRY(c, hipMemcpyAsync(bp.h_status.p, bp.d_status, (size_t)n_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (total) {
-    HIP_TRY(c, hipMemcpyAsync(text_out, bp.d_text, total, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, bp.ev0, bp.ev1) == hipSuccess) {
-    bp.kernel_us += (double)ms * 1000.0;
-  }
-  bp.n_blocks += n_blocks;
-  bp.n_comp += n_comp;
-  bp.n_text += total;
-  for (uint32_t i = 0; i < n_blocks; ++i) {
-    const uint32_t s = bp.h_status.p[i];
-    if (s != INF_OK) {
-      if (bad_block) {
-        *bad_block = i;
-      }
-      return set_err(c, GRP_ERR_INVALID, "grp_bgzf_inflate: block %u is not a valid DEFLATE stream of %u bytes with CRC32 %08x: %s", i, blocks[i].text_len, blocks[i].crc32, s < INF_STATUS_COUNT ? INF_STATUS_TEXT[s] : "unknown status");
-    }
-  }
-  return GRP_OK;
-}
-
-extern "C" int
-grp_debug_bgzf_stats(const grp_ctx* c, uint64_t out[4])
-{
-  if (!c || !out) {
-    return GRP_ERR_INVALID;
-  }
-  out[0] = c->bgzf.n_blocks;
-  out[1] = c->bgzf.n_comp;
-  out[2] = c->bgzf.n_text;
-  out[3] = (uint64_t)c->bgzf.kernel_us;
-  return GRP_OK;
+  return inflate_entries(c, c->bgzf, comp, n_comp, nullptr, 0, blocks, n_blocks, text_out, text_cap, bad_block);
 }
 
 extern "C" int
@@ -921,117 +978,18 @@ grp_gzip_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t
   if (bad_seg) {
     *bad_seg = UINT32_MAX;
   }
-  if ((!comp && n_comp) || (!dict && n_dict) || (!segs && n_segs) || n_comp > (1ull << 32) || n_dict > (1ull << 32) || n_segs > MAX_GRID_WGS) {
-    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: bad argument (at most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 segments per call)");
-  }
-  // the table is checked before anything is launched
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n_segs; ++i) {
-    const grp_gzip_segment& g = segs[i];
-    const char* why = g.comp_bit > n_comp * 8 || g.n_bits > n_comp * 8 - g.comp_bit ? "its bits do not lie inside the compressed bytes"
-                      : g.dict_len > INF_RING                                        ? "a history of more than 32768 bytes"
-                      : g.dict_off > n_dict || g.dict_len > n_dict - g.dict_off      ? "its history does not lie inside the histories"
-                      : g.flags & ~GRP_GZIP_SEG_FINAL                                ? "an unknown flag"
-                      : g.text_len > 0xffff0000u                                     ? "more than 4 GiB - 64 KiB of text"
-                                                                                     : nullptr;
-    if (why) {
-      if (bad_seg) {
-        *bad_seg = i;
-      }
-      return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u: %s (bits [%llu, +%llu) of %llu bytes, history [%llu, +%u) of %llu, text %u, flags %u)", i, why, (unsigned long long)g.comp_bit,
-                     (unsigned long long)g.n_bits, (unsigned long long)n_comp, (unsigned long long)g.dict_off, g.dict_len, (unsigned long long)n_dict, g.text_len, g.flags);
-    }
-    total += g.text_len;
-  }
-  if (total > text_cap || (total && !text_out)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: the segments hold %llu bytes of text, the caller's buffer %llu", (unsigned long long)total, (unsigned long long)text_cap);
-  }
-  if (n_segs == 0) {
-    return GRP_OK;
-  }
-  auto& gp = c->gzip;
-  auto& bp = c->bgzf; // (the CRC32 tables are shared)
-  hipStream_t st = c->stream2;
-  if (!bp.d_tab.p) {
-    std::vector<uint32_t> tab(4 * 256 + 32);
-    crc_tables(tab.data());
-    HIP_TRY(c, bp.d_tab.reset(tab.size()));
-    HIP_TRY(c, hipMemcpy(bp.d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, bp.ev0.create(hipEventDefault));
-    HIP_TRY(c, bp.ev1.create(hipEventDefault));
-  }
-  if (!gp.ev0.e) {
-    HIP_TRY(c, gp.ev0.create(hipEventDefault));
-    HIP_TRY(c, gp.ev1.create(hipEventDefault));
-  }
-  // grown, never shrunk; the kernel reads whole words: 8 bytes of padding behind the compressed bytes and the histories
-  HIP_TRY(c, gp.d_comp.ensure(n_comp + 8));
-  HIP_TRY(c, gp.d_dict.ensure(n_dict + 8));
-  HIP_TRY(c, gp.d_text.ensure(total + 8));
-  HIP_TRY(c, gp.d_segs.ensure(n_segs));
-  HIP_TRY(c, gp.d_toff.ensure(n_segs));
-  HIP_TRY(c, gp.d_status.ensure(n_segs));
-  if (gp.h_segs.cap < n_segs) {
-    const uint64_t cap = (uint64_t)n_segs + n_segs / 4 + 64;
-    HIP_TRY(c, gp.h_segs.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, gp.h_toff.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, gp.h_status.reset(cap, hipHostMallocDefault));
-  }
-  memcpy(gp.h_segs.p, segs, (size_t)n_segs * sizeof(grp_gzip_segment));
-  uint64_t off = 0;
-  for (uint32_t i = 0; i < n_segs; ++i) {
-    gp.h_toff.p[i] = off;
-    off += segs[i].text_len;
-  }
-  if (n_comp) {
-    HIP_TRY(c, hipMemcpyAsync(gp.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipMemsetAsync(gp.d_comp + n_comp, 0, 8, st));
-  if (n_dict) {
-    HIP_TRY(c, hipMemcpyAsync(gp.d_dict, dict, n_dict, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipMemcpyAsync(gp.d_segs, gp.h_segs.p, (size_t)n_segs * sizeof(grp_gzip_segment), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(gp.d_toff, gp.h_toff.p, (size_t)n_segs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(gp.ev0, st));
-  k_gzip_inflate<<<n_segs, 64, 0, st>>>(gp.d_comp, gp.d_dict, gp.d_segs, gp.d_toff, n_segs, reinterpret_cast<char*>(gp.d_text.p), gp.d_status);
-  k_gzip_crc<<<n_segs, 64, 0, st>>>(gp.d_segs, gp.d_toff, n_segs, reinterpret_cast<const char*>(gp.d_text.p), bp.d_tab, gp.d_status);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(gp.ev1, st));
-  HIP_TRY(c, hipMemcpyAsync(gp.h_status.p, gp.d_status, (size_t)n_segs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (total) {
-    HIP_TRY(c, hipMemcpyAsync(text_out, gp.d_text, total, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, gp.ev0, gp.ev1) == hipSuccess) {
-    gp.kernel_us += (double)ms * 1000.0;
-  }
-  gp.n_segs += n_segs;
-  gp.n_comp += n_comp;
-  gp.n_text += total;
-  for (uint32_t i = 0; i < n_segs; ++i) {
-    const uint32_t s = gp.h_status.p[i];
-    if (s != INF_OK) {
-      if (bad_seg) {
-        *bad_seg = i;
-      }
-      return set_err(c, GRP_ERR_INVALID, "grp_gzip_inflate: segment %u is not %llu bits of valid DEFLATE blocks that hold %u bytes of text with CRC32 %08x: %s", i, (unsigned long long)segs[i].n_bits, segs[i].text_len, segs[i].crc32,
-                     s < INF_STATUS_COUNT ? INF_STATUS_TEXT[s] : "unknown status");
-    }
-  }
-  return GRP_OK;
+  return inflate_entries(c, c->gzip, comp, n_comp, dict, n_dict, segs, n_segs, text_out, text_cap, bad_seg);
+}
+
+extern "C" int
+grp_debug_bgzf_stats(const grp_ctx* c, uint64_t out[4])
+{
+  return inflate_stats(c ? &c->bgzf : nullptr, out);
 }
 
 extern "C" int
 grp_debug_gzip_stats(const grp_ctx* c, uint64_t out[4])
 {
-  if (!c || !out) {
-    return GRP_ERR_INVALID;
-  }
-  out[0] = c->gzip.n_segs;
-  out[1] = c->gzip.n_comp;
-  out[2] = c->gzip.n_text;
-  out[3] = (uint64_t)c->gzip.kernel_us;
-  return GRP_OK;
+  return inflate_stats(c ? &c->gzip : nullptr, out);
 }
 #endif

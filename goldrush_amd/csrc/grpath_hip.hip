@@ -301,36 +301,25 @@ struct grp_ctx : CtxStreams
     Event text_up[FQ_TEXT_SLOTS];   // the slot's prefetched body has arrived (recorded on the copy stream)
     Event text_done[FQ_TEXT_SLOTS]; // the main stream's last use of the slot's text (grp_fastq_free records it: the next upload into the slot waits for it, not the host)
   } ingest;
-  // grp_bgzf_inflate (grp_inflate.inc): the compressed bytes, the block table with the text offsets, the text and the
-  // per-block status words of one call; grown, never shrunk
-  struct BgzfPool
-  {
-    DevBuf<uint8_t> d_comp, d_text;
-    DevBuf<grp_bgzf_block> d_blocks;
-    DevBuf<uint64_t> d_toff;
-    DevBuf<uint32_t> d_status;
-    DevBuf<uint32_t> d_tab; // CRC32 slicing tables and x^(2^k)
-    HostBuf<grp_bgzf_block> h_blocks; // page-locked staging
-    HostBuf<uint64_t> h_toff;
-    HostBuf<uint32_t> h_status;
-    Event ev0, ev1; // around the two kernels
-    uint64_t n_blocks = 0, n_comp = 0, n_text = 0; // grp_debug_bgzf_stats
-    double kernel_us = 0.0;
-  } bgzf;
-  // grp_gzip_inflate: the same for the segments of a serial stream, with their histories
-  struct GzipPool
+  // grp_bgzf_inflate / grp_gzip_inflate (grp_inflate.inc): the compressed bytes, the histories (segments only), the
+  // table with the text offsets, the text and the per-entry status words of one call; grown, never shrunk
+  template <class Entry>
+  struct InflatePool
   {
     DevBuf<uint8_t> d_comp, d_dict, d_text;
-    DevBuf<grp_gzip_segment> d_segs;
+    DevBuf<Entry> d_entries;
     DevBuf<uint64_t> d_toff;
     DevBuf<uint32_t> d_status;
-    HostBuf<grp_gzip_segment> h_segs; // page-locked staging
+    HostBuf<Entry> h_entries; // page-locked staging
     HostBuf<uint64_t> h_toff;
     HostBuf<uint32_t> h_status;
     Event ev0, ev1; // around the two kernels
-    uint64_t n_segs = 0, n_comp = 0, n_text = 0; // grp_debug_gzip_stats
+    uint64_t n_entries = 0, n_comp = 0, n_text = 0; // grp_debug_bgzf_stats / grp_debug_gzip_stats
     double kernel_us = 0.0;
-  } gzip;
+  };
+  InflatePool<grp_bgzf_block> bgzf;
+  InflatePool<grp_gzip_segment> gzip;
+  DevBuf<uint32_t> d_crc_tab; // CRC32 slicing tables and x^(2^k), of both (inflate_crc_tables)
   const char* reg_text = nullptr; // the caller's text buffer, page-locked by grp_fastq_pin
   size_t reg_bytes = 0;
   uint32_t timing_mask = (1u << GRP_K_FILL) | (1u << GRP_K_RANK) | (1u << GRP_K_QUERY) | (1u << GRP_K_DECIDE) | (1u << GRP_K_QUERY_LAT) | (1u << GRP_K_VERIFY) | (1u << GRP_K_BATCH);

@@ -5,16 +5,14 @@
 // Same flags, same stderr messages, same output files (<prefix>_<n>.fq in
 // --silver_path mode, <prefix>.fa otherwise), same exit codes.
 #include "../../../include/grpath_host.h"
-#include "gr_bgzf.hpp"
 #include "gr_classifier.hpp"
 #include "gr_fastq.hpp"
-#include "gr_gzidx.hpp"
 #include "gr_opts.hpp"
 #include "gr_params.hpp"
+#include "gr_source.hpp"
 
 #include <algorithm>
 #include <chrono>
-#include <cerrno>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -22,10 +20,7 @@
 #include <functional>
 #include <iomanip>
 #include <iostream>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <unordered_set>
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -36,750 +31,6 @@
 
 namespace gr {
 namespace {
-
-double
-now_s()
-{
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// records / bases per host batch (one grp_reads upload each).  GRP_BATCH_RECORDS
-// overrides the record count (tests use it to exercise the batch boundaries).
-size_t
-batch_records()
-{
-  static const size_t n = [] {
-    const char* e = getenv("GRP_BATCH_RECORDS");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (size_t)v : (size_t)16384;
-  }();
-  return n;
-}
-#define BATCH_RECORDS batch_records()
-constexpr size_t BATCH_BASES = size_t(384) << 20;
-
-size_t
-ingest_chunk_bytes()
-{
-  static const size_t n = [] {
-    const char* e = getenv("GRP_INGEST_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (size_t)v : (size_t)256 << 20;
-  }();
-  return n;
-}
-
-struct PathRun
-{
-  Opts opt;
-  grp_engine_vt vt{};
-  grp_engine_ext ext{}; // the optional entry points behind the table's 48 (gr_path_main_ext)
-  void* ctx = nullptr;
-  std::vector<std::string> seeds;
-  std::unordered_set<std::string> filter_out_reads;
-  std::ofstream out;
-  uint32_t world = 1, rank = 0; // ranks sharing the classification windows (one process per GPU)
-  // several ranks: every rank hashes the reads of its share of the batches into its bit vector, the
-  // vectors are OR-merged before the rank build (round 3: the CLI's fill is no longer replicated)
-  bool shard_fill = false;   // batch b belongs to rank b % world
-  bool merge_rccl = false;   // ... merged by RCCL inside the engine (else staged through host memory and /dev/shm)
-  void* shm = nullptr;       // gr_shm_allgather handle
-  int32_t device = -1;       // HIP device ordinal of this rank
-  // a plain gzip input: the restart points the first complete pass over it wrote down (gr_gzidx.hpp); the passes behind
-  // it inflate its segments on the device
-  std::shared_ptr<GzIndex> gzidx;
-
-  int fail_engine(const char* what)
-  {
-    std::cerr << "goldrush-path: " << what << ": " << (vt.last_error ? vt.last_error(ctx) : "engine error") << std::endl;
-    return 1;
-  }
-};
-
-// ---- record sources -----------------------------------------------------------
-// A batch of consecutive FASTQ records; offsets are relative to `text`.
-struct Rec
-{
-  size_t id_off, id_len, seq_off, seq_len, qual_off, qual_len;
-};
-
-struct Batch
-{
-  const char* text = nullptr;
-  uint64_t base_off = 0;            // offset of text[0] in the (decompressed) input stream
-  std::vector<Rec> rec;
-  std::vector<uint32_t> avg, delta; // calc_phred_average, valid where stats() ran
-  std::vector<uint8_t> non_acgt;    // find_first_not_of("ACGTacgt") != npos
-  bool seq_is_upper = false;        // the host reader folds case while copying
-  std::string id_str(size_t i) const { return std::string(text + rec[i].id_off, rec[i].id_len); }
-};
-
-class RecordSource
-{
-public:
-  virtual ~RecordSource() {}
-  virtual bool ok() const = 0;
-  virtual bool is_fastq() = 0;
-  virtual bool next(Batch& b) = 0;
-  // Phred statistics (and the ACGT check) of the records with seq_len >= min_len
-  virtual void stats(Batch& b, size_t min_len, bool need_acgt) = 0;
-  // the selected records as a batch of packed reads on the device
-  virtual int upload(Batch& b, const std::vector<uint32_t>& sel, std::vector<uint32_t>& lens, void** reads) = 0;
-};
-
-// host reader + host packing (engines without the ingest entry points)
-class HostSource : public RecordSource
-{
-public:
-  HostSource(PathRun& run)
-    : run_(run)
-    , fq_(run.opt.input)
-  {}
-  bool ok() const override { return fq_.ok(); }
-  bool is_fastq() override { return fq_.is_fastq(); }
-  bool next(Batch& b) override
-  {
-    if (!fq_.next_batch(rb_, BATCH_RECORDS, BATCH_BASES)) {
-      return false;
-    }
-    b.text = rb_.text.data();
-    b.rec.resize(rb_.rec.size());
-    for (size_t i = 0; i < rb_.rec.size(); ++i) {
-      const RecordRef& r = rb_.rec[i];
-      b.rec[i] = Rec{ r.id_off, r.id_len, r.seq_off, r.seq_len, r.qual_off, r.qual_len };
-    }
-    b.seq_is_upper = true;
-    return true;
-  }
-  void stats(Batch& b, size_t min_len, bool need_acgt) override
-  {
-    const size_t n = b.rec.size();
-    b.avg.assign(n, 0);
-    b.delta.assign(n, 0);
-    b.non_acgt.assign(n, 0);
-#if defined(_OPENMP)
-#pragma omp parallel for schedule(dynamic, 8)
-#endif
-    for (size_t i = 0; i < n; ++i) {
-      const Rec& r = b.rec[i];
-      if (r.seq_len < min_len) {
-        continue;
-      }
-      calc_phred_average(b.text + r.qual_off, r.qual_len, b.avg[i], b.delta[i]);
-      if (need_acgt) {
-        const char* s = b.text + r.seq_off; // already upper-cased
-        for (size_t j = 0; j < r.seq_len; ++j) {
-          const char c = s[j];
-          if (c != 'A' && c != 'C' && c != 'G' && c != 'T') {
-            b.non_acgt[i] = 1;
-            break;
-          }
-        }
-      }
-    }
-  }
-  int upload(Batch& b, const std::vector<uint32_t>& sel, std::vector<uint32_t>& lens, void** reads) override
-  {
-    const size_t n = sel.size();
-    lens.resize(n);
-    word_off_.resize(n + 1);
-    uint64_t w = 0;
-    for (size_t i = 0; i < n; ++i) {
-      word_off_[i] = w;
-      lens[i] = (uint32_t)b.rec[sel[i]].seq_len;
-      w += (b.rec[sel[i]].seq_len + 15) / 16;
-    }
-    word_off_[n] = w;
-    packed_.resize(w ? w : 1);
-#if defined(_OPENMP)
-#pragma omp parallel for schedule(dynamic, 16)
-#endif
-    for (size_t i = 0; i < n; ++i) {
-      pack_2bit(b.text + b.rec[sel[i]].seq_off, b.rec[sel[i]].seq_len, packed_.data() + word_off_[i]);
-    }
-    return run_.vt.reads_upload(run_.ctx, packed_.data(), word_off_.data(), lens.data(), (uint32_t)n, reads);
-  }
-
-private:
-  PathRun& run_;
-  FastqStream fq_;
-  RecordBatch rb_;
-  std::vector<uint32_t> packed_;
-  std::vector<uint64_t> word_off_;
-};
-
-// raw text chunks parsed, filtered and packed on the GPU (grpath_ingest.h).
-// A reader thread keeps the NEXT chunk of the file coming (InputFile: parallel pread of a plain
-// file, zlib for gzip data) while the caller works on the current one — upload, parse, pack, fill
-// or classify — so a pass costs max(read, GPU) per chunk instead of their sum.  Four slots in ONE
-// page-locked buffer; every slot has room in front of the bytes read for the unconsumed tail of
-// the chunk before it (a partial record), which is copied there before the parse.
-// A BGZF-compressed file (gr_bgzf.hpp) whose members the engine can inflate (grp_engine_ext::bgzf_inflate; GRP_BGZF=off:
-// no) takes the same road: the reader thread reads COMPRESSED bytes and walks the members' headers; a slot is filled with
-// whole members until its text, its compressed bytes or its block table is full; the consumer has the engine inflate
-// them into the slot's text before that text is handed to fastq_prefetch / fastq_parse.  Everything behind that — the
-// carried tail, parse, pack, stats — does not know.  Plain gzip is one serial stream and stays with zlib; from a member
-// in mid-file that is not BGZF on (bgzip output followed by gzip output) zlib reads the rest.
-// A file that is gzip from its first byte and not taken by the BGZF form (grp_engine_ext::gzip_inflate; GRP_GZIP_INDEX=off:
-// no): the first pass that reads it to its end does so through GzIndexReader — zlib as before, on the reader thread — and
-// leaves the index of its restart points in the run; in every pass behind it the reader thread preads whole SEGMENTS
-// into a slot until its text, its compressed bytes, its histories or its table is full, and the consumer has the engine
-// inflate them, exactly like the members of a BGZF file.  A pass that ends early (the Phred median) leaves no index, a
-// file that changed between two passes drops it, an index with a segment larger than a slot is not used.
-class GpuSource : public RecordSource
-{
-public:
-  GpuSource(PathRun& run)
-    : run_(run)
-    , in_(run.opt.input)
-  {
-    chunk_ = std::max<size_t>(ingest_chunk_bytes(), 64);
-    {
-      const char* e = getenv("GRP_BGZF");
-      if (run_.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
-        // is the first member a complete BGZF member?  (a member is at most 64 KiB; a pipe cannot be pread: zlib)
-        const int fd = ::open(run.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
-        if (fd >= 0) {
-          std::vector<unsigned char> head(BGZF_MAX_MEMBER);
-          const ssize_t k = pread(fd, head.data(), head.size(), 0);
-          grp_bgzf_block b;
-          if (k > 0 && bgzf_scan(head.data(), (size_t)k, &b, 1, nullptr, nullptr) == 1) {
-            bgzf_ = true;
-            zfd_ = fd;
-          } else {
-            ::close(fd);
-          }
-        }
-      }
-    }
-    if (!bgzf_ && run_.ext.gzip_inflate && gzip_index_enabled()) {
-      if (run_.gzidx && !run_.gzidx->matches(run.opt.input)) {
-        run_.gzidx.reset(); // the file was written since: this pass builds a new one
-      }
-      const int fd = ::open(run.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
-      struct stat st;
-      unsigned char magic[2] = { 0, 0 };
-      const bool gz = fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-      if (gz && run_.gzidx) {
-        if (run_.gzidx->max_text <= chunk_) { // (else the whole pass goes through zlib)
-          gzseg_ = true;
-          zfd_ = fd;
-        }
-      } else if (gz) {
-        gzbuild_.reset(new GzIndexReader(run.opt.input, gzip_index_span(), gzip_index_max_bytes()));
-        if (!gzbuild_->ok()) {
-          gzbuild_.reset();
-        }
-      }
-      if (fd >= 0 && zfd_ != fd) {
-        ::close(fd);
-      }
-    }
-    if (gzseg_) {
-      comp_cap_ = std::max<size_t>(chunk_ / 2, (size_t)run_.gzidx->max_comp + 8);
-      dict_cap_ = chunk_ / 8 + 32768; // (32 KiB per 256 KiB of text at the default span)
-      tab_cap_ = std::max<size_t>(chunk_ / 4096, 64);
-      for (Slot& sl : slot_) {
-        sl.segs.resize(tab_cap_);
-      }
-    }
-    if (bgzf_) {
-      chunk_ = std::max<size_t>(chunk_, BGZF_MAX_TEXT); // a tiny GRP_INGEST_CHUNK still holds one member
-      comp_cap_ = std::max<size_t>(chunk_ / 2, BGZF_MAX_MEMBER);
-      tab_cap_ = std::max<size_t>(chunk_ / 4096, 64);
-      for (Slot& sl : slot_) {
-        sl.blocks.resize(tab_cap_);
-      }
-    }
-    if (in_.plain_size() != 0) { // a small file: one slot holds it all, no 2 x 256 MiB to allocate and page-lock
-      chunk_ = std::min<size_t>(chunk_, std::max<size_t>((size_t)in_.plain_size() + 1, size_t(1) << 16));
-    }
-    front_ = std::min<size_t>(std::max<size_t>(chunk_ / 16, 4096), (size_t)GRP_FASTQ_PREFETCH_FRONT); // (what a prefetched body may have in front of it, grpath_ingest.h)
-    buf_.resize((size_t)kSlots * (front_ + chunk_ + comp_cap_ + dict_cap_)); // (the compressed bytes of the slots behind their texts, the histories behind those: one page-locked buffer)
-    const char* pin_min = getenv("GRP_PIN_MIN_BYTES"); // tests: page-lock small buffers too
-    if (run_.vt.fastq_pin && run_.vt.fastq_unpin && buf_.size() >= (pin_min ? (size_t)atoll(pin_min) : (size_t(8) << 20))) {
-      pinned_ = run_.vt.fastq_pin(run_.ctx, buf_.data(), buf_.size()) == GRP_OK;
-    }
-  }
-  ~GpuSource() override
-  {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    if (reader_.joinable()) {
-      reader_.join();
-    }
-    release();
-    if (run_.vt.fastq_prefetch) {
-      (void)run_.vt.fastq_prefetch(run_.ctx, nullptr, 0); // bodies handed over ahead of a parse that never came (an early end)
-    }
-    if (getenv("GRP_TRACE_INGEST")) {
-      std::cerr << "GRP_TRACE_INGEST source: " << n_pre_[0] << " chunks, next chunk not ready at " << n_pre_[1] << ", uploads started ahead " << n_pre_[2] << "; seconds waiting for the reader " << t_tr_[0]
-                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << n_bgzf_blocks_
-                << ", gzip segments inflated on the device " << n_gzip_segs_ << std::endl;
-    }
-    if (zfd_ >= 0) {
-      ::close(zfd_);
-    }
-    if (pinned_) {
-      run_.vt.fastq_unpin(run_.ctx); // before the buffer goes away: the engine cannot know when the host frees memory
-    }
-  }
-  bool ok() const override { return in_.ok(); }
-  bool is_fastq() override { return in_.peek() == '@'; } // (asked before the first chunk is read)
-  bool next(Batch& b) override
-  {
-    release();
-    if (!reader_.joinable() && !done_) {
-      reader_ = std::thread([this] { read_loop(); });
-    }
-    while (!done_) {
-      // the slot handed out by the previous call goes back to the reader, the next one is awaited
-      Slot* sl = nullptr;
-      {
-        std::unique_lock<std::mutex> g(mu_);
-        if (held_ >= 0) {
-          slot_[held_].uploaded = false;
-          slot_[held_].state = Slot::FREE;
-          held_ = -1;
-          cv_.notify_all();
-        }
-        const double tw0 = now_s();
-        cv_.wait(g, [&] { return slot_[take_].state == Slot::READY; });
-        t_tr_[0] += now_s() - tw0;
-        sl = &slot_[take_];
-        held_ = take_;
-        take_ = (take_ + 1) % kSlots;
-      }
-      if (!inflate_slot(held_)) { // (the failure is noted: the run ends with an error behind this pass)
-        done_ = true;
-        break;
-      }
-      const bool eof = sl->eof;
-      char* data = slot_data(held_);
-      // the tail of the chunk before, in front of what was read
-      char* text = nullptr;
-      size_t fill = carry_.size() + sl->n;
-      if (carry_.size() <= front_) {
-        text = data - carry_.size();
-        if (!carry_.empty()) { // (a prefetch reads the slot's body only: the room in front of it is free to write)
-          const double tc0 = now_s();
-          memcpy(text, carry_.data(), carry_.size());
-          t_tr_[3] += now_s() - tc0;
-        }
-      } else {
-        // a record longer than a chunk: assembled in a buffer of its own (pageable; rare)
-        big_.resize(fill);
-        memcpy(big_.data(), carry_.data(), carry_.size());
-        memcpy(big_.data() + carry_.size(), data, sl->n);
-        text = big_.data();
-      }
-      const uint64_t text_off = sl->file_off - carry_.size(); // stream offset of text[0]
-      if (fill == 0) {
-        done_ = true;
-        break;
-      }
-      uint64_t n_rec = 0, used = 0;
-      int stopped = 0;
-      const double tp0 = now_s();
-      const int prc = run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
-      t_tr_[1] += now_s() - tp0;
-      if (prc != GRP_OK) {
-        std::cerr << "goldrush-path: FASTQ ingest: " << (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "failed") << std::endl;
-        failed_ = true;
-        done_ = true;
-        break;
-      }
-      if (n_rec == 0 && !eof && !stopped) {
-        // not one complete record yet: everything is carried into the next chunk
-        release();
-        carry_.assign(text, text + fill);
-        continue;
-      }
-      carry_.assign(text + used, text + fill);
-      if (eof || stopped) {
-        done_ = true;
-      }
-      if (n_rec == 0) {
-        release();
-        continue;
-      }
-      meta_.resize(n_rec);
-      run_.vt.fastq_records(fq_, meta_.data());
-      b.text = text;
-      b.base_off = text_off;
-      b.rec.resize(n_rec);
-      for (size_t i = 0; i < n_rec; ++i) {
-        const grp_fastq_record& m = meta_[i];
-        b.rec[i] = Rec{ (size_t)m.id_off, m.id_len, (size_t)m.seq_off, m.seq_len, (size_t)m.qual_off, m.qual_len };
-      }
-      b.seq_is_upper = false;
-      prefetch_next();
-      return true;
-    }
-    return false;
-  }
-  // The uploads of the next TWO chunks' bodies, started as soon as the reader has them (round 5).  A copy issued behind the
-  // fill of the current chunk only begins when that has ended (tools/dev/r5_ingest_timeline.sh: fill, then copy, then parse,
-  // one after the other); issued one chunk ahead — with the tail of the chunk before copied in front first — it still lay on
-  // the path of every chunk (copy 5.5 ms + parse + the host's share against a fill of 7 ms).  The body does not depend on
-  // that tail: it goes up two chunks ahead, the engine leaves room in front of it and the parse uploads the tail alone
-  // (grpath_ingest.h: grp_fastq_prefetch).
-  void prefetch_next()
-  {
-    ++n_pre_[0];
-    if (!run_.vt.fastq_prefetch || done_) {
-      return;
-    }
-    for (int ahead = 0; ahead < 2; ++ahead) {
-      const int j = (take_ + ahead) % kSlots;
-      size_t n = 0;
-      {
-        std::lock_guard<std::mutex> g(mu_);
-        if (slot_[j].state != Slot::READY) {
-          n_pre_[1] += ahead == 0;
-          return; // the reader is still at it (and the slots behind it are not ready either)
-        }
-        if (slot_[j].eof && slot_[j].n == 0) {
-          return;
-        }
-        n = slot_[j].n; // (a READY slot is the consumer's until it releases it)
-      }
-      if (slot_[j].uploaded || n == 0) {
-        continue;
-      }
-      if (!inflate_slot(j)) {
-        return;
-      }
-      const double tq0 = now_s();
-      const int qrc = run_.vt.fastq_prefetch(run_.ctx, slot_data(j), n);
-      t_tr_[2] += now_s() - tq0;
-      if (qrc != GRP_OK) {
-        return; // no free buffer on the device: later
-      }
-      slot_[j].uploaded = true;
-      ++n_pre_[2];
-    }
-  }
-  void stats(Batch& b, size_t min_len, bool) override
-  {
-    const size_t n = b.rec.size();
-    b.avg.assign(n, 0);
-    b.delta.assign(n, 0);
-    b.non_acgt.assign(n, 0);
-    for (size_t i = 0; i < n; ++i) {
-      b.non_acgt[i] = (meta_[i].flags & GRP_FQ_NON_ACGT) ? 1 : 0;
-      if (b.rec[i].seq_len >= min_len) {
-        // the device summed left to right in double; log10 / truncation happen here
-        phred_from_sums(meta_[i].phred_sum, meta_[i].phred_first, b.rec[i].qual_len, b.avg[i], b.delta[i]);
-      }
-    }
-  }
-  int upload(Batch& b, const std::vector<uint32_t>& sel, std::vector<uint32_t>& lens, void** reads) override
-  {
-    lens.resize(sel.size());
-    for (size_t i = 0; i < sel.size(); ++i) {
-      lens[i] = (uint32_t)b.rec[sel[i]].seq_len;
-    }
-    return run_.vt.fastq_pack(run_.ctx, fq_, sel.data(), (uint32_t)sel.size(), reads);
-  }
-  bool failed() const { return failed_; }
-
-private:
-  struct Slot
-  {
-    enum State { FREE, READY } state = FREE;
-    size_t n = 0;          // bytes read
-    uint64_t file_off = 0; // stream offset of the first of them
-    bool eof = false;      // the data ends with this chunk
-    bool uploaded = false; // consumer's: the engine has been handed the body ahead of its parse (prefetch_next)
-    // BGZF: the n bytes are the text of these members, inflated by the consumer before their first use
-    std::vector<grp_bgzf_block> blocks; // tab_cap_ entries; comp_off inside the slot's compressed bytes
-    size_t n_blocks = 0, comp_n = 0;
-    uint64_t comp_file_off = 0;         // where the slot's compressed bytes begin in the file
-    bool inflated = false, bad = false; // consumer's
-    // a gzip index: the n bytes are the text of these segments (comp_bit inside the slot's compressed bytes, dict_off inside its histories)
-    std::vector<grp_gzip_segment> segs;
-    size_t n_segs = 0, dict_n = 0;
-  };
-  unsigned char* slot_dict(int i) { return reinterpret_cast<unsigned char*>(buf_.data()) + (size_t)kSlots * (front_ + chunk_ + comp_cap_) + (size_t)i * dict_cap_; }
-  char* slot_data(int i) { return buf_.data() + (size_t)i * (front_ + chunk_) + front_; }
-  unsigned char* slot_comp(int i) { return reinterpret_cast<unsigned char*>(buf_.data()) + (size_t)kSlots * (front_ + chunk_) + (size_t)i * comp_cap_; }
-  // the slot's members inflated into its text (once); false: the engine refused one of them
-  bool inflate_slot(int j)
-  {
-    Slot& sl = slot_[j];
-    if ((sl.n_blocks == 0 && sl.n_segs == 0) || sl.inflated) {
-      return !sl.bad;
-    }
-    sl.inflated = true;
-    uint32_t bad = UINT32_MAX;
-    if (sl.n_segs != 0) {
-      if (run_.ext.gzip_inflate(run_.ctx, slot_comp(j), sl.comp_n, slot_dict(j), sl.dict_n, sl.segs.data(), (uint32_t)sl.n_segs, slot_data(j), chunk_, &bad) != GRP_OK) {
-        sl.bad = true;
-        const uint64_t bit = sl.comp_file_off * 8 + (bad < sl.n_segs ? sl.segs[bad].comp_bit : 0);
-        note_input_failure("reading " + run_.opt.input + " failed: gzip segment " + (bad < sl.n_segs ? "" : "in the chunk ") + "at byte " + std::to_string(bit >> 3) + " (bit " + std::to_string(bit & 7) + "): " +
-                           (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
-        return false;
-      }
-      n_gzip_segs_ += sl.n_segs;
-      return true;
-    }
-    if (run_.ext.bgzf_inflate(run_.ctx, slot_comp(j), sl.comp_n, sl.blocks.data(), (uint32_t)sl.n_blocks, slot_data(j), chunk_, &bad) != GRP_OK) {
-      sl.bad = true;
-      uint64_t at = sl.comp_file_off; // the members of a slot follow each other
-      if (bad != UINT32_MAX && bad > 0 && bad < sl.n_blocks) {
-        at += sl.blocks[bad - 1].comp_off + sl.blocks[bad - 1].comp_len + 8;
-      }
-      note_input_failure("reading " + run_.opt.input + " failed: BGZF member " + (bad != UINT32_MAX ? "at byte " + std::to_string(at) : "in the chunk at byte " + std::to_string(at)) + ": " +
-                         (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
-      return false;
-    }
-    n_bgzf_blocks_ += sl.n_blocks;
-    return true;
-  }
-  // The reader's side of a BGZF file: whole members into slot i until its text (chunk_), its compressed bytes
-  // (comp_cap_) or its table (tab_cap_) is full.  Returns the bytes of text the members hold.  A member that is not BGZF
-  // hands the rest of the file to zlib (ztail_); a file that ends inside a member is an error, one that ends without
-  // the empty end-of-file member is not (zlib accepts it too).
-  size_t read_bgzf(int i, bool& eof)
-  {
-    constexpr size_t kPiece = size_t(16) << 20;
-    Slot& sl = slot_[i];
-    unsigned char* comp = slot_comp(i);
-    for (;;) { // (again only behind a table full of empty members)
-      size_t have = 0, pos = 0, text = 0, nb = 0;
-      bool full = false, file_end = false, other = false;
-      sl.comp_file_off = zoff_;
-      while (!full) {
-        if (!file_end && have < comp_cap_ && have - pos < BGZF_MAX_MEMBER) {
-          const size_t want = std::min(comp_cap_ - have, kPiece);
-          size_t k = 0;
-          while (k < want) {
-            const ssize_t r = pread(zfd_, comp + have + k, want - k, (off_t)(zoff_ + have + k));
-            if (r < 0 && errno == EINTR) {
-              continue;
-            }
-            if (r < 0) {
-              note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(zoff_ + have + k) + ": " + strerror(errno));
-            }
-            if (r <= 0) {
-              file_end = true;
-              break;
-            }
-            k += (size_t)r;
-          }
-          have += k;
-        }
-        int why = 1;
-        const size_t base = pos;
-        const size_t got = bgzf_scan(comp + base, have - base, &sl.blocks[nb], tab_cap_ - nb, nullptr, &why);
-        for (size_t t = 0; t < got; ++t) {
-          grp_bgzf_block& b = sl.blocks[nb]; // (comp_off: inside what was scanned)
-          if (text + b.text_len > chunk_) {
-            full = true;
-            break;
-          }
-          b.comp_off += base;
-          text += b.text_len;
-          pos = (size_t)b.comp_off + b.comp_len + 8;
-          ++nb;
-        }
-        if (full) {
-          break;
-        }
-        if (nb == tab_cap_) {
-          full = true;
-        } else if (why == 2) {
-          other = true;
-          break;
-        } else if (file_end) { // (why 0: bytes of a member are missing; 1: the members end with the file)
-          if (have > pos) {
-            note_input_failure("reading " + run_.opt.input + " failed: the file ends inside the BGZF member at byte " + std::to_string(zoff_ + pos) + " (truncated)");
-          }
-          eof = true;
-          break;
-        } else if (have == comp_cap_) {
-          full = true;
-        }
-      }
-      zoff_ += pos;
-      sl.n_blocks = nb;
-      sl.comp_n = pos;
-      if (other) {
-        // from this member on zlib reads, from a descriptor of its own that stands there
-        const int fd = ::open(run_.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
-        if (fd >= 0 && lseek(fd, (off_t)zoff_, SEEK_SET) == (off_t)zoff_) {
-          ztail_.reset(new InputFile(run_.opt.input, fd));
-        } else if (fd >= 0) {
-          ::close(fd);
-        }
-        if (!ztail_ || !ztail_->ok()) {
-          note_input_failure("reading " + run_.opt.input + " failed: cannot read on behind the BGZF members at byte " + std::to_string(zoff_));
-          ztail_.reset();
-          eof = true;
-        }
-      }
-      if (text != 0 || eof || other) {
-        return text;
-      }
-    }
-  }
-  // The reader's side of an indexed gzip file: whole segments into slot i until its text (chunk_), its compressed bytes
-  // (comp_cap_), its histories (dict_cap_) or its table (tab_cap_) is full; the compressed bytes of a slot are one range
-  // of the file (with the trailers and headers between two members in it).  Returns the bytes of text they hold.
-  size_t read_gzseg(int i, bool& eof)
-  {
-    const GzIndex& ix = *run_.gzidx;
-    Slot& sl = slot_[i];
-    if (gz_next_ >= ix.segs.size()) {
-      eof = true;
-      return 0;
-    }
-    const uint64_t byte0 = ix.segs[gz_next_].first_byte();
-    uint64_t end = byte0;
-    size_t text = 0, ns = 0, nd = 0;
-    while (gz_next_ + ns < ix.segs.size() && ns < tab_cap_) {
-      const GzSegment& g = ix.segs[gz_next_ + ns];
-      if (text + g.text_len > chunk_ || g.end_byte() - byte0 > comp_cap_ || nd + g.dict_len > dict_cap_) {
-        break; // (never the slot's first: the constructor has seen to that)
-      }
-      sl.segs[ns] = grp_gzip_segment{ g.comp_bit - byte0 * 8, g.n_bits, nd, g.dict_len, g.text_len, g.crc32, g.flags };
-      if (g.dict_len) {
-        memcpy(slot_dict(i) + nd, ix.dict(g), g.dict_len);
-      }
-      nd = (nd + g.dict_len + 3) & ~size_t(3);
-      text += g.text_len;
-      end = g.end_byte();
-      ++ns;
-    }
-    unsigned char* comp = slot_comp(i);
-    const size_t want = (size_t)(end - byte0);
-    size_t k = 0;
-    while (k < want) {
-      const ssize_t r = pread(zfd_, comp + k, want - k, (off_t)(byte0 + k));
-      if (r < 0 && errno == EINTR) {
-        continue;
-      }
-      if (r <= 0) {
-        note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(byte0 + k) + ": " + (r < 0 ? strerror(errno) : "the file ends in front of a segment of its index (it was written during the run)"));
-        eof = true;
-        return 0;
-      }
-      k += (size_t)r;
-    }
-    sl.comp_file_off = byte0;
-    sl.comp_n = want;
-    sl.n_segs = ns;
-    sl.dict_n = std::min(nd, dict_cap_);
-    gz_next_ += ns;
-    eof = gz_next_ == ix.segs.size();
-    return text;
-  }
-  void read_loop()
-  {
-    uint64_t off = 0;
-    for (int i = 0;; i = (i + 1) % kSlots) {
-      {
-        std::unique_lock<std::mutex> g(mu_);
-        cv_.wait(g, [&] { return stop_ || slot_[i].state == Slot::FREE; });
-        if (stop_) {
-          return;
-        }
-      }
-      size_t got = 0;
-      bool eof = false;
-      slot_[i].n_blocks = slot_[i].comp_n = 0; // (a FREE slot is the reader's)
-      slot_[i].inflated = slot_[i].bad = false;
-      slot_[i].n_segs = slot_[i].dict_n = 0;
-      if (bgzf_ && !ztail_) {
-        got = read_bgzf(i, eof);
-      } else if (gzseg_) {
-        got = read_gzseg(i, eof);
-      }
-      if (got == 0 && !eof && !gzseg_ && (!bgzf_ || ztail_)) {
-        slot_[i].n_blocks = slot_[i].comp_n = 0; // (empty members in front of the part zlib reads)
-        InputFile& in = ztail_ ? *ztail_ : in_;
-        while (!eof && got < chunk_) {
-          const size_t k = gzbuild_ ? gzbuild_->read(slot_data(i) + got, chunk_ - got) : in.read(slot_data(i) + got, chunk_ - got);
-          if (k == 0) {
-            eof = true;
-          }
-          got += k;
-        }
-        if (eof && gzbuild_ && gzbuild_->complete()) {
-          run_.gzidx = gzbuild_->take(); // (read by the next pass's source, which begins behind this thread's end)
-        }
-      }
-      {
-        std::lock_guard<std::mutex> g(mu_);
-        slot_[i].n = got;
-        slot_[i].file_off = off;
-        slot_[i].eof = eof;
-        slot_[i].state = Slot::READY;
-      }
-      cv_.notify_all();
-      off += got;
-      if (eof) {
-        return;
-      }
-    }
-  }
-  void release()
-  {
-    if (fq_) {
-      run_.vt.fastq_free(fq_);
-      fq_ = nullptr;
-    }
-  }
-  PathRun& run_;
-  InputFile in_;
-  std::vector<char> buf_;  // kSlots x [front | chunk]
-  uint64_t n_pre_[3] = { 0, 0, 0 }; // developer trace: chunks returned, next slot not ready, prefetches the engine took
-  double t_tr_[4] = { 0, 0, 0, 0 };  // developer trace: seconds waiting for the reader / in the parse call / in the prefetch calls / copying tails
-  std::vector<char> carry_; // unconsumed tail of the chunk before
-  std::vector<char> big_;
-  size_t chunk_ = 0, front_ = 0;
-  // a BGZF file: the reader's descriptor and how far it has come, the capacities of a slot beside its text, what
-  // follows the BGZF members (through zlib)
-  bool bgzf_ = false;
-  int zfd_ = -1;
-  uint64_t zoff_ = 0;
-  size_t comp_cap_ = 0, tab_cap_ = 0;
-  std::unique_ptr<InputFile> ztail_;
-  uint64_t n_bgzf_blocks_ = 0; // (developer trace)
-  // a plain gzip file: this pass builds the index (zlib on the reader thread), or it reads the segments of the run's index
-  std::unique_ptr<GzIndexReader> gzbuild_;
-  bool gzseg_ = false;
-  size_t gz_next_ = 0, dict_cap_ = 0;
-  uint64_t n_gzip_segs_ = 0;
-  bool pinned_ = false;
-  std::thread reader_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  // four chunk buffers (round 5; two before): the caller's batch lives in one, the bodies of the next two have been handed to
-  // the engine ahead (prefetch_next) and the reader fills the fourth
-  static constexpr int kSlots = 4;
-  Slot slot_[kSlots];
-  int take_ = 0;  // the slot the next chunk arrives in
-  int held_ = -1; // the slot the caller's current batch lives in
-  bool stop_ = false;
-  bool done_ = false, failed_ = false;
-  void* fq_ = nullptr;
-  std::vector<grp_fastq_record> meta_;
-};
-
-std::unique_ptr<RecordSource>
-open_source(PathRun& run)
-{
-  const bool gpu = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
-  if (gpu) {
-    return std::unique_ptr<RecordSource>(new GpuSource(run));
-  }
-  return std::unique_ptr<RecordSource>(new HostSource(run));
-}
 
 // goldrush_path.cpp:1109-1112 -> calc_ntcard_genome_size (ntcard.hpp:248-275): the
 // hash stream of EVERY record (no read filter) sampled on the device; the host only

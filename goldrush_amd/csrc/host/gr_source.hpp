@@ -1,0 +1,83 @@
+// The record sources of goldrush-path (gr_path.cpp): a pass over the input hands out batches of consecutive FASTQ
+// records, their Phred statistics and the selected ones as packed reads on the device.  HostSource reads and packs on
+// the host (engines without the ingest entry points); GpuSource hands raw text chunks to the engine (grpath_ingest.h),
+// from plain text, gzip through zlib, BGZF members or the segments of an indexed gzip file (gr_source.cpp).
+#pragma once
+#include "../../../include/grpath_host.h"
+#include "gr_gzidx.hpp"
+#include "gr_opts.hpp"
+
+#include <cstddef>
+#include <cstdint>
+#include <fstream>
+#include <iostream>
+#include <memory>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+namespace gr {
+
+double now_s(); // steady clock, seconds
+
+struct PathRun
+{
+  Opts opt;
+  grp_engine_vt vt{};
+  grp_engine_ext ext{}; // the optional entry points behind the table's 48 (gr_path_main_ext)
+  void* ctx = nullptr;
+  std::vector<std::string> seeds;
+  std::unordered_set<std::string> filter_out_reads;
+  std::ofstream out;
+  uint32_t world = 1, rank = 0; // ranks sharing the classification windows (one process per GPU)
+  // several ranks: every rank hashes the reads of its share of the batches into its bit vector, the
+  // vectors are OR-merged before the rank build (round 3: the CLI's fill is no longer replicated)
+  bool shard_fill = false;   // batch b belongs to rank b % world
+  bool merge_rccl = false;   // ... merged by RCCL inside the engine (else staged through host memory and /dev/shm)
+  void* shm = nullptr;       // gr_shm_allgather handle
+  int32_t device = -1;       // HIP device ordinal of this rank
+  // a plain gzip input: the restart points the first complete pass over it wrote down (gr_gzidx.hpp); the passes behind
+  // it inflate its segments on the device
+  std::shared_ptr<GzIndex> gzidx;
+
+  int fail_engine(const char* what)
+  {
+    std::cerr << "goldrush-path: " << what << ": " << (vt.last_error ? vt.last_error(ctx) : "engine error") << std::endl;
+    return 1;
+  }
+};
+
+// A batch of consecutive FASTQ records; offsets are relative to `text`.
+struct Rec
+{
+  size_t id_off, id_len, seq_off, seq_len, qual_off, qual_len;
+};
+
+struct Batch
+{
+  const char* text = nullptr;
+  uint64_t base_off = 0;            // offset of text[0] in the (decompressed) input stream
+  std::vector<Rec> rec;
+  std::vector<uint32_t> avg, delta; // calc_phred_average, valid where stats() ran
+  std::vector<uint8_t> non_acgt;    // find_first_not_of("ACGTacgt") != npos
+  bool seq_is_upper = false;        // the host reader folds case while copying
+  std::string id_str(size_t i) const { return std::string(text + rec[i].id_off, rec[i].id_len); }
+};
+
+class RecordSource
+{
+public:
+  virtual ~RecordSource() {}
+  virtual bool ok() const = 0;
+  virtual bool is_fastq() = 0;
+  virtual bool next(Batch& b) = 0;
+  // Phred statistics (and the ACGT check) of the records with seq_len >= min_len
+  virtual void stats(Batch& b, size_t min_len, bool need_acgt) = 0;
+  // the selected records as a batch of packed reads on the device
+  virtual int upload(Batch& b, const std::vector<uint32_t>& sel, std::vector<uint32_t>& lens, void** reads) = 0;
+};
+
+// GpuSource where the engine has the ingest entry points (GRP_HOST_INGEST: no), else HostSource
+std::unique_ptr<RecordSource> open_source(PathRun& run);
+
+} // namespace gr

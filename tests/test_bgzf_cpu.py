@@ -3,17 +3,13 @@ program (gr_path_main_ext) over the oracle engine with a zlib-backed stand-in fo
 table: a BGZF file, and a BGZF file followed by a plain gzip member, give the plain file's outputs, and the stand-in is
 handed every member exactly once per pass.  (tests/test_gpu_cli_bgzf.py does the same with the HIP engine.)"""
 import gzip
-import json
 import os
-import re
 import struct
-import subprocess
-import sys
-import textwrap
 
 import pytest
 
 import bgzf_cases as B
+import ext_runner as X
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -91,67 +87,13 @@ def test_scan_respects_the_table_capacity(host):
         assert blocks == B.walk_members(f)[0][:cap]
 
 
-RUNNER = textwrap.dedent("""
-    import ctypes as C, json, os, sys, zlib
-    import numpy as np
-    sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests")); sys.path.insert(0, os.path.join({root!r}, "oracle"))
-    import orc
-    from goldrush_amd import host, native
-    from oracle_engine import OracleCliEngine
-    eng = OracleCliEngine(orc, ingest=True)
-    calls = []
-
-    def bgzf_inflate(ctx, comp_p, n_comp, blocks_p, n, text_p, cap, bad_p):  # grp_bgzf_inflate through zlib
-        comp = C.string_at(comp_p, n_comp)
-        blocks = np.frombuffer(C.string_at(blocks_p, n * native.bgzf_block_dtype.itemsize), dtype=native.bgzf_block_dtype)
-        assert int(blocks["text_len"].sum()) <= cap
-        out, seen = [], []
-        for i, b in enumerate(blocks):
-            off, ln = int(b["comp_off"]), int(b["comp_len"])
-            assert off + ln <= n_comp
-            try:
-                t = zlib.decompress(comp[off:off + ln], -15)
-            except zlib.error:
-                t = None
-            if t is None or len(t) != int(b["text_len"]) or zlib.crc32(t) != int(b["crc32"]):
-                bad_p[0] = i
-                return -1
-            out.append(t)
-            seen.append([int(b["crc32"]), len(t)])
-        text = b"".join(out)
-        C.memmove(text_p, text, len(text))
-        calls.append(seen)
-        return 0
-
-    ext = host.grp_engine_ext()
-    ext.struct_size = C.sizeof(host.grp_engine_ext)
-    cb = host.BGZF_INFLATE_FN(bgzf_inflate)
-    if not os.environ.get("NO_EXT_INFLATE"):
-        ext.bgzf_inflate = cb
-    args = [b"goldrush_path"] + [a.encode() for a in sys.argv[1:]]
-    arr = (C.c_char_p * (len(args) + 1))(*args, None)
-    rc = host.load().gr_path_main_ext(len(args), arr, C.byref(eng.vt), C.byref(ext))
-    sys.stdout.flush(); sys.stderr.flush()
-    json.dump(calls, open(os.environ["CALLS_OUT"], "w"))
-    os._exit(rc)
-""")
-
-ARGS = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j2", "-d5", "-x10", "-s1011011110110111101101", "-g60000", "-b4", "-H600000", "--verbose",
-        "-P0", "-r0.9", "--silver_path", "-M3", "-m1500"]
-TRACE = re.compile(r"BGZF blocks inflated on the device (\d+)")
+TRACE = X.BGZF_TRACE
+_pick = X.pick
 
 
 def _run(tmp_path, tag, path, **env):
-    d = tmp_path / tag
-    d.mkdir()
-    script = tmp_path / "runner.py"
-    script.write_text(RUNNER.format(root=ROOT))
-    calls = str(d / "calls.json")
-    e = dict(os.environ, OMP_NUM_THREADS="2", GRP_TRACE_INGEST="1", CALLS_OUT=calls, **env)
-    e.pop("GRP_HOST_INGEST", None)
-    rp = subprocess.run([sys.executable, str(script)] + ARGS + ["-i", str(path), "-p", str(d / "out")], capture_output=True, text=True, timeout=900, env=e)
-    files = {f: open(d / f, "rb").read() for f in sorted(os.listdir(d)) if f != "calls.json"}
-    return rp, files, json.load(open(calls)) if os.path.exists(calls) else None
+    rp, files, calls = X.run(tmp_path, tag, path, ("bgzf",), **env)
+    return rp, files, calls and calls["bgzf"]
 
 
 @pytest.fixture(scope="module")
@@ -177,11 +119,6 @@ def plain_run(oracle, native, inputs, tmp_path_factory):
     return rp, files
 
 
-def _pick(stderr):
-    keep = ("Visited", "Saw:", "Assigned:", "Unassigned:", "Total queries", "Total hits", "Total misses", "Num reads", "m_filterSize", "num_", "Total reads skipped")
-    return [l for l in stderr.splitlines() if l.startswith(keep)]
-
-
 @pytest.mark.parametrize("name,chunk", [("bgzf", 0), ("bgzf", 4096), ("bgzf", 100000), ("no_eof_member", 70000), ("bgzf_then_gzip", 0), ("bgzf_then_gzip", 66000)])
 def test_host_program_inflates_bgzf_through_the_ext_table(oracle, native, tmp_path, inputs, plain_run, name, chunk):
     paths, data = inputs
@@ -199,6 +136,25 @@ def test_host_program_inflates_bgzf_through_the_ext_table(oracle, native, tmp_pa
     if chunk:  # a slot takes whole members up to its text capacity, max(chunk, 64 KiB)
         assert max(sum(b[1] for b in call) for call in calls) <= max(chunk, 65536)
         assert len(calls) > passes
+
+
+@pytest.mark.parametrize("name,chunk", [("bgzf_then_gzip", 66000), ("bgzf", 0)])
+def test_bgzf_comes_first_where_the_table_has_both_entries(oracle, native, tmp_path, inputs, plain_run, name, chunk):
+    """both stand-ins in the table: a BGZF file is still taken by the BGZF form, what follows its members by zlib, and the
+    gzip segments' entry is not called in any pass"""
+    paths, data = inputs
+    rp, files, calls = X.run(tmp_path, name, paths[name], ("bgzf", "gzip"), **({"GRP_INGEST_CHUNK": str(chunk)} if chunk else {}))
+    assert rp.returncode == 0, rp.stderr[-3000:]
+    assert files == plain_run[1]
+    assert _pick(rp.stderr) == _pick(plain_run[0].stderr)
+    members = [[crc, isize] for _, _, isize, crc in B.walk_members(data[name])[0]]
+    assert len(members) > 5
+    traced = [int(n) for n in TRACE.findall(rp.stderr)]
+    passes = len(traced)
+    assert passes >= 2 and traced == [len(members)] * passes, traced
+    assert [b for call in calls["bgzf"] for b in call] == members * passes
+    assert [int(n) for n in X.GZIP_TRACE.findall(rp.stderr)] == [0] * passes
+    assert calls["gzip"] == []
 
 
 def test_switch_and_missing_entry_point_take_the_zlib_path(oracle, native, tmp_path, inputs, plain_run):

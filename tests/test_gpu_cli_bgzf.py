@@ -4,11 +4,11 @@ damaged file ends the run with an error."""
 import gzip
 import os
 import re
-import subprocess
 
 import pytest
 
 import bgzf_cases as B
+from cli_runner import cli, traced, log as _log, run as _run  # noqa: F401 (cli: a fixture)
 from test_gpu_cli import _mk_fastq
 
 pytestmark = pytest.mark.gpu
@@ -18,14 +18,6 @@ SILVER = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j4", "-d5", "
 NTCARD = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j4", "-d5", "-x10", "-s1011011110110111101101", "-g150000", "-b4", "-P0", "-m0", "--ntcard", "--verbose"]
 TRACE = re.compile(r"BGZF blocks inflated on the device (\d+)")
 SIZES = [1, 65280, 7, 30011, 2, 64000, 513, 40000]  # text bytes per member: records straddle the members
-
-
-@pytest.fixture(scope="module")
-def cli(native):
-    from goldrush_amd import host as h
-
-    assert os.path.exists(h.CLI_PATH), "goldrush-path binary missing: run __graft_entry__.build()"
-    return h.CLI_PATH
 
 
 @pytest.fixture(scope="module")
@@ -50,22 +42,8 @@ def inputs(tmp_path_factory):
     return paths, len(blocks)
 
 
-def _run(cli, tmp_path_factory, args, path, **env):
-    d = tmp_path_factory.mktemp("run")
-    rp = subprocess.run([cli] + args + ["-i", path, "-p", str(d / "out")], capture_output=True, text=True, timeout=900, env=dict(os.environ, GRP_TRACE_INGEST="1", **env))
-    files = {f: open(d / f, "rb").read() for f in sorted(os.listdir(d))}
-    return rp, files
-
-
-def _log(rp, path):
-    """stderr without the timing lines (and the input's name)"""
-    return [l.replace(path, "INPUT") for l in rp.stderr.splitlines() if not (l.startswith("in ") or "(sec)" in l or l.startswith("GRP_TRACE_INGEST"))]
-
-
 def _traced(rp):
-    n = [int(x) for x in TRACE.findall(rp.stderr)]
-    assert n, "no GRP_TRACE_INGEST line"
-    return n
+    return traced(rp, TRACE)
 
 
 @pytest.fixture(scope="module")

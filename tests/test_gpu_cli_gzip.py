@@ -7,11 +7,11 @@ bytes: that index is unusable and every pass stays with zlib (the index itself s
 400 000 bytes hold one or two segments each."""
 import os
 import re
-import subprocess
 
 import pytest
 
 import gzip_cases as G
+from cli_runner import cli, traced, log as _log, run as _run  # noqa: F401 (cli: a fixture)
 from test_gpu_cli import _mk_fastq
 
 pytestmark = pytest.mark.gpu
@@ -20,14 +20,6 @@ SILVER = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j4", "-d5", "
           "--silver_path", "-M2", "-m3500", "--verbose"]
 NTCARD = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j4", "-d5", "-x10", "-s1011011110110111101101", "-g150000", "-b4", "-P0", "-m0", "--ntcard", "--verbose"]
 TRACE = re.compile(r"gzip segments inflated on the device (\d+)")
-
-
-@pytest.fixture(scope="module")
-def cli(native):
-    from goldrush_amd import host as h
-
-    assert os.path.exists(h.CLI_PATH), "goldrush-path binary missing: run __graft_entry__.build()"
-    return h.CLI_PATH
 
 
 @pytest.fixture(scope="module")
@@ -45,26 +37,8 @@ def inputs(tmp_path_factory):
     return paths
 
 
-def _run(cli, tmp_path_factory, args, path, **env):
-    d = tmp_path_factory.mktemp("run")
-    e = dict(os.environ, GRP_TRACE_INGEST="1", **env)
-    for k in ("GRP_GZIP_INDEX", "GRP_GZIP_SPAN", "GRP_GZIP_INDEX_MAX_GB", "GRP_INGEST_CHUNK"):
-        if k not in env:
-            e.pop(k, None)
-    rp = subprocess.run([cli] + args + ["-i", path, "-p", str(d / "out")], capture_output=True, text=True, timeout=900, env=e)
-    files = {f: open(d / f, "rb").read() for f in sorted(os.listdir(d))}
-    return rp, files
-
-
-def _log(rp, path):
-    """stderr without the timing lines (and the input's name)"""
-    return [l.replace(path, "INPUT") for l in rp.stderr.splitlines() if not (l.startswith("in ") or "(sec)" in l or l.startswith("GRP_TRACE_INGEST"))]
-
-
 def _traced(rp):
-    n = [int(x) for x in TRACE.findall(rp.stderr)]
-    assert n, "no GRP_TRACE_INGEST line"
-    return n
+    return traced(rp, TRACE)
 
 
 @pytest.fixture(scope="module")

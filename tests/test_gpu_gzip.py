@@ -1,14 +1,18 @@
-"""GPU: grp_gzip_inflate (csrc/grp_inflate.inc, k_gzip_inflate) — the segments of a serial DEFLATE stream inflated one wave
+"""GPU: grp_gzip_inflate (csrc/grp_inflate.inc, k_inflate<grp_gzip_segment>) — the segments of a serial DEFLATE stream inflated one wave
 per segment: a start at any bit, a preset history, an end at a block boundary, any amount of text.  The streams are those of
 tests/gzip_cases.py, the segments the index's (csrc/host/gr_gzidx.cpp; tests/test_gzip_index_cpu.py checks every one of them
-with zlib), the expectation is the text zlib inflates; every refused input is one zlib refuses too, or holds another text."""
+with zlib), the expectation is the text zlib inflates; every refused input is one zlib refuses too, or holds another text.
+The launcher, the buffer pool and the CRC32 tables are those of grp_bgzf_inflate (tests/test_gpu_bgzf.py): the last test
+mixes the two on one engine."""
 import zlib
 
 import numpy as np
 import pytest
 
+import bgzf_cases as B
 import gzip_cases as G
 from helpers import default_seeds
+from test_gpu_bgzf import _pack as _pack_members
 
 pytestmark = pytest.mark.gpu
 
@@ -176,3 +180,31 @@ def test_argument_errors_launch_nothing(eng, native, cases):
     assert eng.gzip_stats() == before
     assert eng.gzip_inflate(comp, hist, table) == text[:g0["text_len"] + g1["text_len"]]
     assert eng.gzip_inflate(b"", b"", []) == b""
+
+
+def test_segments_and_members_on_one_engine(native, cases):
+    """the two formats share the launcher and the CRC32 tables and have a pool each: calls of both on one engine, the
+    segments first, give zlib's texts, name the refused block and count their own work only"""
+    f, text, segs = cases["tiny_level1"]
+    ok = [(f, g) for g in segs[50000][:3]]
+    seg_text = text[:sum(g["text_len"] for _, g in ok)]
+    members = [B.confirm_good(p) + (p,) for p in (B.deflate(B.texts()[t], **B.FORMS[form]) for t, form in (("fastq", "level6"), ("bytes", "level1"), ("len257", "fixed")))]
+    items = [(p, len(t), crc) for t, crc, p in members]
+    e = native.Engine(22, 3, 1000, 1 << 20, default_seeds())
+    try:
+        comp, hist, table = _pack(ok, gap=2)
+        assert e.gzip_inflate(comp, hist, table) == seg_text
+        mcomp, blocks = _pack_members(items, gap=2)
+        assert e.bgzf_inflate(mcomp, blocks) == b"".join(t for t, _, _ in members)
+        assert e.gzip_inflate(comp, hist, table) == seg_text
+        bcomp, bblocks = _pack_members([items[0], B.refused()["wrong_crc"], items[2]], gap=2)
+        with pytest.raises(native.GrpError) as err:
+            e.bgzf_inflate(bcomp, bblocks)
+        assert err.value.code == native.GRP_ERR_INVALID and err.value.bad_block == 1 and "block 1" in str(err.value), str(err.value)
+        gs, bs = e.gzip_stats(), e.bgzf_stats()
+        assert (gs["segments"], gs["comp_bytes"], gs["text_bytes"]) == (6, 2 * len(comp), 2 * len(seg_text))
+        # (a call whose table passes the checks is counted, whatever its kernels find)
+        assert (bs["blocks"], bs["comp_bytes"], bs["text_bytes"]) == (6, len(mcomp) + len(bcomp), sum(b[2] for b in blocks + bblocks))
+        assert gs["kernel_us"] > 0 and bs["kernel_us"] > 0
+    finally:
+        e.close()

@@ -5,19 +5,14 @@ whole host program (gr_path_main_ext) over the oracle engine with a zlib-backed 
 engine table: the outputs are the plain file's, the stand-in is handed every segment exactly once, in order, in each pass
 behind the one that built the index.  (tests/test_gpu_gzip.py and test_gpu_cli_gzip.py do the same with the HIP engine.)"""
 import gzip
-import json
 import os
-import re
-import subprocess
-import sys
-import textwrap
 import zlib
 
 import pytest
 
+import ext_runner as X
 import gzip_cases as G
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["tiny_level1", "tiny_level6", "tiny_level9", "fixed", "stored", "flushed", "acgt", "distance_32768", "two_members_and_an_empty_one", "bgzf"]
 ONE_MEMBER = ("flushed", "stored", "acgt", "distance_32768", "fixed")
 
@@ -159,73 +154,15 @@ def test_reader_hands_out_what_gzread_hands_out(host, cases, tmp_path):
         assert not failed or len(ix["text"]) < len(text) or tag == "cut_in_trailer"
 
 
-RUNNER = textwrap.dedent("""
-    import ctypes as C, json, os, sys, zlib
-    import numpy as np
-    sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests")); sys.path.insert(0, os.path.join({root!r}, "oracle"))
-    import orc
-    import gzip_cases as G
-    from goldrush_amd import host, native
-    from oracle_engine import OracleCliEngine
-    eng = OracleCliEngine(orc, ingest=True)
-    calls = []
-
-    def gzip_inflate(ctx, comp_p, n_comp, dict_p, n_dict, segs_p, n, text_p, cap, bad_p):  # grp_gzip_inflate through zlib
-        comp, hist = C.string_at(comp_p, n_comp), C.string_at(dict_p, n_dict)
-        segs = np.frombuffer(C.string_at(segs_p, n * native.gzip_segment_dtype.itemsize), dtype=native.gzip_segment_dtype)
-        assert int(segs["text_len"].sum()) <= cap
-        out, seen = [], []
-        for i, g in enumerate(segs):
-            bit, nb, do, dl = int(g["comp_bit"]), int(g["n_bits"]), int(g["dict_off"]), int(g["dict_len"])
-            assert bit + nb <= 8 * n_comp and do + dl <= n_dict and dl <= 32768
-            try:
-                t, eof = G.inflate_segment(comp, bit, nb, hist[do:do + dl])
-            except zlib.error:
-                t = None
-            if t is None or len(t) != int(g["text_len"]) or zlib.crc32(t) != int(g["crc32"]) or eof != bool(int(g["flags"]) & 1):
-                bad_p[0] = i
-                return -1
-            out.append(t)
-            seen.append([int(g["crc32"]), len(t)])
-        text = b"".join(out)
-        C.memmove(text_p, text, len(text))
-        calls.append(seen)
-        return 0
-
-    ext = host.grp_engine_ext()
-    ext.struct_size = C.sizeof(host.grp_engine_ext)
-    cb = host.GZIP_INFLATE_FN(gzip_inflate)
-    if os.environ.get("OLD_EXT"):  # a caller from before the entry point: its table ends in front of it
-        ext.struct_size = host.grp_engine_ext.gzip_inflate.offset
-    elif not os.environ.get("NO_EXT_INFLATE"):
-        ext.gzip_inflate = cb
-    args = [b"goldrush_path"] + [a.encode() for a in sys.argv[1:]]
-    arr = (C.c_char_p * (len(args) + 1))(*args, None)
-    rc = host.load().gr_path_main_ext(len(args), arr, C.byref(eng.vt), C.byref(ext))
-    sys.stdout.flush(); sys.stderr.flush()
-    json.dump(calls, open(os.environ["CALLS_OUT"], "w"))
-    os._exit(rc)
-""")
-
-ARGS = ["-k22", "-w16", "-t500", "-u5", "-a1", "-o0.1", "-h3", "-j2", "-d5", "-x10", "-s1011011110110111101101", "-g60000", "-b4", "-H600000", "--verbose",
-        "-P0", "-r0.9", "--silver_path", "-M3", "-m1500"]
-TRACE = re.compile(r"gzip segments inflated on the device (\d+)")
-BGZF_TRACE = re.compile(r"BGZF blocks inflated on the device (\d+)")
+ARGS = X.ARGS  # (the same list: run() sees what a test appends)
+TRACE = X.GZIP_TRACE
+BGZF_TRACE = X.BGZF_TRACE
+_pick = X.pick
 
 
 def _run(tmp_path, tag, path, **env):
-    d = tmp_path / tag
-    d.mkdir()
-    script = tmp_path / "runner.py"
-    script.write_text(RUNNER.format(root=ROOT))
-    calls = str(d / "calls.json")
-    e = dict(os.environ, OMP_NUM_THREADS="2", GRP_TRACE_INGEST="1", CALLS_OUT=calls, **env)
-    for k in ("GRP_HOST_INGEST", "GRP_GZIP_INDEX", "GRP_GZIP_SPAN", "GRP_GZIP_INDEX_MAX_GB"):
-        if k not in env:
-            e.pop(k, None)
-    rp = subprocess.run([sys.executable, str(script)] + ARGS + ["-i", str(path), "-p", str(d / "out")], capture_output=True, text=True, timeout=900, env=e)
-    files = {f: open(d / f, "rb").read() for f in sorted(os.listdir(d)) if f != "calls.json"}
-    return rp, files, json.load(open(calls)) if os.path.exists(calls) else None
+    rp, files, calls = X.run(tmp_path, tag, path, ("gzip",), **env)
+    return rp, files, calls and calls["gzip"]
 
 
 @pytest.fixture(scope="module")
@@ -237,11 +174,6 @@ def plain_run(oracle, native, cases, tmp_path_factory):
     assert rp.returncode == 0 and files and any(files.values()), rp.stderr[-2000:]
     assert calls == [] and TRACE.findall(rp.stderr) and {int(n) for n in TRACE.findall(rp.stderr)} == {0}
     return rp, files
-
-
-def _pick(stderr):
-    keep = ("Visited", "Saw:", "Assigned:", "Unassigned:", "Total queries", "Total hits", "Total misses", "Num reads", "m_filterSize", "num_", "Total reads skipped")
-    return [l for l in stderr.splitlines() if l.startswith(keep)]
 
 
 @pytest.mark.parametrize("name,span,chunk,ntcard", [("tiny_level6", 1, 0, False), ("tiny_level6", 50000, 100000, False), ("tiny_level1", 50000, 100000, True), ("two_members_and_an_empty_one", 1, 100000, False),

@@ -5,7 +5,7 @@
 //   python tools/dev/inflate_host_cases.py /tmp/inflate_cases.bin
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -w tools/dev/inflate_host_check.cpp goldrush_amd/csrc/host/gr_gzidx.cpp goldrush_amd/csrc/host/gr_fastq.cpp -lz -o /tmp/inflate_host_check
 //   /tmp/inflate_host_check /tmp/inflate_cases.bin
-// The segment form (k_gzip_inflate) with the index that feeds it, on plain gzip files (tests/gzip_cases.py writes its streams):
+// The segment form (k_inflate<grp_gzip_segment>) with the index that feeds it, on plain gzip files (tests/gzip_cases.py writes its streams):
 //   python tests/gzip_cases.py /tmp/gzip_cases && /tmp/inflate_host_check --gzip /tmp/gzip_cases/*.gz
 // every file is read through GzIndexReader (csrc/host/gr_gzidx.cpp) at spans 1, 50 000 and 10^9; every segment is inflated by
 // zlib on its own (inflatePrime + inflateSetDictionary) and by the decoder, at two alignments of the output, with buffers
@@ -88,7 +88,7 @@ static int gzip_main(int argc, char** argv)
           char* out = outw.data() + (mis ? 3 : 0);
           memset(outw.data(), 0x55, outw.size());
           memset(&g_s, 0xAA, sizeof g_s);
-          const uint32_t st = inf_segment(g_s, comp, dict, e, out);
+          const uint32_t st = inf_entry(g_s, comp, dict, e, out);
           if (st != 0 || memcmp(out, text.data() + off, g.text_len) != 0) { printf("%s span %llu seg %zu mis %d: status %u (%s) or text differs\n", argv[a], (unsigned long long)span, i, mis, st, INF_STATUS_TEXT[st]); ++bad; continue; }
           if ((uint8_t)out[g.text_len] != 0x55 && !(mis == 0 && g.text_len + 1 >= outw.size())) { printf("%s seg %zu: wrote behind the text\n", argv[a], i); ++bad; }
           if (crc_member(g_cs, tabs, out, g.text_len) != g.crc32) { printf("%s span %llu seg %zu: crc differs\n", argv[a], (unsigned long long)span, i); ++bad; }
@@ -115,7 +115,7 @@ static int gzip_main(int argc, char** argv)
             uint64_t fbit = 0;
             if (flip[q] >= 0) { fbit = d.comp_bit + (uint64_t)flip[q]; comp[fbit >> 3] ^= (uint8_t)(1u << (fbit & 7)); }
             memset(&g_s, 0xAA, sizeof g_s);
-            const uint32_t st = inf_segment(g_s, comp, dict, d, o2.data());
+            const uint32_t st = inf_entry(g_s, comp, dict, d, o2.data());
             if (flip[q] >= 0) { comp[fbit >> 3] ^= (uint8_t)(1u << (fbit & 7)); }
             if ((uint8_t)o2[d.text_len] != 0x55) { printf("%s seg %zu form %zu: wrote behind the text\n", argv[a], i, q); ++bad; }
             if (st != 0) { ++n_refused; continue; }
@@ -156,7 +156,7 @@ int main(int argc, char** argv)
     for (int mis = 0; mis < 2; ++mis) {
       char* out = outw.data() + (mis ? 3 : 0);
       memset(outw.data(), 0x55, outw.size());
-      const uint32_t st = inf_member(s, comp, pre, comp_len, out, text_len);
+      const uint32_t st = inf_entry(s, comp, nullptr, grp_bgzf_block{ pre, comp_len, text_len, crc, 0 }, out);
       if (ok) {
         if (st != 0 || memcmp(out, text.data(), text_len) != 0) { printf("case %u mis %d: status %u (%s) or text differs\n", c, mis, st, INF_STATUS_TEXT[st]); ++bad; continue; }
         if ((uint8_t)out[text_len] != 0x55) { printf("case %u: wrote behind the text\n", c); ++bad; }
