@@ -117,7 +117,7 @@ batch_unit_jb(const DevBatch& b, uint32_t unit, uint32_t parts)
 // several seeds live across unrolled claim loops loses touches of the last seed with this hipcc.  The guard:
 // tests/test_gpu_batch.py::test_claim_loops_keep_every_touch (this kernel: [batch]).
 // The query line of a probe's unit is read by the lane's QUAD — one 64-byte request that brings header AND ID slot
-// (the query's access, quad_answer; rounds 2 - 4 loaded 16 bytes of header and 4 bytes of slot per lane: round 5's matrix,
+// (the query's access, quad_decode; rounds 2 - 4 loaded 16 bytes of header and 4 bytes of slot per lane: round 5's matrix,
 // profiles/r05_collect_matrix.txt).
 template<int H, int WT>
 __global__ void __launch_bounds__(THREADS)
@@ -156,16 +156,14 @@ k_batch_collect(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint3
   const Probe pr = grp_locate(f, seed_hash_t<WT>(sTab, sd, s, window_at(sBases, boff + fs)));
   uint32_t lr, rel, bit, qid = 0;
   {
-    const uint32_t sub = threadIdx.x & 3u, quad_base = (threadIdx.x & 63u) & ~3u;
-    const uint4 p0 = f.buckets[quad_bcast64<0>(pr.b) * GRP_UNIT_U4 + sub];
-    const uint4 p1 = f.buckets[quad_bcast64<1>(pr.b) * GRP_UNIT_U4 + sub];
-    const uint4 p2 = f.buckets[quad_bcast64<2>(pr.b) * GRP_UNIT_U4 + sub];
-    const uint4 p3 = f.buckets[quad_bcast64<3>(pr.b) * GRP_UNIT_U4 + sub];
-    const QuadAnswer a0 = quad_answer<0>(p0, pr.off, quad_base);
-    const QuadAnswer a1 = quad_answer<1>(p1, pr.off, quad_base);
-    const QuadAnswer a2 = quad_answer<2>(p2, pr.off, quad_base);
-    const QuadAnswer a3 = quad_answer<3>(p3, pr.off, quad_base);
-    const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+    const QuadLane ql = quad_lane();
+    const uint32_t pbytes = quad_piece_bytes(ql.sub);
+    uint4 pc[4];
+    pc[0] = quad_load<0>(f.buckets, pr.b, pbytes);
+    pc[1] = quad_load<1>(f.buckets, pr.b, pbytes);
+    pc[2] = quad_load<2>(f.buckets, pr.b, pbytes);
+    pc[3] = quad_load<3>(f.buckets, pr.b, pbytes);
+    const QuadAnswer mine = quad_decode(pc, pr.off, ql);
     lr = mine.lr;
     rel = mine.rel;
     bit = mine.bit;

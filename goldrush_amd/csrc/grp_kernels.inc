@@ -515,9 +515,133 @@ struct QuadAnswer
   uint32_t rel; // bucket's relative rank (for the overflow table)
 };
 
-// Round G: `piece` is this lane's 16 bytes of the bucket probed by quad lane G,
-// `off` this lane's OWN bit offset (lane G's is broadcast).  Every lane of the
-// quad computes lane G's answer; lane G keeps it.
+// The quad read of a probe's 64-byte line: round G reads the bucket of quad lane G's probe, four lanes x 16 bytes in one
+// instruction.  Two piece orders:
+//  - ROTATED (quad_load / quad_decode): quad lane L loads piece quad_piece<G>(L) = (L - G) & 3.  The request is the same
+//    line, but the header piece (piece 0: {rel, bitmap lo, bitmap hi, ids[0]}) of lane G's probe arrives in lane G
+//    ITSELF, in its round-G registers: a lane decodes only its own probe, once, and only the ID word crosses lanes.
+//  - STRAIGHT (quad_answer_straight): lane L loads piece L, the header always arrives in quad lane 0 and every lane of
+//    the quad runs the whole decode for all four rounds (four DPP broadcasts, shift, popcount, slot arithmetic each) to
+//    keep one of the four results.  More instructions, a few registers fewer in some instantiations: quad_rotated()
+//    says which k_query forms stay on it.
+// The rotated form leans on this hipcc's code generation in three places (bit_select, quad_opaque, quad_load).  When the
+// toolchain moves, re-check with tools/dev/kernel_resources.py against profiles/r10_quad_kernel_resources.txt: the row of
+// k_query<3, 1, 0, true, false, false> (168 VGPRs, no VGPR spill, no scratch: three workgroups per CU) first, then the
+// waves per SIMD of the forms quad_rotated() lists.
+template<int G>
+__device__ inline uint32_t
+quad_piece(uint32_t sub)
+{
+  return (sub - (uint32_t)G) & 3u;
+}
+
+// the four rounds' piece offsets in bytes, one per byte of a word: ONE register across the kernel (quad_load extracts
+// its round's byte)
+__device__ inline uint32_t
+quad_piece_bytes(uint32_t sub)
+{
+  return (quad_piece<0>(sub) << 4) | (quad_piece<1>(sub) << 12) | (quad_piece<2>(sub) << 20) | (quad_piece<3>(sub) << 28);
+}
+
+// Round G's 16 bytes of bucket b's line for this lane, rotated order.  The offset is extracted by a VOLATILE asm so that
+// it stays at the load: as four plain values the offsets are hoisted out of the pass loop and held as 64-bit address
+// parts in up to eight registers, which the streaming form does not have (VGPRs spilled) and which cost the many-seed
+// forms a wave.
+template<int G>
+__device__ inline uint4
+quad_load(const uint4* buckets, uint64_t b, uint32_t piece_bytes)
+{
+  uint32_t o;
+  asm volatile("v_bfe_u32 %0, %1, %2, 8" : "=v"(o) : "v"(piece_bytes), "n"(8 * G));
+  return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(buckets) + (quad_bcast64<G>(b) * (GRP_UNIT_U4 * 16u) + o));
+}
+
+// (a & m) | (b & ~m) in one instruction.  The selects of the exchange go through lane masks held in registers (0 / ~0):
+// written as `c ? a : b` over words that come straight from the bucket loads, hipcc turns each select into a branch
+// over exec so as to sink the load's wait into it (four branches a word); written as and / or, it distributes the nest
+// into six masks and ten instructions a word.  Hence the instruction itself.
+__device__ inline uint32_t
+bit_select(uint32_t m, uint32_t a, uint32_t b)
+{
+  uint32_t r;
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+  return r;
+}
+
+// a mask the optimiser cannot see through (an empty asm): it would otherwise recognise 0 / ~0 as a sign-extended
+// condition and turn the bit_select back into the select it replaces
+__device__ inline uint32_t
+quad_opaque(uint32_t m)
+{
+  asm("" : "+v"(m));
+  return m;
+}
+
+// a lane's place in its quad: constants of the kernel
+struct QuadLane
+{
+  uint32_t sub;        // quad lane: threadIdx.x & 3
+  uint32_t quad_base;  // first lane of the quad inside the wave
+  uint32_t m0, m1, m2; // ~0 where sub == 0 / 1 / 2
+};
+
+__device__ inline QuadLane
+quad_lane()
+{
+  QuadLane q;
+  q.sub = threadIdx.x & 3u;
+  q.quad_base = (threadIdx.x & 63u) & ~3u;
+  q.m0 = quad_opaque(q.sub == 0u ? ~0u : 0u);
+  q.m1 = quad_opaque(q.sub == 1u ? ~0u : 0u);
+  q.m2 = quad_opaque(q.sub == 2u ? ~0u : 0u);
+  return q;
+}
+
+// the value of round `sub`: a lane's own round (a register select, no exchange)
+__device__ inline uint32_t
+quad_own(const QuadLane& q, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3)
+{
+  return bit_select(q.m0, v0, bit_select(q.m1, v1, bit_select(q.m2, v2, v3)));
+}
+
+// Round G of the ID exchange: `slot` is the lane's own ID slot (dword index inside its bucket), lane G's is broadcast
+// (the one DPP move of the round); every lane picks that component of its round-G piece, and lane G pulls the word
+// from the lane that holds the slot's piece (`src`, its own byte address for ds_bpermute).  Lane G keeps the result.
+template<int G>
+__device__ inline uint32_t
+quad_id_round(const uint4& piece, uint32_t slot, int src)
+{
+  const uint32_t sg = quad_bcast<G>(slot);
+  const uint32_t c0 = quad_opaque((uint32_t)((int32_t)(sg << 31) >> 31)); // ~0 where the component's bit 0 / bit 1 is set
+  const uint32_t c1 = quad_opaque((uint32_t)((int32_t)(sg << 30) >> 31));
+  const uint32_t word = bit_select(c1, bit_select(c0, piece.w, piece.z), bit_select(c0, piece.y, piece.x));
+  return (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)word);
+}
+
+// `pc[G]` is this lane's piece of round G (loaded in quad_piece order), `off` its OWN probe's bit offset.  The header
+// is the piece of the lane's own round; bit, local rank, rel and the slot 3 + min(lr, 12) are computed once.  Only the
+// ID word crosses lanes: piece p = slot >> 2 of lane G's line is held by quad lane (G + p) & 3 (for G = sub: `src`,
+// the same in all four rounds; slot 3, ids[0], is the lane's own header piece and needs no special case).
+__device__ __forceinline__ QuadAnswer
+quad_decode(const uint4 (&pc)[4], uint32_t off, const QuadLane& q)
+{
+  const uint64_t bm = (uint64_t)quad_own(q, pc[0].y, pc[1].y, pc[2].y, pc[3].y) | ((uint64_t)quad_own(q, pc[0].z, pc[1].z, pc[2].z, pc[3].z) << 32);
+  QuadAnswer a;
+  a.rel = quad_own(q, pc[0].x, pc[1].x, pc[2].x, pc[3].x);
+  a.bit = (uint32_t)((bm >> off) & 1ull);
+  a.lr = grp_local_rank(bm, off);
+  const uint32_t slot = 3u + min(a.lr, GRP_BUCKET_IDS - 1u); // dword index inside the bucket
+  const int src = (int)((q.quad_base + ((q.sub + (slot >> 2)) & 3u)) << 2);
+  const uint32_t r0 = quad_id_round<0>(pc[0], slot, src);
+  const uint32_t r1 = quad_id_round<1>(pc[1], slot, src);
+  const uint32_t r2 = quad_id_round<2>(pc[2], slot, src);
+  const uint32_t r3 = quad_id_round<3>(pc[3], slot, src);
+  a.id = quad_own(q, r0, r1, r2, r3);
+  return a;
+}
+
+// The straight order.  Round G: `piece` is this lane's 16 bytes (piece `sub`) of the bucket probed by quad lane G, `off`
+// this lane's OWN bit offset (lane G's is broadcast).  Every lane of the quad computes lane G's answer; lane G keeps it.
 template<int G>
 __device__ inline QuadAnswer
 quad_answer(const uint4& piece, uint32_t off, uint32_t quad_base)
@@ -536,6 +660,63 @@ quad_answer(const uint4& piece, uint32_t off, uint32_t quad_base)
   return a;
 }
 
+__device__ __forceinline__ QuadAnswer
+quad_answer_straight(const uint4 (&pc)[4], uint32_t off, const QuadLane& q)
+{
+  const QuadAnswer a0 = quad_answer<0>(pc[0], off, q.quad_base);
+  const QuadAnswer a1 = quad_answer<1>(pc[1], off, q.quad_base);
+  const QuadAnswer a2 = quad_answer<2>(pc[2], off, q.quad_base);
+  const QuadAnswer a3 = quad_answer<3>(pc[3], off, q.quad_base);
+  const uint32_t sub = q.sub;
+  QuadAnswer a; // (field by field: a select between whole structs ends in scratch memory here)
+  a.bit = (sub == 0) ? a0.bit : (sub == 1) ? a1.bit : (sub == 2) ? a2.bit : a3.bit;
+  a.lr = (sub == 0) ? a0.lr : (sub == 1) ? a1.lr : (sub == 2) ? a2.lr : a3.lr;
+  a.id = (sub == 0) ? a0.id : (sub == 1) ? a1.id : (sub == 2) ? a2.id : a3.id;
+  a.rel = (sub == 0) ? a0.rel : (sub == 1) ? a1.rel : (sub == 2) ? a2.rel : a3.rel;
+  return a;
+}
+
+// one round's load / a probe's answer in the order a kernel form is compiled for
+template<bool ROT, int G>
+__device__ __forceinline__ uint4
+quad_read(const uint4* buckets, uint64_t b, const QuadLane& q, uint32_t piece_bytes)
+{
+  if constexpr (ROT) {
+    return quad_load<G>(buckets, b, piece_bytes);
+  } else {
+    return buckets[quad_bcast64<G>(b) * GRP_UNIT_U4 + q.sub];
+  }
+}
+
+template<bool ROT>
+__device__ __forceinline__ QuadAnswer
+quad_result(const uint4 (&pc)[4], uint32_t off, const QuadLane& q)
+{
+  if constexpr (ROT) {
+    return quad_decode(pc, off, q);
+  } else {
+    return quad_answer_straight(pc, off, q);
+  }
+}
+
+// Which k_query forms read in rotated order.  All do but those that lose a wave per SIMD to it with this hipcc (a few
+// VGPRs across an allocation boundary, tools/dev/kernel_resources.py) and were not shown to run faster for it: the
+// global-table redo forms <3,1,-1,false,false,true> (96 -> 98 VGPRs), <3,1,0,false,true,true> (128 -> 130),
+// <4,1,0,false,false,true> (127 -> 129) and <16,1,0,false,false,true> (247 -> 264), which run for the few flagged
+// tiles only and cannot be timed in a workload.  (<4,1,0,false,false,false>, 127 -> 129, and <16,1,0,false,false,false>,
+// 246 -> 264, lose a wave as well and run faster rotated: the query kernels of an h = 4 stream by 4 %, of an h = 16
+// stream by 6 %, DESIGN.md 4.)
+template<int H, int FR, int WT, bool ST, bool VER, bool GT>
+constexpr bool
+quad_rotated()
+{
+  if (GT && !ST && FR == 1) {
+    if ((H == 3 && WT == -1 && !VER) || (H == 3 && WT == 0 && VER) || (H == 4 && WT == 0 && !VER) || (H > GRP_H_GROUP && WT == 0 && !VER)) {
+      return false;
+    }
+  }
+  return true;
+}
 // ---- query -------------------------------------------------------------------------
 
 // per-tile count table in LDS: open addressing, key = ID (0 = empty).  An
@@ -2579,14 +2760,18 @@ k_query(DevFilter f,
     // (multiLensfrHashIterator.hpp:49-68): its frame index is clamped
     last[s] = Lp - sd->span[s];
   }
-  const uint32_t sub = threadIdx.x & 3u;         // my 16-byte piece of a bucket
-  const uint32_t quad_base = (threadIdx.x & 63u) & ~3u;
+  const QuadLane ql = quad_lane();
+  constexpr bool ROT = quad_rotated<H, FR, WT, ST, VER, GT>();
+  const uint32_t pbytes = quad_piece_bytes(ql.sub); // round g loads piece (sub - g) & 3 of a bucket
 
   // Every lane owns FR frames per pass; the 64-byte bucket of each probe is
-  // read by the lane's quad with ONE coalesced access (4 x 16 B) and the bitmap /
-  // ID slot are exchanged inside the quad with DPP / bpermute.  Random 16-byte
-  // loads issued per lane run at ~27 G/s on MI355X, quad-coalesced bucket reads
-  // at ~48 G buckets/s (tools/gather_bench.hip modes 7 / 10).
+  // read by the lane's quad with ONE coalesced access (4 x 16 B), the pieces
+  // rotated so that a probe's header arrives in the lane that owns the probe:
+  // the lane decodes bitmap, rank and slot itself, once, and only the ID word
+  // is exchanged inside the quad (one DPP move + one bpermute per round,
+  // quad_decode).  Random 16-byte loads issued per lane run at ~27 G/s on
+  // MI355X, quad-coalesced bucket reads at ~48 G buckets/s, in either piece
+  // order (tools/gather_bench.hip modes 7 / 10, 24 / 28).
   // Frames of a pass.  Seeds that share their halves (DevSeeds::n_left): a frame's right halves
   // serve the H - 1 frames in front of it, handed over by wave shuffles — so the first three waves
   // of a workgroup end on H - 1 helper lanes (they compute the halves of the next wave's first
@@ -2725,10 +2910,10 @@ k_query(DevFilter f,
       for (int j = 0; j < FR; ++j) {
 #pragma unroll
         for (int s = 0; s < H; ++s) {
-          piece[j][s][0] = f.buckets[quad_bcast64<0>(bk[j][s]) * GRP_UNIT_U4 + sub];
-          piece[j][s][1] = f.buckets[quad_bcast64<1>(bk[j][s]) * GRP_UNIT_U4 + sub];
-          piece[j][s][2] = f.buckets[quad_bcast64<2>(bk[j][s]) * GRP_UNIT_U4 + sub];
-          piece[j][s][3] = f.buckets[quad_bcast64<3>(bk[j][s]) * GRP_UNIT_U4 + sub];
+          piece[j][s][0] = quad_read<ROT, 0>(f.buckets, bk[j][s], ql, pbytes);
+          piece[j][s][1] = quad_read<ROT, 1>(f.buckets, bk[j][s], ql, pbytes);
+          piece[j][s][2] = quad_read<ROT, 2>(f.buckets, bk[j][s], ql, pbytes);
+          piece[j][s][3] = quad_read<ROT, 3>(f.buckets, bk[j][s], ql, pbytes);
         }
       }
       uint64_t bk_next[PIPE ? FR : 1][PIPE ? H : 1];
@@ -2749,11 +2934,7 @@ k_query(DevFilter f,
         bool vneed[VER ? H : 1], vamb[VER ? H : 1];
 #pragma unroll
         for (int s = 0; s < H; ++s) {
-          QuadAnswer a0 = quad_answer<0>(piece[j][s][0], off[j][s], quad_base);
-          QuadAnswer a1 = quad_answer<1>(piece[j][s][1], off[j][s], quad_base);
-          QuadAnswer a2 = quad_answer<2>(piece[j][s][2], off[j][s], quad_base);
-          QuadAnswer a3 = quad_answer<3>(piece[j][s][3], off[j][s], quad_base);
-          const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+          const QuadAnswer mine = quad_result<ROT>(piece[j][s], off[j][s], ql);
           all = all && mine.bit; // atRank (MIBloomFilter.hpp:465-476)
           uint32_t d = mine.id;  // getData (:614-621)
 
@@ -2843,10 +3024,10 @@ k_query(DevFilter f,
         for (int q = 0; q < GRP_H_GROUP; ++q) {
           const int s = gi * GRP_H_GROUP + q;
           if (seed_on<H>(s, hn)) {
-            piece[q][0] = f.buckets[quad_bcast64<0>(bk[0][s]) * GRP_UNIT_U4 + sub];
-            piece[q][1] = f.buckets[quad_bcast64<1>(bk[0][s]) * GRP_UNIT_U4 + sub];
-            piece[q][2] = f.buckets[quad_bcast64<2>(bk[0][s]) * GRP_UNIT_U4 + sub];
-            piece[q][3] = f.buckets[quad_bcast64<3>(bk[0][s]) * GRP_UNIT_U4 + sub];
+            piece[q][0] = quad_read<ROT, 0>(f.buckets, bk[0][s], ql, pbytes);
+            piece[q][1] = quad_read<ROT, 1>(f.buckets, bk[0][s], ql, pbytes);
+            piece[q][2] = quad_read<ROT, 2>(f.buckets, bk[0][s], ql, pbytes);
+            piece[q][3] = quad_read<ROT, 3>(f.buckets, bk[0][s], ql, pbytes);
           }
         }
 #pragma unroll
@@ -2855,11 +3036,7 @@ k_query(DevFilter f,
           if (!seed_on<H>(s, hn)) {
             continue;
           }
-          QuadAnswer a0 = quad_answer<0>(piece[q][0], off[0][s], quad_base);
-          QuadAnswer a1 = quad_answer<1>(piece[q][1], off[0][s], quad_base);
-          QuadAnswer a2 = quad_answer<2>(piece[q][2], off[0][s], quad_base);
-          QuadAnswer a3 = quad_answer<3>(piece[q][3], off[0][s], quad_base);
-          const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+          const QuadAnswer mine = quad_result<ROT>(piece[q], off[0][s], ql);
           all = all && mine.bit; // atRank (MIBloomFilter.hpp:465-476): over all h seeds of the frame
           uint32_t d = mine.id;  // getData (:614-621)
           if (mine.lr >= GRP_BUCKET_IDS && live) {

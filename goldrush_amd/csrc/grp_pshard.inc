@@ -98,21 +98,19 @@ k_ps_partition(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32
 __global__ void __launch_bounds__(THREADS)
 k_ps_gather(DevFilter f, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ answers, uint64_t n)
 {
-  const uint32_t sub = threadIdx.x & 3u, quad_base = (threadIdx.x & 63u) & ~3u;
+  const QuadLane ql = quad_lane();
+  const uint32_t pbytes = quad_piece_bytes(ql.sub);
   for (uint64_t i0 = (uint64_t)blockIdx.x * THREADS; i0 < n; i0 += (uint64_t)gridDim.x * THREADS) {
     const uint64_t i = i0 + threadIdx.x;
     const unsigned long long key = i < n ? keys[i] : 0ull; // (lanes beyond the bin read bucket 0: the quad exchange needs every lane)
     const uint64_t b = key >> 6;
     const uint32_t off = (uint32_t)(key & 63ull);
-    const uint4 p0 = f.buckets[quad_bcast64<0>(b) * GRP_UNIT_U4 + sub];
-    const uint4 p1 = f.buckets[quad_bcast64<1>(b) * GRP_UNIT_U4 + sub];
-    const uint4 p2 = f.buckets[quad_bcast64<2>(b) * GRP_UNIT_U4 + sub];
-    const uint4 p3 = f.buckets[quad_bcast64<3>(b) * GRP_UNIT_U4 + sub];
-    const QuadAnswer a0 = quad_answer<0>(p0, off, quad_base);
-    const QuadAnswer a1 = quad_answer<1>(p1, off, quad_base);
-    const QuadAnswer a2 = quad_answer<2>(p2, off, quad_base);
-    const QuadAnswer a3 = quad_answer<3>(p3, off, quad_base);
-    const QuadAnswer mine = (sub == 0) ? a0 : (sub == 1) ? a1 : (sub == 2) ? a2 : a3;
+    uint4 pc[4];
+    pc[0] = quad_load<0>(f.buckets, b, pbytes);
+    pc[1] = quad_load<1>(f.buckets, b, pbytes);
+    pc[2] = quad_load<2>(f.buckets, b, pbytes);
+    pc[3] = quad_load<3>(f.buckets, b, pbytes);
+    const QuadAnswer mine = quad_decode(pc, off, ql);
     uint32_t d = mine.id;
     if (mine.lr >= GRP_BUCKET_IDS && mine.bit) { // 14th.. set bit of its bucket: rare side table
       d = grp_ovf_get(f, f.super[b >> GRP_SUPER_SHIFT] + mine.rel + mine.lr);

@@ -43,6 +43,8 @@
 //            bit 5: the header through two agent-scope 8-byte loads; bit 6: ID store skipped (a touch that does not write)
 //   mode 24: mode 10's quad read of a 64-B line where the lines lie 128 B apart (the query on the unit layout)
 //   mode 25: one 128-B unit read whole by 8 lanes, one lane writes 4 B into each half
+//   mode 28: mode 24 with the quad's pieces rotated per round (lane L loads piece (L - g) & 3 of quad lane g's line): the
+//            load order of quad_decode, where a probe's header arrives in the lane that owns the probe
 //   mode 26: like 21 with the count word in a SEPARATE line of a bucket-indexed table B (64 B per bucket, same index)
 // usage: gather_bench <tableA_MiB> <tableB_MiB> <items_per_lane> <mode> [unroll] [workgroups]
 #include <hip/hip_runtime.h>
@@ -390,6 +392,20 @@ __global__ void __launch_bounds__(256) k_gather(const uint4* __restrict__ A, uin
           uint4 t = A[idx * 8 + sub];
           const uint32_t want = (uint32_t)(idx >> 3) % 4u;
           uint32_t got = __shfl(t.w, (lane / 4) * 4 + want, 64);
+          if (sub == g) acc += got + t.x;
+        }
+      }
+    } else if (mode == 28) { // mode 24 with the pieces ROTATED: in round g lane L loads piece (L - g) & 3, so lane g gets its own line's header
+      const uint64_t nu = nA / 8;
+      const int lane = threadIdx.x & 63;
+      const int sub = lane & 3;
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        for (int g = 0; g < 4; ++g) {
+          const uint64_t idx = __shfl(ia[u], (lane / 4) * 4 + g, 64) % nu;
+          uint4 t = A[idx * 8 + ((sub - g) & 3)];
+          const uint32_t want = (uint32_t)(idx >> 3) % 4u; // the piece that holds the word asked for: in quad lane (g + want) & 3
+          uint32_t got = __shfl(t.w, (lane / 4) * 4 + (int)((g + want) & 3u), 64);
           if (sub == g) acc += got + t.x;
         }
       }
