@@ -6,6 +6,8 @@
 //                               check (ballot)
 //   k_fq_phred                  one lane per record: left-to-right double Phred sums
 //   k_fq_pack                   2 bits per base for the selected records
+//   k_bam_records / k_bam_pack  the same table and the same packed words from unaligned BAM records
+//                               (grp_bam_parse: the record chain is walked on the host, host/gr_bam.hpp)
 
 #include "../../include/grpath_ingest.h"
 
@@ -314,11 +316,165 @@ k_fq_pack(const uint8_t* __restrict__ text, const uint64_t* __restrict__ seq_off
   }
 }
 
+// ---- unaligned BAM records (host/gr_bam.hpp) ---------------------------------------------------------------------------
+// The host has walked the record chain (a pointer chase of 4-byte reads: one lane's work, and the bytes are in host
+// memory) and checked every record's fields against its block: these kernels take a record's offset and trust its fixed
+// part.  Every load lies inside the record's own name, bases or qualities, at whatever alignment the name left them.
+constexpr uint32_t BAM_BAD_QUAL = 0x40000000u; // a quality byte above 93 (0xFF: absent): no FASTQ character
+
+// all eight 4-bit codes of a word are A, C, G or T (1, 2, 4, 8: one bit set)?
+__device__ inline bool
+bam_acgt8(uint32_t x)
+{
+  uint32_t p = x - ((x >> 1) & 0x55555555u);
+  p = (p & 0x33333333u) + ((p >> 2) & 0x33333333u); // bits set, per code
+  return p == 0x11111111u;
+}
+
+// one of the four bytes of a word is above 93?
+__device__ inline bool
+bam_qual4_bad(uint32_t x)
+{
+  return ((((x & 0x7F7F7F7Fu) + 0x22222222u) | x) & 0x80808080u) != 0u; // (94 + 0x22 = 0x80; no carry between bytes)
+}
+
+// this lane's share of a test over the bytes [s0, e0): 16 bytes per lane and load over the aligned middle (as k_fq_records'
+// ACGT test), single bytes in front of it and behind it
+template<class ByteBad, class WordBad>
+__device__ inline bool
+bam_scan_bad(const uint8_t* __restrict__ text, uint64_t s0, uint64_t e0, uint32_t lane, ByteBad byte_bad, WordBad word_bad)
+{
+  bool bad = false;
+  const uint64_t a0 = (s0 + 15u) & ~(uint64_t)15, a1 = e0 & ~(uint64_t)15; // the aligned middle [a0, a1)
+  if (a0 < a1) {
+    for (uint64_t b = s0 + lane; b < a0; b += 64) {
+      bad = bad || byte_bad(text[b]);
+    }
+    for (uint64_t b = a0 + (uint64_t)lane * 16u; b < a1; b += 64u * 16u) {
+      const uint4 v = *reinterpret_cast<const uint4*>(text + b);
+      bad = bad || word_bad(v.x) || word_bad(v.y) || word_bad(v.z) || word_bad(v.w);
+    }
+    for (uint64_t b = a1 + lane; b < e0; b += 64) {
+      bad = bad || byte_bad(text[b]);
+    }
+  } else {
+    for (uint64_t b = s0 + lane; b < e0; b += 64) {
+      bad = bad || byte_bad(text[b]);
+    }
+  }
+  return bad;
+}
+
+// one wave per record: the table entry from the fixed 32 bytes, the name's length, the ACGT test over the 4-bit codes and
+// the range test over the qualities.  rec_off[r] = the record's block_size field, counted from `text` like every offset
+// written here (the caller takes `lead` off).
+__global__ void __launch_bounds__(THREADS)
+k_bam_records(const uint8_t* __restrict__ text, const uint64_t* __restrict__ rec_off, uint64_t n_records, grp_fastq_record* __restrict__ out)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t r = (uint64_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+  if (r >= n_records) {
+    return;
+  }
+  const uint64_t o = rec_off[r];
+  const uint8_t* f = text + o + 4; // refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, ... (little endian, unaligned)
+  const uint32_t l_name = f[8];
+  const uint32_t n_cigar = (uint32_t)f[12] | ((uint32_t)f[13] << 8);
+  const uint32_t l_seq = (uint32_t)f[16] | ((uint32_t)f[17] << 8) | ((uint32_t)f[18] << 16) | ((uint32_t)f[19] << 24);
+  const uint64_t name = o + 4 + gr::BAM_FIXED;
+  // id = the name up to its NUL (the host has seen it at l_name - 1), cut at the first whitespace like a FASTQ header
+  uint32_t id_len = l_name - 1;
+  for (uint32_t base = 0; base < l_name; base += 64) { // (l_read_name is one byte: four rounds at the most)
+    const uint32_t i = base + lane;
+    bool stop = false;
+    if (i < l_name) {
+      const uint8_t ch = text[name + i];
+      stop = ch == 0 || ch == ' ' || (ch >= 9 && ch <= 13);
+    }
+    const unsigned long long m = __ballot(stop);
+    if (m != 0ull) {
+      id_len = base + (uint32_t)__ffsll((long long)m) - 1u;
+      break;
+    }
+  }
+  grp_fastq_record rec;
+  rec.flags = 0;
+  rec.id_off = name;
+  rec.id_len = id_len;
+  rec.seq_off = name + l_name + 4ull * n_cigar;
+  rec.seq_len = l_seq;
+  rec.qual_off = rec.seq_off + ((uint64_t)l_seq + 1) / 2;
+  rec.qual_len = l_seq;
+  // the ACGT test over the l_seq / 2 whole bytes; the last base of an odd length is the high code of the byte behind them,
+  // whose low code is padding the specification leaves undefined
+  const uint64_t whole = rec.seq_off + l_seq / 2;
+  bool bad = bam_scan_bad(
+    text, rec.seq_off, whole, lane, [](uint8_t b) { return __popc(b >> 4) != 1 || __popc(b & 15u) != 1; }, [](uint32_t w) { return !bam_acgt8(w); });
+  if ((l_seq & 1u) && lane == 0) {
+    bad = bad || __popc(text[whole] >> 4) != 1;
+  }
+  const bool qbad = bam_scan_bad(
+    text, rec.qual_off, rec.qual_off + l_seq, lane, [](uint8_t b) { return b > gr::BAM_MAX_QUAL; }, [](uint32_t w) { return bam_qual4_bad(w); });
+  if (__ballot(bad) != 0ull) {
+    rec.flags |= GRP_FQ_NON_ACGT;
+  }
+  if (__ballot(qbad) != 0ull) {
+    rec.flags |= BAM_BAD_QUAL;
+  }
+  // (the Phred sums: k_fq_phred over qual_off / qual_len, with the table of raw qualities)
+  rec.phred_sum = 0.0;
+  rec.phred_first = 0.0;
+  if (lane == 0) {
+    out[r] = rec;
+  }
+}
+
+// 16 bases of 4-bit codes (8 bytes, the first base in the high half of the first byte) as a word of grp_reads: 1, 2, 4, 8
+// -> 0, 1, 2, 3, base j at bits 2j
+__device__ inline uint32_t
+bam_pack16(uint64_t x)
+{
+  const uint64_t c = ((x >> 1) & 0x7777777777777777ull) - ((x >> 3) & 0x1111111111111111ull); // per code: 1, 2, 4, 8 -> 0, 1, 2, 3 (never a borrow: n >> 1 >= n >> 3)
+  uint64_t t = ((c >> 4) & 0x0303030303030303ull) | ((c & 0x0303030303030303ull) << 2);      // per byte: its two bases in the low four bits
+  t = (t | (t >> 4)) & 0x00FF00FF00FF00FFull;
+  t = (t | (t >> 8)) & 0x0000FFFF0000FFFFull;
+  return (uint32_t)(t | (t >> 16));
+}
+
+// one workgroup per selected record (k_fq_pack's geometry); a word's 8 source bytes begin wherever the name left them
+__global__ void __launch_bounds__(THREADS)
+k_bam_pack(const uint8_t* __restrict__ text, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ len, const uint64_t* __restrict__ word_off, uint32_t* __restrict__ packed)
+{
+  const uint32_t r = blockIdx.x;
+  const uint8_t* src = text + seq_off[r];
+  const uint32_t n = len[r];
+  const uint32_t nw = (n + 15u) / 16u;
+  uint32_t* dst = packed + word_off[r];
+  for (uint32_t w = threadIdx.x; w < nw; w += THREADS) {
+    const uint32_t cnt = min(16u, n - w * 16u);
+    const uint8_t* s = src + (uint64_t)w * 8u;
+    uint64_t x = 0;
+    if (cnt == 16u) {
+      __builtin_memcpy(&x, s, 8);
+    } else { // the record's last word: its (cnt + 1) / 2 bytes and not one more
+      for (uint32_t j = 0; j < (cnt + 1u) / 2u; ++j) {
+        x |= (uint64_t)s[j] << (8u * j);
+      }
+    }
+    uint32_t v = bam_pack16(x);
+    if (cnt < 16u) {
+      v &= (1u << (2u * cnt)) - 1u; // (the padding code behind an odd length is not a base)
+    }
+    dst[w] = v;
+  }
+}
+
 } // namespace
 
 struct grp_fastq
 {
   grp_ctx* ctx = nullptr;
+  bool bam = false; // the chunk holds BAM records (grp_bam_parse): seq_off = 4-bit codes, packed by k_bam_pack
   uint8_t* d_text = nullptr; // 16-byte aligned; the text begins `lead` bytes behind it
   DevBuf<uint8_t> own_text;  // what d_text points into where no slot of the context was free
   uint32_t lead = 0;
@@ -349,37 +505,19 @@ ingest_stage(grp_ctx* c, uint64_t front_bytes, uint64_t rec_bytes)
   return GRP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
+// The bytes of a chunk into one of the context's text buffers, for grp_fastq_parse and grp_bam_parse alike: the slot (or a
+// buffer of the handle's own), the body that a prefetch has brought up already, the copy on the side stream, and the
+// main stream made to wait for it.  fq->d_text / lead / pool_slot say where the bytes are.
 int
-grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, int* stopped)
+ingest_upload(grp_ctx* c, grp_fastq* fq, const char* text, uint64_t n_bytes, const char* who)
 {
-  if (!c || !out || !n_records || !bytes_consumed || (!text && n_bytes)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_fastq_parse: bad argument");
-  }
-  *out = nullptr;
-  *n_records = 0;
-  *bytes_consumed = 0;
-  if (stopped) {
-    *stopped = 0;
-  }
-  if (n_bytes >= (1ull << 36)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_fastq_parse: chunk too large");
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  grp_fastq* fq = new grp_fastq();
-  fq->ctx = c;
-  fq->n_bytes = n_bytes;
-  if (n_bytes == 0) {
-    *out = fq;
-    return GRP_OK;
-  }
-  auto fail = [&](int code) {
-    grp_fastq_free(fq);
-    return code;
-  };
+#define ING_TRY(expr)                                                                                                  \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess) {                                                                                            \
+      return set_err(c, GRP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                                   \
+    }                                                                                                                  \
+  } while (0)
   bool prefetched = false; // the text's body is already on the device (or on its way on the side stream): grp_fastq_prefetch
   uint64_t front_len = 0;  // prefetched: the bytes of `text` in front of that body, uploaded here
   uint64_t dev_off = 0;    // offset of text[0] in its slot
@@ -425,8 +563,8 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
         (void)hipStreamSynchronize(c->stream3);
         const uint64_t want = FQ_FRONT + n_bytes + n_bytes / 8 + 64;
         if (ip.text[i].reset(want) != hipSuccess) {
-          set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: allocating %llu bytes of device memory failed", (unsigned long long)want);
-          return fail(GRP_ERR_NOMEM);
+          set_err(c, GRP_ERR_NOMEM, "%s: allocating %llu bytes of device memory failed", who, (unsigned long long)want);
+          return GRP_ERR_NOMEM;
         }
       }
       slot = i;
@@ -438,32 +576,12 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
       fq->d_text = ip.text[slot] + (dev_off & ~(uint64_t)15);
       fq->lead = (uint32_t)(dev_off & 15u);
     } else if (fq->own_text.reset(n_bytes + 64) != hipSuccess) {
-      set_err(c, GRP_ERR_NOMEM, "grp_fastq_parse: allocating %llu bytes of device memory failed", (unsigned long long)n_bytes);
-      return fail(GRP_ERR_NOMEM);
+      set_err(c, GRP_ERR_NOMEM, "%s: allocating %llu bytes of device memory failed", who, (unsigned long long)n_bytes);
+      return GRP_ERR_NOMEM;
     } else {
       fq->d_text = fq->own_text;
     }
   }
-  // table of the host's pow() values (calc_phred_average.cpp:21-24)
-  if (!c->d_delog) {
-    double tab[256];
-    for (int ch = 0; ch < 256; ++ch) {
-      const int q = (int)((char)ch - 33);
-      tab[ch] = std::pow(10.0, -q / 10.0);
-    }
-    if (c->d_delog.reset(256) != hipSuccess || hipMemcpy(c->d_delog, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) {
-      set_err(c, GRP_ERR_HIP, "grp_fastq_parse: cannot set up the Phred table");
-      return fail(GRP_ERR_HIP);
-    }
-  }
-#define FQ_TRY(expr)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess) {                                                                                            \
-      set_err(c, GRP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                                          \
-      return fail(GRP_ERR_HIP);                                                                                        \
-    }                                                                                                                  \
-  } while (0)
   // The whole parse runs on the SIDE stream (round 5): the caller has usually just queued the fill of the chunk
   // before on the main stream without waiting for it, and the copy (a DMA out of the page-locked chunk buffer), the
   // line scan and the record extraction of this chunk run beside it — the waits below are for the side stream alone,
@@ -473,32 +591,94 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
   // not the host.
   hipStream_t ps = c->stream2;
   if (!c->ingest.uploaded) {
-    FQ_TRY(c->ingest.uploaded.create(hipEventDisableTiming));
+    ING_TRY(c->ingest.uploaded.create(hipEventDisableTiming));
   }
   const uint32_t lead = fq->lead;
-  const uint64_t n_total = lead + n_bytes; // what the kernels see: the slot's 16-byte group the text begins in, from its start
   if (fq->pool_slot >= 0 && c->ingest.text_up[fq->pool_slot]) {
     // the last body copied into this slot ahead of its parse (this chunk's — or a dropped one's, still on its way)
-    FQ_TRY(hipStreamWaitEvent(ps, c->ingest.text_up[fq->pool_slot], 0));
+    ING_TRY(hipStreamWaitEvent(ps, c->ingest.text_up[fq->pool_slot], 0));
   }
   if (!prefetched) {
     if (fq->pool_slot >= 0 && c->ingest.text_done[fq->pool_slot]) {
-      FQ_TRY(hipStreamWaitEvent(ps, c->ingest.text_done[fq->pool_slot], 0));
+      ING_TRY(hipStreamWaitEvent(ps, c->ingest.text_done[fq->pool_slot], 0));
     }
-    FQ_TRY(hipMemcpyAsync(fq->d_text, text, n_bytes, hipMemcpyHostToDevice, ps));
-    FQ_TRY(hipMemsetAsync(fq->d_text + n_bytes, 0, 64, ps));
+    ING_TRY(hipMemcpyAsync(fq->d_text, text, n_bytes, hipMemcpyHostToDevice, ps));
+    ING_TRY(hipMemsetAsync(fq->d_text + n_bytes, 0, 64, ps));
   } else if (front_len) {
     // the body is in place (or arriving): the tail of the chunk before goes in front of it — by a kernel out of a mapped
     // staging buffer (see k_ing_bytes)
     if (ingest_stage(c, front_len, 0) != GRP_OK) {
-      return fail(GRP_ERR_HIP);
+      return GRP_ERR_HIP;
     }
     memcpy(c->ingest.h_front, text, front_len);
     k_ing_bytes<<<dim3((uint32_t)std::min<uint64_t>((front_len + THREADS - 1) / THREADS, 64)), dim3(THREADS), 0, ps>>>(fq->d_text + lead, c->ingest.h_front.dev, front_len);
-    FQ_TRY(hipGetLastError());
+    ING_TRY(hipGetLastError());
   }
-  FQ_TRY(hipEventRecord(c->ingest.uploaded, ps));
-  FQ_TRY(hipStreamWaitEvent(c->stream, c->ingest.uploaded, 0)); // what the main stream does with this chunk (pack) comes behind its text
+  ING_TRY(hipEventRecord(c->ingest.uploaded, ps));
+  ING_TRY(hipStreamWaitEvent(c->stream, c->ingest.uploaded, 0)); // what the main stream does with this chunk (pack) comes behind its text
+  return GRP_OK;
+#undef ING_TRY
+}
+
+// 10^(-q/10) for the byte that stands for quality q: the host's pow() values (calc_phred_average.cpp:21-24).  FASTQ text
+// holds q + 33 (shift 33), a BAM record holds q itself (shift 0): the same values, 33 entries apart.
+int
+ingest_phred_table(grp_ctx* c, DevBuf<double>& d_tab, int shift, const char* who)
+{
+  if (!d_tab) {
+    double tab[256];
+    for (int ch = 0; ch < 256; ++ch) {
+      const int q = shift ? (int)((char)ch - shift) : ch;
+      tab[ch] = std::pow(10.0, -q / 10.0);
+    }
+    if (d_tab.reset(256) != hipSuccess || hipMemcpy(d_tab, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) {
+      return set_err(c, GRP_ERR_HIP, "%s: cannot set up the Phred table", who);
+    }
+  }
+  return GRP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int
+grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, int* stopped)
+{
+  if (!c || !out || !n_records || !bytes_consumed || (!text && n_bytes)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_fastq_parse: bad argument");
+  }
+  *out = nullptr;
+  *n_records = 0;
+  *bytes_consumed = 0;
+  if (stopped) {
+    *stopped = 0;
+  }
+  if (n_bytes >= (1ull << 36)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_fastq_parse: chunk too large");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  grp_fastq* fq = new grp_fastq();
+  fq->ctx = c;
+  fq->n_bytes = n_bytes;
+  if (n_bytes == 0) {
+    *out = fq;
+    return GRP_OK;
+  }
+  auto fail = [&](int code) {
+    grp_fastq_free(fq);
+    return code;
+  };
+  if (ingest_phred_table(c, c->d_delog, 33, "grp_fastq_parse") != GRP_OK) {
+    return fail(GRP_ERR_HIP);
+  }
+  const int urc = ingest_upload(c, fq, text, n_bytes, "grp_fastq_parse");
+  if (urc != GRP_OK) {
+    return fail(urc);
+  }
+  hipStream_t ps = c->stream2;
+  const uint32_t lead = fq->lead;
+  const uint64_t n_total = lead + n_bytes; // what the kernels see: the slot's 16-byte group the text begins in, from its start
   const uint64_t n_blocks = (n_total + NL_BLOCK_BYTES - 1) / NL_BLOCK_BYTES;
   grp_ctx::IngestPool& ip = c->ingest; // scratch of this call, kept for the next chunk
   auto cleanup = [&]() {};
@@ -582,9 +762,111 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
     FQ_TRY2(hipStreamSynchronize(ps));
   }
   cleanup();
-#undef FQ_TRY
 #undef FQ_TRY2
   *n_records = fq->rec.size();
+  *out = fq;
+  return GRP_OK;
+}
+
+int
+grp_bam_parse(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset)
+{
+  if (!c || !out || !n_records || !bytes_consumed || !bad_offset || (!bytes && n_bytes)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_bam_parse: bad argument");
+  }
+  *out = nullptr;
+  *n_records = 0;
+  *bytes_consumed = 0;
+  *bad_offset = 0;
+  if (n_bytes >= (1ull << 36)) {
+    return set_err(c, GRP_ERR_INVALID, "grp_bam_parse: chunk too large");
+  }
+  // the record chain, on the host (gr_bam.hpp): where the complete records begin, or the record that is refused
+  std::vector<uint64_t> offs;
+  uint64_t used = 0, bad = 0;
+  const char* why = nullptr;
+  if (gr::bam_walk(reinterpret_cast<const uint8_t*>(bytes), n_bytes, final_chunk != 0, &used, &bad, &why, [&](const gr::BamRecord& r) {
+        offs.push_back(r.off);
+        return true;
+      }) != 0) {
+    *bad_offset = bad;
+    return set_err(c, GRP_ERR_INVALID, "%s", why);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  grp_fastq* fq = new grp_fastq();
+  fq->ctx = c;
+  fq->bam = true;
+  fq->n_bytes = n_bytes;
+  *bytes_consumed = used;
+  if (n_bytes == 0) {
+    *out = fq;
+    return GRP_OK;
+  }
+  auto fail = [&](int code) {
+    grp_fastq_free(fq);
+    *bytes_consumed = 0;
+    return code;
+  };
+#define BAM_TRY(expr)                                                                                                  \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess) {                                                                                            \
+      set_err(c, GRP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                                          \
+      return fail(GRP_ERR_HIP);                                                                                        \
+    }                                                                                                                  \
+  } while (0)
+  if (ingest_phred_table(c, c->d_delog_raw, 0, "grp_bam_parse") != GRP_OK) {
+    return fail(GRP_ERR_HIP);
+  }
+  // (all of `bytes` goes up, complete records or not: a body uploaded ahead is this chunk's whatever the walk found)
+  const int urc = ingest_upload(c, fq, bytes, n_bytes, "grp_bam_parse");
+  if (urc != GRP_OK) {
+    return fail(urc);
+  }
+  hipStream_t ps = c->stream2; // the side stream, as grp_fastq_parse
+  const uint64_t n_rec = offs.size();
+  if (n_rec) {
+    grp_ctx::IngestPool& ip = c->ingest;
+    if (n_rec > ip.h_bam_off.cap) {
+      BAM_TRY(hipStreamSynchronize(ps));
+      BAM_TRY(ip.h_bam_off.reset(n_rec + n_rec / 4 + 512, hipHostMallocMapped | hipHostMallocCoherent));
+    }
+    if (ingest_stage(c, 0, n_rec * sizeof(grp_fastq_record)) != GRP_OK) {
+      return fail(GRP_ERR_HIP);
+    }
+    if (n_rec * sizeof(grp_fastq_record) > ip.d_rec.cap) {
+      BAM_TRY(ip.d_rec.reset((n_rec + n_rec / 4 + 64) * sizeof(grp_fastq_record)));
+    }
+    // the walk's table goes up beside the bytes: the kernels read it out of page-locked, device-mapped memory (see k_ing_bytes)
+    for (uint64_t i = 0; i < n_rec; ++i) {
+      ip.h_bam_off[i] = offs[i] + fq->lead;
+    }
+    grp_fastq_record* const d_rec = reinterpret_cast<grp_fastq_record*>(ip.d_rec.p);
+    k_bam_records<<<dim3((uint32_t)((n_rec + (THREADS / 64) - 1) / (THREADS / 64))), dim3(THREADS), 0, ps>>>(fq->d_text, ip.h_bam_off.dev, n_rec, d_rec);
+    k_fq_phred<<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog_raw, d_rec);
+    BAM_TRY(hipGetLastError());
+    const uint64_t rec_words = n_rec * sizeof(grp_fastq_record) / 8;
+    k_ing_words<<<dim3((uint32_t)std::min<uint64_t>((rec_words + THREADS - 1) / THREADS, 256)), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.h_rec.dev), reinterpret_cast<const unsigned long long*>(d_rec), rec_words);
+    BAM_TRY(hipGetLastError());
+    BAM_TRY(hipStreamSynchronize(ps));
+    fq->rec.resize(n_rec);
+    memcpy(fq->rec.data(), ip.h_rec, n_rec * sizeof(grp_fastq_record));
+    for (uint64_t i = 0; i < n_rec; ++i) {
+      grp_fastq_record& rr = fq->rec[i];
+      rr.id_off -= fq->lead; // the caller's offsets count from bytes[0]
+      rr.seq_off -= fq->lead;
+      rr.qual_off -= fq->lead;
+      if (rr.flags & BAM_BAD_QUAL) {
+        *bad_offset = offs[i];
+        set_err(c, GRP_ERR_INVALID, "a quality without a FASTQ character (absent: 0xFF, or above 93)");
+        return fail(GRP_ERR_INVALID);
+      }
+    }
+  } else {
+    BAM_TRY(hipStreamSynchronize(ps));
+  }
+#undef BAM_TRY
+  *n_records = n_rec;
   *out = fq;
   return GRP_OK;
 }
@@ -733,7 +1015,11 @@ grp_fastq_pack(grp_ctx* c, grp_fastq* fq, const uint32_t* sel, uint32_t n_sel, g
     return bail(set_err(c, GRP_ERR_HIP, "grp_fastq_pack: upload failed: %s", hipGetErrorString(e)));
   }
   if (n_sel) {
-    k_fq_pack<<<dim3(n_sel), dim3(THREADS), 0, c->stream>>>(fq->d_text + fq->lead, d_so, d_len, d_word_off, rd->d_packed);
+    if (fq->bam) {
+      k_bam_pack<<<dim3(n_sel), dim3(THREADS), 0, c->stream>>>(fq->d_text + fq->lead, d_so, d_len, d_word_off, rd->d_packed);
+    } else {
+      k_fq_pack<<<dim3(n_sel), dim3(THREADS), 0, c->stream>>>(fq->d_text + fq->lead, d_so, d_len, d_word_off, rd->d_packed);
+    }
     if (hipGetLastError() != hipSuccess) {
       return bail(set_err(c, GRP_ERR_HIP, "grp_fastq_pack: kernel launch failed"));
     }

@@ -21,6 +21,7 @@
 #include "grp_device.h"
 #include "host/gr_tile_geom.hpp"
 #include "host/gr_tiles_core.hpp"
+#include "host/gr_bam.hpp"
 
 #include "../../include/grpath.h"
 #include "../../include/grpath_ingest.h"
@@ -274,6 +275,7 @@ struct grp_ctx : CtxStreams
   uint32_t comm_world = 1, comm_rank = 0;
   uint32_t n_comm_merges = 0; // grp_bv_merge_ranks calls that succeeded
   DevBuf<double> d_delog; // 10^(-Q/10) table for the FASTQ ingest
+  DevBuf<double> d_delog_raw; // ... and for BAM records, whose quality bytes are Q itself (the same values, 33 entries apart)
   // buffers of the FASTQ ingest, kept between chunks (round 4: a chunk used to pay seven hipMalloc / hipFree pairs,
   // 256 MiB of text among them — every hipFree waits for the device)
   struct IngestPool
@@ -293,6 +295,7 @@ struct grp_ctx : CtxStreams
     DevBuf<uint32_t> d_counts;
     DevBuf<uint64_t> d_base, d_super, d_total, d_nl;
     DevBuf<uint8_t> d_rec; // grp_fastq_record[], in bytes
+    HostBuf<uint64_t> h_bam_off; // ... page-locked, device-mapped staging of that table
     Event uploaded; // the chunk's text has arrived (copied on the side stream, beside the fill of the chunk before)
     // page-locked, device-mapped staging of a parse (grp_ingest.inc: ingest_stage): [0] newlines, [1] end of the last record
     HostBuf<uint64_t> h_scal;

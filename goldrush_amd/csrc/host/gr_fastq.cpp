@@ -1,4 +1,5 @@
 #include "gr_fastq.hpp"
+#include "gr_bam.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -98,6 +99,21 @@ clear_input_failure()
   std::lock_guard<std::mutex> g(g_fail_mu);
   g_failed = false;
   g_fail_what.clear();
+}
+
+void
+note_bam_failure(const std::string& path, uint64_t off, const char* why)
+{
+  note_input_failure("reading " + path + " failed: BAM record at byte " + std::to_string(off) + " of the decompressed stream: " + (why ? why : "refused"));
+}
+
+int
+input_format(const unsigned char* head, size_t n)
+{
+  if (n >= 4 && !memcmp(head, "BAM\1", 4)) {
+    return 2;
+  }
+  return n >= 1 && head[0] == '@' ? 1 : 0;
 }
 
 // *err: errno of a read that failed (0: none; a short count is then the end of the file)
@@ -213,7 +229,8 @@ InputFile::peek()
 }
 
 FastqStream::FastqStream(const std::string& path)
-  : in_(path)
+  : path_(path)
+  , in_(path)
 {
   buf_.resize(size_t(8) << 20);
 }
@@ -248,10 +265,88 @@ FastqStream::fill()
 bool
 FastqStream::is_fastq()
 {
-  if (pos_ == end_ && !fill()) {
-    return false;
+  if (format_ < 0) {
+    while (end_ - pos_ < 4 && fill()) {
+    }
+    format_ = input_format(reinterpret_cast<const unsigned char*>(buf_.data()) + pos_, end_ - pos_);
   }
-  return buf_[pos_] == '@';
+  return format_ != 0;
+}
+
+// The records of a BAM stream as the records of its FASTQ twin: the shared walk over what the buffer holds, every record
+// decoded into the batch.  A refused record, or a stream that ends inside the header or a record, is an input failure.
+bool
+FastqStream::next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bases)
+{
+  while (!stopped_ && out.rec.size() < max_records && out.bases < max_bases) {
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(buf_.data()) + pos_;
+    if (!bam_header_done_) {
+      uint64_t hb = 0;
+      const int rc = bam_header(p, end_ - pos_, &hb);
+      if (rc == 0 && fill()) {
+        continue;
+      }
+      if (rc != 1) {
+        note_bam_failure(path_, stream_off_, rc == 0 ? "the stream ends inside the BAM header (truncated)" : "not a BAM header");
+        stopped_ = true;
+        break;
+      }
+      pos_ += hb;
+      stream_off_ += hb;
+      bam_header_done_ = true;
+      continue;
+    }
+    uint64_t used = 0, bad = 0;
+    const char* why = nullptr;
+    bool full = false;
+    int rc = bam_walk(p, end_ - pos_, eof_, &used, &bad, &why, [&](const BamRecord& b) {
+      if (out.rec.size() >= max_records || out.bases >= max_bases) {
+        full = true;
+        return false;
+      }
+      RecordRef r{};
+      r.id_off = out.text.size();
+      r.id_len = bam_id_len(p + b.name_off, b.l_read_name);
+      out.text.insert(out.text.end(), p + b.name_off, p + b.name_off + r.id_len);
+      out.text.push_back('\0');
+      r.seq_off = out.text.size();
+      r.seq_len = r.qual_len = b.l_seq;
+      out.text.resize(r.seq_off + 2 * (size_t)b.l_seq + 2, '\0');
+      r.qual_off = r.seq_off + b.l_seq + 1;
+      bam_decode_bases(p + b.seq_off, 0, b.l_seq, out.text.data() + r.seq_off);
+      if (!bam_decode_quals(p + b.qual_off, b.l_seq, out.text.data() + r.qual_off)) {
+        out.text.resize(r.id_off);
+        bad = b.off;
+        why = "a quality without a FASTQ character (absent: 0xFF, or above 93)";
+        full = true;
+        return false;
+      }
+      out.rec.push_back(r);
+      out.bases += r.seq_len;
+      return true;
+    });
+    if (rc == 0 && why) {
+      rc = -1;
+    }
+    if (rc != 0) {
+      note_bam_failure(path_, stream_off_ + bad, why);
+      stopped_ = true;
+      break;
+    }
+    pos_ += used;
+    stream_off_ += used;
+    if (full || eof_) {
+      if (eof_ && !full) {
+        stopped_ = true;
+      }
+      break;
+    }
+    if (!fill() && pos_ == end_) { // (a tail at the end of the data: walked once more, as the final one)
+      stopped_ = true;
+      break;
+    }
+  }
+  return !out.rec.empty();
 }
 
 bool
@@ -286,6 +381,9 @@ bool
 FastqStream::next_batch(RecordBatch& out, size_t max_records, size_t max_bases)
 {
   out.clear();
+  if (is_fastq() && format_ == 2) {
+    return next_batch_bam(out, max_records, max_bases);
+  }
   while (!stopped_ && out.rec.size() < max_records && out.bases < max_bases) {
     const char* p;
     size_t n;

@@ -3,6 +3,7 @@
 // whitespace, sequence case-folded to upper case, 4-line records, records in
 // file order.  Plain or gzip-compressed text (zlib; btllib::SeqReader pipes compressed
 // input through an external decompressor).
+// An unaligned BAM stream (gr_bam.hpp) is handed out as the records of its FASTQ twin.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -20,6 +21,10 @@ namespace gr {
 void note_input_failure(const std::string& what);
 bool input_failed(std::string* what = nullptr);
 void clear_input_failure();
+// ... a BAM input (gr_bam.hpp) whose record at `off` of the decompressed stream is refused
+void note_bam_failure(const std::string& path, uint64_t off, const char* why);
+// what the first four bytes of the data say: 1 FASTQ ('@'), 2 BAM ("BAM\1"), 0 neither
+int input_format(const unsigned char* head, size_t n);
 
 class InputFile
 {
@@ -76,7 +81,8 @@ public:
   explicit FastqStream(const std::string& path);
   ~FastqStream();
   bool ok() const { return in_.ok(); }
-  // SeqReader::get_format() == FASTQ  <=>  first byte of the file is '@'
+  // SeqReader::get_format() == FASTQ  <=>  first byte of the file is '@'; unaligned BAM (the data begins with "BAM\1")
+  // is read as its FASTQ twin (gr_bam.hpp): a format this program reads
   bool is_fastq();
   // appends up to max_records / ~max_bases to `out` (cleared first); false at EOF
   bool next_batch(RecordBatch& out, size_t max_records, size_t max_bases);
@@ -84,6 +90,11 @@ public:
 private:
   bool fill();
   bool get_line(const char*& p, size_t& n); // without the trailing newline / CR / blanks
+  bool next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bases);
+  std::string path_;
+  int format_ = -1;          // input_format of the data (-1: not looked at yet)
+  bool bam_header_done_ = false;
+  uint64_t stream_off_ = 0;  // BAM: offset of buf_[pos_] in the decompressed stream
   InputFile in_;
   std::vector<char> buf_;
   size_t pos_ = 0, end_ = 0;

@@ -104,5 +104,8 @@ main(int argc, char** argv)
   ext.gzip_inflate = [](void* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n, char* text, uint64_t cap, uint32_t* bad) {
     return grp_gzip_inflate(static_cast<grp_ctx*>(c), comp, n_comp, dict, n_dict, segs, n, text, cap, bad);
   };
+  ext.bam_parse = [](void* c, const char* bytes, uint64_t n, int fin, void** out, uint64_t* nrec, uint64_t* used, uint64_t* bad) {
+    return grp_bam_parse(static_cast<grp_ctx*>(c), bytes, n, fin, reinterpret_cast<grp_fastq**>(out), nrec, used, bad);
+  };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

@@ -59,6 +59,7 @@ calc_ntcard_genome_size(PathRun& run, uint64_t& genome_size)
   std::vector<uint32_t> sel, lens, extra, run_extra, packed;
   std::vector<uint64_t> word_off;
   std::vector<std::pair<size_t, size_t>> runs;
+  std::string bam_seq; // a BAM record with other codes than A, C, G, T, as text
   // (another format fails in fill_bit_vector, as in the reference; nothing is counted here)
   const bool readable = src->ok() && src->is_fastq();
   while (readable && src->next(b)) {
@@ -76,7 +77,7 @@ calc_ntcard_genome_size(PathRun& run, uint64_t& genome_size)
         }
         continue;
       }
-      const char* seq = b.text + b.rec[i].seq_off;
+      const char* seq = b.seq_text(b.rec[i], 0, b.rec[i].seq_len, bam_seq);
       ntcard_split(seq, b.rec[i].seq_len, s0, h, runs, run_extra);
       for (size_t r = 0; r < runs.size(); ++r) {
         const size_t w0 = packed.size();
@@ -248,8 +249,8 @@ open_plain_input(const std::string& path)
     return -1;
   }
   struct stat st;
-  unsigned char magic[2] = { 0, 0 };
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || pread(fd, magic, 2, 0) != 2 || (magic[0] == 0x1f && magic[1] == 0x8b)) {
+  unsigned char magic[4] = { 0, 0, 0, 0 }; // (gzip data, or BAM that is not compressed: records are not text to read back)
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || pread(fd, magic, 4, 0) < 2 || (magic[0] == 0x1f && magic[1] == 0x8b) || !memcmp(magic, "BAM\1", 4)) {
     close(fd);
     return -1;
   }
@@ -387,6 +388,9 @@ fill_bit_vector(PathRun& run, Resident& res)
               << "num_reads_skipped_by_invalid_bases: " << by_bases << "\n"
               << "Total reads skipped: " << by_phred + by_delta + by_length + by_bases << std::endl;
   }
+  if (num_passed_reads == 0 && input_failed()) {
+    return -1; // (not an input without usable reads: one that could not be read — the caller reports that)
+  }
   if (num_passed_reads == 0) {
     std::cerr << "Error: no reads passed the Phred score and min length requirements\n"
               << "Try again with a lower Phred threshold or lower min length" << std::endl;
@@ -428,6 +432,7 @@ struct SinkState
   int fd = -1;
   std::vector<char> text;
   std::string upper;
+  std::string bam_seq, bam_qual; // a BAM record's written slice as text
   // --debug: the records that are not classified, in file order ({record, 1 = too short / 2 = filtered}),
   // and for every classified read the number of them in front of it
   const std::vector<std::pair<uint32_t, uint8_t>>* skipped = nullptr;
@@ -497,8 +502,6 @@ commit_sink(void* user, const gr_commit* c)
   const Batch& b = st.resident ? fetched : *st.batch;
   const Rec& r = st.resident ? fetched_rec : b.rec[(*st.sel)[c->read]];
   const char first = run.opt.silver_path ? '@' : '>';
-  const char* seq = b.text + r.seq_off;
-  const char* qual = b.text + r.qual_off;
   size_t off = 0, n_seq = r.seq_len, n_qual = r.qual_len;
   const char* suffix = "_untrimmed\n";
   if (c->dec.kind == DEC_INSERT_TRIMMED) {
@@ -509,15 +512,19 @@ commit_sink(void* user, const gr_commit* c)
     n_seq = std::min(end_pos, r.seq_len - off);
     n_qual = (off <= r.qual_len) ? std::min(end_pos, r.qual_len - off) : 0;
   }
+  const size_t qoff = std::min(off, r.qual_len);
+  // the written slice (a BAM batch: it alone is decoded — bases through the code table, qualities + 33)
+  const char* seq = b.seq_text(r, off, n_seq, st.bam_seq);
+  const char* qual = b.qual_text(r, qoff, n_qual, st.bam_qual);
   std::ofstream& o = run.out;
   o.put(first);
   o.write(b.text + r.id_off, (std::streamsize)r.id_len);
   o << suffix;
-  if (b.seq_is_upper) {
-    o.write(seq + off, (std::streamsize)n_seq);
+  if (b.seq_is_upper || b.bam) { // (the code table is upper case)
+    o.write(seq, (std::streamsize)n_seq);
   } else {
     // SeqReader folds the case of what the reference later writes
-    st.upper.assign(seq + off, n_seq);
+    st.upper.assign(seq, n_seq);
     for (char& ch : st.upper) {
       if (ch >= 'a' && ch <= 'z') {
         ch = (char)(ch - 32);
@@ -526,13 +533,12 @@ commit_sink(void* user, const gr_commit* c)
     o.write(st.upper.data(), (std::streamsize)n_seq);
   }
   o << std::endl;
-  const size_t qoff = std::min(off, r.qual_len);
   if (run.opt.silver_path) {
     o << "+\n";
-    o.write(qual + qoff, (std::streamsize)n_qual);
+    o.write(qual, (std::streamsize)n_qual);
     o << std::endl;
   }
-  return sum_phred(qual + qoff, n_qual);
+  return sum_phred(qual, n_qual);
 }
 
 void
@@ -564,6 +570,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   }
   if (ext && ext->struct_size >= offsetof(grp_engine_ext, gzip_inflate) + sizeof(ext->gzip_inflate)) {
     run.ext.gzip_inflate = ext->gzip_inflate;
+  }
+  if (ext && ext->struct_size >= offsetof(grp_engine_ext, bam_parse) + sizeof(ext->bam_parse)) {
+    run.ext.bam_parse = ext->bam_parse;
   }
   Opts& opt = run.opt;
   // Several GPUs of one node: one process per GPU (GRP_WORLD / GRP_RANK, or the launcher's

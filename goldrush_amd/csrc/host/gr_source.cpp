@@ -529,7 +529,24 @@ open_feed(PathRun& run, InputFile& in, size_t chunk)
   return std::unique_ptr<Feed>(new TextFeed(run, in, std::move(build)));
 }
 
-// Raw text chunks parsed, filtered and packed on the GPU (grpath_ingest.h).
+// What a regular file's data begins with, decompressed if it is gzip (input_format: 1 FASTQ, 2 BAM, 0 neither), through a
+// view of its own on the file; -1: not a regular file — a pipe can only be peeked at, and BAM is not looked for there.
+int
+probe_format(const std::string& path)
+{
+  struct stat st;
+  if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
+    return -1;
+  }
+  InputFile probe(path);
+  unsigned char head[4] = { 0, 0, 0, 0 };
+  const size_t n = probe.ok() ? probe.read(reinterpret_cast<char*>(head), sizeof(head)) : 0;
+  return input_format(head, n);
+}
+
+// Raw text chunks parsed, filtered and packed on the GPU (grpath_ingest.h).  An unaligned BAM input (gr_bam.hpp) takes the
+// same way: the feeds deliver its bytes, the header is skipped in front of the first parse — it may span chunks: the
+// carry of partial records holds it until it is complete — and grp_engine_ext::bam_parse stands where fastq_parse does.
 // A reader thread keeps the NEXT chunk of the input coming (Feed::fill) while the caller works on the current one —
 // inflate, upload, parse, pack, fill or classify — so a pass costs max(read, GPU) per chunk instead of their sum.  Four
 // slots in ONE page-locked buffer; every slot has room in front of the bytes read for the unconsumed tail of
@@ -537,9 +554,10 @@ open_feed(PathRun& run, InputFile& in, size_t chunk)
 class GpuSource : public RecordSource
 {
 public:
-  GpuSource(PathRun& run)
+  GpuSource(PathRun& run, int format)
     : run_(run)
     , in_(run.opt.input)
+    , format_(format)
   {
     chunk_ = std::max<size_t>(ingest_chunk_bytes(), 64);
     feed_ = open_feed(run_, in_, chunk_);
@@ -583,7 +601,7 @@ public:
     }
   }
   bool ok() const override { return in_.ok(); }
-  bool is_fastq() override { return in_.peek() == '@'; } // (asked before the first chunk is read)
+  bool is_fastq() override { return format_ < 0 ? in_.peek() == '@' : format_ != 0; } // (asked before the first chunk is read)
   bool next(Batch& b) override
   {
     release();
@@ -631,16 +649,47 @@ public:
         memcpy(big_.data() + carry_.size(), data, sl->n);
         text = big_.data();
       }
-      const uint64_t text_off = sl->file_off - carry_.size(); // stream offset of text[0]
+      uint64_t text_off = sl->file_off - carry_.size(); // stream offset of text[0]
       if (fill == 0) {
         done_ = true;
         break;
       }
       uint64_t n_rec = 0, used = 0;
       int stopped = 0;
+      const bool bam = format_ == 2;
+      if (bam && !bam_header_done_) {
+        // the records begin behind the header; one that is not complete yet consumes nothing
+        uint64_t hb = 0;
+        const int hrc = bam_header(reinterpret_cast<const uint8_t*>(text), fill, &hb);
+        if (hrc == 0 && !eof) {
+          release();
+          carry_.assign(text, text + fill);
+          continue;
+        }
+        if (hrc != 1) {
+          note_bam_failure(run_.opt.input, text_off, hrc == 0 ? "the stream ends inside the BAM header (truncated)" : "not a BAM header");
+          done_ = true;
+          break;
+        }
+        bam_header_done_ = true;
+        text += hb;
+        fill -= hb;
+        text_off += hb;
+        if (fill == 0 && eof) { // a header and no record
+          done_ = true;
+          break;
+        }
+      }
       const double tp0 = now_s();
-      const int prc = run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
+      uint64_t bad_off = 0;
+      const int prc = bam ? run_.ext.bam_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &bad_off)
+                          : run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
       t_tr_[1] += now_s() - tp0;
+      if (prc == GRP_ERR_INVALID && bam) { // a refused record: the input's failure, not the engine's
+        note_bam_failure(run_.opt.input, text_off + bad_off, run_.vt.last_error ? run_.vt.last_error(run_.ctx) : nullptr);
+        done_ = true;
+        break;
+      }
       if (prc != GRP_OK) {
         std::cerr << "goldrush-path: FASTQ ingest: " << (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "failed") << std::endl;
         failed_ = true;
@@ -671,6 +720,7 @@ public:
         b.rec[i] = Rec{ (size_t)m.id_off, m.id_len, (size_t)m.seq_off, m.seq_len, (size_t)m.qual_off, m.qual_len };
       }
       b.seq_is_upper = false;
+      b.bam = bam;
       prefetch_next();
       return true;
     }
@@ -825,6 +875,8 @@ private:
   int held_ = -1; // the slot the caller's current batch lives in
   bool stop_ = false;
   bool done_ = false, failed_ = false;
+  const int format_;             // probe_format of the input
+  bool bam_header_done_ = false; // BAM: the header has been skipped
   void* fq_ = nullptr;
   std::vector<grp_fastq_record> meta_;
 };
@@ -835,8 +887,9 @@ std::unique_ptr<RecordSource>
 open_source(PathRun& run)
 {
   const bool gpu = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
-  if (gpu) {
-    return std::unique_ptr<RecordSource>(new GpuSource(run));
+  const int format = gpu ? probe_format(run.opt.input) : 0;
+  if (gpu && !(format == 2 && !run.ext.bam_parse)) { // (a BAM file and an engine without bam_parse: the host reader)
+    return std::unique_ptr<RecordSource>(new GpuSource(run, format));
   }
   return std::unique_ptr<RecordSource>(new HostSource(run));
 }

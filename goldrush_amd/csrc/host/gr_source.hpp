@@ -2,8 +2,10 @@
 // records, their Phred statistics and the selected ones as packed reads on the device.  HostSource reads and packs on
 // the host (engines without the ingest entry points); GpuSource hands raw text chunks to the engine (grpath_ingest.h),
 // from plain text, gzip through zlib, BGZF members or the segments of an indexed gzip file (gr_source.cpp).
+// An unaligned BAM input (gr_bam.hpp) is read as its FASTQ twin by either source.
 #pragma once
 #include "../../../include/grpath_host.h"
+#include "gr_bam.hpp"
 #include "gr_gzidx.hpp"
 #include "gr_opts.hpp"
 
@@ -61,7 +63,29 @@ struct Batch
   std::vector<uint32_t> avg, delta; // calc_phred_average, valid where stats() ran
   std::vector<uint8_t> non_acgt;    // find_first_not_of("ACGTacgt") != npos
   bool seq_is_upper = false;        // the host reader folds case while copying
+  // `text` is a chunk of BAM records (gr_bam.hpp): seq_off = a record's 4-bit bases, qual_off = its raw Phred bytes; the
+  // name is text as it stands.  What reads a record's bases or qualities goes through seq_text / qual_text.
+  bool bam = false;
   std::string id_str(size_t i) const { return std::string(text + rec[i].id_off, rec[i].id_len); }
+  // bases [from, from + n) of a record as the characters of its FASTQ form (`tmp`: where they are decoded to, if they must be)
+  const char* seq_text(const Rec& r, size_t from, size_t n, std::string& tmp) const
+  {
+    if (!bam) {
+      return text + r.seq_off + from;
+    }
+    tmp.resize(n);
+    bam_decode_bases(reinterpret_cast<const uint8_t*>(text + r.seq_off), from, n, &tmp[0]);
+    return tmp.data();
+  }
+  const char* qual_text(const Rec& r, size_t from, size_t n, std::string& tmp) const
+  {
+    if (!bam) {
+      return text + r.qual_off + from;
+    }
+    tmp.resize(n);
+    (void)bam_decode_quals(reinterpret_cast<const uint8_t*>(text + r.qual_off) + from, n, &tmp[0]); // (the parse has refused what has no character)
+    return tmp.data();
+  }
 };
 
 class RecordSource
@@ -69,7 +93,7 @@ class RecordSource
 public:
   virtual ~RecordSource() {}
   virtual bool ok() const = 0;
-  virtual bool is_fastq() = 0;
+  virtual bool is_fastq() = 0; // a format this program reads: FASTQ, or unaligned BAM (read as its FASTQ twin)
   virtual bool next(Batch& b) = 0;
   // Phred statistics (and the ACGT check) of the records with seq_len >= min_len
   virtual void stats(Batch& b, size_t min_len, bool need_acgt) = 0;

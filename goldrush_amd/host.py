@@ -107,8 +107,16 @@ BGZF_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _v
 GZIP_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32))
 
 
+BAM_PARSE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+
+
 class grp_engine_ext(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN)]
+    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN)]
+
+
+class gr_bam_record(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("name_off", C.c_uint64), ("seq_off", C.c_uint64), ("qual_off", C.c_uint64), ("end", C.c_uint64),
+                ("l_read_name", C.c_uint32), ("l_seq", C.c_uint32), ("flag", C.c_uint32), ("id_len", C.c_uint32)]
 
 
 COMMIT_FN = C.CFUNCTYPE(C.c_double, _vp, C.POINTER(gr_commit))
@@ -152,6 +160,9 @@ SIGNATURES = {
     "gr_path_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(grp_engine_vt)]),
     "gr_path_main_ext": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(grp_engine_vt), C.POINTER(grp_engine_ext)]),
     "gr_bgzf_scan": (C.c_size_t, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "gr_bam_header": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gr_bam_walk": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]),
+    "gr_bam_decode": (C.c_int, [_vp, C.POINTER(gr_bam_record), _vp, _vp]),
     "gr_input_read": (C.c_uint64, [C.c_char_p, C.c_uint64, _vp, C.c_uint64]),
     "gr_gzidx_build": (_vp, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
     "gr_gzidx_info": (None, [_vp, _vp]),
@@ -276,6 +287,30 @@ def bgzf_scan(buf: bytes, cap: int = 1 << 16):
     return [(int(b["comp_off"]), int(b["comp_len"]), int(b["text_len"]), int(b["crc32"])) for b in blocks[:n]], consumed.value, why.value
 
 
+def bam_header(buf: bytes):
+    """gr_bam_header -> (1 complete / 0 more bytes needed / -1 not BAM, where the first record begins)"""
+    raw = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+    hb = C.c_uint64()
+    return load().gr_bam_header(_p(raw), len(buf), C.byref(hb)), hb.value
+
+
+def bam_walk(buf: bytes, final_chunk: bool = True, cap: int = 1 << 16):
+    """gr_bam_walk over bytes that begin at a record -> (rc, [gr_bam_record], records found, consumed, bad_offset, why)"""
+    raw = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+    recs = (gr_bam_record * max(cap, 1))()
+    n, used, bad, why = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_char_p()
+    rc = load().gr_bam_walk(_p(raw), len(buf), 1 if final_chunk else 0, recs, cap, C.byref(n), C.byref(used), C.byref(bad), C.byref(why))
+    return rc, list(recs[:min(n.value, cap)]), n.value, used.value, bad.value, (why.value or b"").decode()
+
+
+def bam_decode(buf: bytes, rec: gr_bam_record):
+    """gr_bam_decode -> (rc, bases, quality characters) of one record of bam_walk"""
+    raw = np.frombuffer(buf, dtype=np.uint8)
+    seq, qual = C.create_string_buffer(rec.l_seq + 1), C.create_string_buffer(rec.l_seq + 1)
+    rc = load().gr_bam_decode(_p(raw), C.byref(rec), seq, qual)
+    return rc, seq.raw[:rec.l_seq], qual.raw[:rec.l_seq]
+
+
 def gzip_index(path, span: int = 256 << 10, max_bytes: int = 16 << 30, stop_after: int = 0, text_cap: int = 0) -> dict:
     """gr_gzidx_build: the host program's first pass over a plain gzip file.  Returns complete / dropped / failed, the
     bytes of text read (and the text itself up to text_cap), the bytes the index holds, whether the file still matches,
@@ -311,6 +346,7 @@ def hip_engine_ext() -> grp_engine_ext:
     ext.struct_size = C.sizeof(grp_engine_ext)
     ext.bgzf_inflate = C.cast(lib.grp_bgzf_inflate, BGZF_INFLATE_FN)
     ext.gzip_inflate = C.cast(lib.grp_gzip_inflate, GZIP_INFLATE_FN)
+    ext.bam_parse = C.cast(lib.grp_bam_parse, BAM_PARSE_FN)
     return ext
 
 

@@ -167,6 +167,7 @@ gzip_segment_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_of
 SIGNATURES.update({
     "grp_fastq_prefetch": (C.c_int, [_vp, _vp, C.c_uint64]),
     "grp_fastq_parse": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "grp_bam_parse": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "grp_fastq_records": (C.c_int, [_vp, _vp]),
     "grp_fastq_pack": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "grp_fastq_free": (None, [_vp]),
@@ -382,6 +383,27 @@ class Engine:
         if n_rec.value:
             self._check(self.lib.grp_fastq_records(out, _ptr(rec)))
         return out, rec, used.value, bool(stopped.value)
+
+    def bam_parse(self, data, final_chunk: bool = True, n_bytes: "int | None" = None):
+        """grp_bam_parse: the records of an unaligned BAM stream, `data` beginning at a record (the header skipped).  `data` is
+        bytes, or a caller-owned uint8 array of which the first n_bytes are parsed in place (what a pinned or prefetched
+        buffer needs).  Returns (handle, records[fastq_record_dtype], bytes_consumed); the handle is served by fastq_pack /
+        fastq_free.  A refused record raises GrpError with .bad_offset = its offset in `data`."""
+        if isinstance(data, np.ndarray):
+            buf, n = data, data.size if n_bytes is None else n_bytes
+        else:
+            buf, n = (np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)), len(data)
+        out = C.c_void_p()
+        n_rec, used, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.grp_bam_parse(self._h, _ptr(buf), n, 1 if final_chunk else 0, C.byref(out), C.byref(n_rec), C.byref(used), C.byref(bad))
+        if rc != GRP_OK:
+            e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
+            e.bad_offset = bad.value
+            raise e
+        rec = np.zeros(n_rec.value, dtype=fastq_record_dtype)
+        if n_rec.value:
+            self._check(self.lib.grp_fastq_records(out, _ptr(rec)))
+        return out, rec, used.value
 
     # -- BGZF members inflated on the device (include/grpath_ingest.h)
     def bgzf_inflate(self, comp, blocks, text_cap: "int | None" = None) -> bytes:

@@ -623,6 +623,9 @@ int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
 typedef struct grp_gzip_segment grp_gzip_segment;
 int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
 int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
+/* ... and the records of an unaligned BAM stream, parsed where FASTQ text is (grpath_ingest.h) */
+typedef struct grp_fastq grp_fastq;
+int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
 
 /* 1: the library was built with GRP_DEV_HOOKS (make DEV=1): the measurement-only prototypes of include/grpath_dev.h are
  * compiled in; 0: the product build (they are not exported) */

@@ -292,6 +292,25 @@ int gr_gzidx_segment(const gr_gzidx* h, uint64_t i, grp_gzip_segment* seg, unsig
 int gr_gzidx_matches(const gr_gzidx* h, const char* path);
 void gr_gzidx_free(gr_gzidx* h);
 
+/* ---- unaligned BAM input (csrc/host/gr_bam.hpp) -------------------------------------------------------------------------
+ * A BAM file is read as its FASTQ twin: per record "@<name up to its NUL>\n<bases by =ACMGRSVTWYHKDBN>\n+\n<qual + 33>\n".
+ * gr_bam_header: the header at the front of buf[0, n): 1 complete (*header_bytes = where the first record begins), 0 more
+ * bytes needed, -1 not BAM.  gr_bam_walk: the record chain of buf[0, n), which begins at a record — the walk the engine's
+ * grp_bam_parse performs: up to `cap` complete records into recs (all offsets from buf), *n_records of them found,
+ * *consumed = the bytes they span; 0, or -1 with *bad_offset = the refused record and *why = the reason: a block_size
+ * smaller than the record's fields, l_read_name 0, a name without NUL, flag 0x10 / 0x100 / 0x800, and with final_chunk a
+ * stream that ends inside a record.  gr_bam_decode: l_seq bases and l_seq quality characters of one record; -1: a
+ * quality without a FASTQ character (0xFF, above 93). */
+typedef struct
+{
+  uint64_t off, name_off, seq_off, qual_off, end; /* block_size field, name, 4-bit bases, qualities, the next record */
+  uint32_t l_read_name, l_seq, flag;
+  uint32_t id_len; /* the name up to its NUL, cut at the first whitespace */
+} gr_bam_record;
+int gr_bam_header(const unsigned char* buf, uint64_t n, uint64_t* header_bytes);
+int gr_bam_walk(const unsigned char* buf, uint64_t n, int final_chunk, gr_bam_record* recs, uint64_t cap, uint64_t* n_records, uint64_t* consumed, uint64_t* bad_offset, const char** why);
+int gr_bam_decode(const unsigned char* buf, const gr_bam_record* rec, char* seq_out, char* qual_out);
+
 /* ---- optional engine entry points that came after grp_engine_vt was frozen at 48 members: a second table, every member
  * optional (NULL, or a struct_size that ends in front of it: the host takes the path it took without it) */
 typedef struct
@@ -302,6 +321,10 @@ typedef struct
   /* grp_gzip_inflate: with it, the passes over a plain gzip input behind the first inflate the segments of the first
    * pass's index on the device (GRP_GZIP_INDEX=off: every pass through zlib as before) */
   int (*gzip_inflate)(void* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
+  /* grp_bam_parse: with it, the records of an unaligned BAM input are parsed and packed on the device, where text goes
+   * through fastq_parse (the handle is served by the table's fastq_records / fastq_pack / fastq_free); without it a BAM
+   * file takes the host reader */
+  int (*bam_parse)(void* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, void** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
 } grp_engine_ext;
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */

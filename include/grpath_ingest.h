@@ -144,6 +144,30 @@ int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const u
 /* segments, compressed bytes, text bytes, kernel microseconds (HIP events around the two kernels) since grp_create */
 int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
 
+/*
+ * ---- unaligned BAM: records instead of four text lines ---------------------------------------------------------------
+ * PacBio and Nanopore deliver long reads as unaligned BAM: a BGZF container (grp_bgzf_inflate turns its members into
+ * bytes) around a header and records of 4-bit bases and raw Phred bytes.  The program reads a BAM file as its FASTQ twin
+ * — per record "@<read_name up to its NUL>\n<bases by =ACMGRSVTWYHKDBN>\n+\n<qual + 33>\n" — and grp_bam_parse is
+ * grp_fastq_parse for such bytes, with its contract:
+ *  - `bytes` (host memory; pinned is faster) begins at a record: the caller has skipped the BAM header.  Only complete
+ *    records are consumed; the caller re-submits the tail.  final_chunk with bytes left over is a truncation error.
+ *  - The record chain is walked on the host side of the call (a pointer chase of 4-byte reads over bytes that are in host
+ *    memory; csrc/host/gr_bam.hpp, the one walk the host library uses too); the record table, the ACGT test over the
+ *    4-bit codes, the quality range test, the Phred sums and the pack run on the device.
+ *  - Refused, with GRP_ERR_INVALID, *bad_offset = the record's offset from `bytes` and the reason in grp_last_error:
+ *    a block_size smaller than 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq, l_read_name 0, a name that does
+ *    not end in NUL, flag 0x10 / 0x100 / 0x800 (convert with samtools fastq), qualities that are absent (0xFF) or above
+ *    93 where l_seq > 0, and a stream that ends inside a record.  Nothing is returned then.
+ *  - Not refused: l_seq 0, any n_cigar_op and tags (skipped by block_size), paired-end flags, a non-zero padding code
+ *    behind an odd l_seq (it does not set GRP_FQ_NON_ACGT), a code other than A, C, G, T (it does).
+ *  - The handle is served by grp_fastq_prefetch / _pin / _records / _pack / _free unchanged.  Offsets of the table count
+ *    from `bytes`: id_off / id_len = the name without its NUL, cut at a whitespace; seq_off = the first byte of the
+ *    4-bit bases (high half first), seq_len = l_seq; qual_off = the first raw quality byte, qual_len = l_seq.
+ *    phred_sum / phred_first are the same left-to-right double sums, bit-identical to those of the twin's quality line.
+ */
+int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
+
 #ifdef __cplusplus
 }
 #endif
