@@ -96,6 +96,35 @@ gr_process_options_dump(int argc, char** argv, char* out, size_t cap)
   return rc;
 }
 
+int
+gr_inputs_dump(int argc, char** argv, char* out, size_t cap)
+{
+  gr::Opts o;
+  int rc = gr::process_options(o, argc, argv);
+  std::ostringstream ss;
+  ss << "input=" << o.input << "\n";
+  for (const std::string& i : o.inputs) {
+    ss << "inputs=" << i << "\n";
+  }
+  std::vector<std::string> files;
+  std::string err;
+  if (gr::expand_inputs(o.inputs, files, err)) {
+    for (const std::string& f : files) {
+      ss << "file=" << f << "\n";
+    }
+  } else {
+    ss << "error=" << err << "\n";
+    rc = rc < 0 ? 1 : rc;
+  }
+  const std::string t = ss.str();
+  if (out && cap) {
+    const size_t n = std::min(cap - 1, t.size());
+    std::memcpy(out, t.data(), n);
+    out[n] = '\0';
+  }
+  return rc;
+}
+
 unsigned
 gr_ntcard_sbits(uint64_t input_bytes)
 {

@@ -1,6 +1,7 @@
 #include "gr_opts.hpp"
 
 #include <cstdlib>
+#include <fstream>
 #include <getopt.h>
 #include <iostream>
 
@@ -62,7 +63,10 @@ process_options(Opts& o, int argc, char** argv)
       case 'f': o.filter_file = optarg; break;
       case 'H': o.hash_universe = strtoull(optarg, nullptr, 10); break;
       case 'h': o.hash_num = strtoul(optarg, nullptr, 10); break;
-      case 'i': o.input = optarg; break;
+      case 'i':
+        o.input = optarg;
+        o.inputs.push_back(optarg);
+        break;
       case 'j': o.jobs = strtoul(optarg, nullptr, 10); break;
       case 'k': o.kmer_size = strtoul(optarg, nullptr, 10); break;
       case 'm': o.min_length = strtoul(optarg, nullptr, 10); break;
@@ -113,6 +117,53 @@ process_options(Opts& o, int argc, char** argv)
     }
   }
   return -1;
+}
+
+bool
+expand_inputs(const std::vector<std::string>& inputs, std::vector<std::string>& files, std::string& err)
+{
+  const auto is_list = [](const std::string& p) { return p.size() >= 5 && p.compare(p.size() - 5, 5, ".fofn") == 0; };
+  files.clear();
+  for (const std::string& in : inputs) {
+    if (!is_list(in)) {
+      files.push_back(in);
+      continue;
+    }
+    std::ifstream f(in);
+    if (!f) {
+      err = in + ": the list cannot be read";
+      return false;
+    }
+    const size_t slash = in.rfind('/');
+    const std::string dir = slash == std::string::npos ? std::string() : in.substr(0, slash + 1);
+    size_t listed = 0;
+    std::string line;
+    while (std::getline(f, line)) {
+      while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) {
+        line.pop_back();
+      }
+      const size_t b = line.find_first_not_of(" \t");
+      if (b == std::string::npos || line[b] == '#') {
+        continue;
+      }
+      line.erase(0, b);
+      if (is_list(line)) {
+        err = in + ": a list inside a list (" + line + ")";
+        return false;
+      }
+      files.push_back(line[0] == '/' ? line : dir + line);
+      ++listed;
+    }
+    if (f.bad()) {
+      err = in + ": the list cannot be read";
+      return false;
+    }
+    if (listed == 0) {
+      err = in + ": the list names no file";
+      return false;
+    }
+  }
+  return true;
 }
 
 } // namespace gr

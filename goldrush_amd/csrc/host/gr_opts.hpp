@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace gr {
 
@@ -27,7 +28,8 @@ struct Opts
   uint32_t phred_min = 0;     // -P
   uint32_t phred_delta = 5;   // -d
   std::string prefix_file = "goldrush_out"; // -p
-  std::string input;          // -i
+  std::string input;          // -i   (the last one, as the reference holds it)
+  std::vector<std::string> inputs; // every -i, in command-line order
   std::string seed_preset;    // -s
   std::string filter_file;    // -f
   int help = 0, ntcard = 0, silver_path = 0, verbose = 0, debug = 0;
@@ -36,5 +38,9 @@ struct Opts
 void print_usage(const std::string& progname);
 // returns -1 to continue, otherwise the exit code the reference exits with
 int process_options(Opts& o, int argc, char** argv);
+// The files a run reads, in order: every -i, with a name that ends in ".fofn" replaced by the paths it lists — one per
+// line, blank lines and lines beginning with '#' skipped, relative paths resolved against the list's directory.  false:
+// a list that cannot be read, lists nothing or names another list (`err` names it).
+bool expand_inputs(const std::vector<std::string>& inputs, std::vector<std::string>& files, std::string& err);
 
 } // namespace gr

@@ -43,11 +43,11 @@ calc_ntcard_genome_size(PathRun& run, uint64_t& genome_size)
   const unsigned s0 = (unsigned)run.seeds[0].size(), h = (unsigned)opt.hash_num;
   std::cerr << "Calculating expected entries" << std::endl;
   const double s_time = now_s();
-  uint64_t input_bytes = 0;
-  {
-    std::ifstream in(opt.input, std::ifstream::ate | std::ifstream::binary); // getInf (:44-49)
+  uint64_t input_bytes = 0; // (several files: the tables are sized from the sum of their sizes)
+  for (const std::string& path : run.files) {
+    std::ifstream in(path, std::ifstream::ate | std::ifstream::binary); // getInf (:44-49)
     if (in) {
-      input_bytes = (uint64_t)in.tellg();
+      input_bytes += (uint64_t)in.tellg();
     }
   }
   const unsigned sbits = ntcard_sbits(input_bytes);
@@ -195,7 +195,8 @@ calc_min_phred_threshold(PathRun& run)
 // off, GRP_RESIDENT_MAX_GB caps the packed bytes kept (default 100).
 struct RecLoc
 {
-  uint64_t off;     // offset of the record's id in the input file
+  uint32_t file;    // which of the run's files
+  uint64_t off;     // offset of the record's id in that file
   uint32_t id_len;
   uint32_t seq_rel; // seq / qual relative to `off`
   uint32_t seq_len;
@@ -225,9 +226,50 @@ fnv1a(const char* p, size_t n)
 struct Resident
 {
   bool on = false;
-  int fd = -1;
   uint64_t packed_bytes = 0, max_bytes = 0;
   std::vector<ResidentBatch> batches;
+  // The files the records are read back from: at most kMaxOpen descriptors at once, the others opened when a record of
+  // theirs is asked for (the one used longest ago makes room).
+  static constexpr size_t kMaxOpen = 64;
+  struct Open
+  {
+    uint32_t file;
+    int fd;
+    uint64_t used;
+  };
+  std::vector<Open> open_fds;
+  uint64_t clock = 0;
+  int fd_of(const PathRun& run, uint32_t file) // -1: the file cannot be opened (any more)
+  {
+    size_t oldest = 0;
+    for (size_t i = 0; i < open_fds.size(); ++i) {
+      if (open_fds[i].file == file) {
+        open_fds[i].used = ++clock;
+        return open_fds[i].fd;
+      }
+      if (open_fds[i].used < open_fds[oldest].used) {
+        oldest = i;
+      }
+    }
+    const int fd = open(run.files[file].c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd < 0) {
+      return -1;
+    }
+    if (open_fds.size() < kMaxOpen) {
+      open_fds.push_back(Open{ file, fd, ++clock });
+    } else {
+      close(open_fds[oldest].fd);
+      open_fds[oldest] = Open{ file, fd, ++clock };
+    }
+    return fd;
+  }
+  void close_files()
+  {
+    for (const Open& o : open_fds) {
+      close(o.fd);
+    }
+    open_fds.clear();
+  }
   void drop(PathRun& run)
   {
     for (ResidentBatch& rb : batches) {
@@ -240,21 +282,23 @@ struct Resident
   }
 };
 
-// plain regular file (no gzip magic)?  Returns a descriptor for pread, -1 otherwise.
-int
-open_plain_input(const std::string& path)
+// plain regular file (no gzip magic) whose records can be read back with pread?  `may_be_empty`: one of several files
+// may hold no byte (no record is ever read back from it).
+bool
+is_plain_input(const std::string& path, bool may_be_empty)
 {
-  const int fd = open(path.c_str(), O_RDONLY);
+  const int fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
   if (fd < 0) {
-    return -1;
+    return false;
   }
   struct stat st;
   unsigned char magic[4] = { 0, 0, 0, 0 }; // (gzip data, or BAM that is not compressed: records are not text to read back)
-  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || pread(fd, magic, 4, 0) < 2 || (magic[0] == 0x1f && magic[1] == 0x8b) || !memcmp(magic, "BAM\1", 4)) {
-    close(fd);
-    return -1;
+  bool plain = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+  if (plain && !(may_be_empty && st.st_size == 0)) {
+    plain = !(pread(fd, magic, 4, 0) < 2 || (magic[0] == 0x1f && magic[1] == 0x8b) || !memcmp(magic, "BAM\1", 4));
   }
-  return fd;
+  close(fd);
+  return plain;
 }
 
 int
@@ -320,7 +364,7 @@ fill_bit_vector(PathRun& run, Resident& res)
         // not in filter_out_reads (read_hashing.cpp:35-42) — without a -f list exactly the reads selected here
         const Rec& r = b.rec[i];
         keep.skipped_before.push_back(skipped - 1);
-        keep.loc.push_back(RecLoc{ b.base_off + r.id_off, (uint32_t)r.id_len, (uint32_t)(r.seq_off - r.id_off), (uint32_t)r.seq_len, (uint64_t)(r.qual_off - r.id_off), (uint32_t)r.qual_len });
+        keep.loc.push_back(RecLoc{ (uint32_t)b.file, b.base_off + r.id_off, (uint32_t)r.id_len, (uint32_t)(r.seq_off - r.id_off), (uint32_t)r.seq_len, (uint64_t)(r.qual_off - r.id_off), (uint32_t)r.qual_len });
         keep.name_hash.push_back(fnv1a(b.text + r.id_off, r.id_len));
       }
       skipped = 0;
@@ -429,7 +473,7 @@ struct SinkState
   const std::vector<uint32_t>* sel = nullptr;
   // reads kept on the device: the record's text comes from the input file
   const ResidentBatch* resident = nullptr;
-  int fd = -1;
+  Resident* res = nullptr;
   std::vector<char> text;
   std::string upper;
   std::string bam_seq, bam_qual; // a BAM record's written slice as text
@@ -484,13 +528,14 @@ commit_sink(void* user, const gr_commit* c)
     const size_t n = (size_t)l.qual_rel + l.qual_len;
     st.text.resize(n);
     size_t got = 0;
+    const int fd = st.res->fd_of(run, l.file);
     while (got < n) {
-      const ssize_t k = pread(st.fd, st.text.data() + got, n - got, (off_t)(l.off + got));
+      const ssize_t k = fd < 0 ? -1 : pread(fd, st.text.data() + got, n - got, (off_t)(l.off + got));
       if (k <= 0) {
         // not exit(1) from inside the commit callback (a streaming window may be parked on this thread's word,
         // ADVICE r03): the failure is noted, this and the later records are not written, and the program ends with
         // an error behind the pass
-        note_input_failure("cannot read the record back from " + run.opt.input);
+        note_input_failure("cannot read the record at byte " + std::to_string(l.off) + " back from " + run.files[l.file]);
         return 0.0;
       }
       got += (size_t)k;
@@ -625,6 +670,18 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   if (ec >= 0) {
     return ec;
   }
+  {
+    // every -i is an input, a ".fofn" list stands for the files it names (gr_opts.hpp); no -i at all: the reference's empty name
+    std::string bad_list;
+    if (!expand_inputs(opt.inputs, run.files, bad_list)) {
+      std::cerr << "goldrush-path: " << bad_list << std::endl;
+      return 1;
+    }
+    if (run.files.empty()) {
+      run.files.push_back(opt.input);
+    }
+    run.gzidx.resize(run.files.size());
+  }
   struct ShmGuard
   {
     void* h = nullptr;
@@ -687,6 +744,16 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
       }
     }
   } guard{ run };
+  if (run.files.size() > 1) {
+    // several inputs: each is looked at before the first pass — a run does not get an hour into the fill before it finds
+    // that its last file is missing
+    const std::string bad = check_inputs(run);
+    if (!bad.empty()) {
+      std::cerr << "goldrush-path: " << bad << std::endl;
+      std::cerr << "Gold Path requires fastq format" << std::endl;
+      return 1;
+    }
+  }
   if (use_ntcard) {
     uint64_t genome_size = 0;
     ec = calc_ntcard_genome_size(run, genome_size);
@@ -756,7 +823,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   std::cerr << "m_filterSize: " << filter_size << std::endl;
   std::cerr << "finished allocating bit vector" << std::endl;
   std::cerr << "in " << std::setprecision(4) << std::fixed << now_s() - s_time << "\n";
-  std::cerr << "opening: " << opt.input << std::endl;
+  for (const std::string& path : run.files) {
+    std::cerr << "opening: " << path << std::endl;
+  }
 
   Resident res;
   struct ResGuard
@@ -766,17 +835,18 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     ~ResGuard()
     {
       res.drop(run);
-      if (res.fd >= 0) {
-        close(res.fd);
-      }
+      res.close_files();
     }
   } res_guard{ run, res };
   {
     const char* e = getenv("GRP_RESIDENT");
     const bool gpu_ingest = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
     if (!(e && !strcmp(e, "off")) && gpu_ingest && !opt.debug) {
-      res.fd = open_plain_input(opt.input);
-      res.on = res.fd >= 0;
+      // (every input a plain seekable file — else the whole run takes the two-pass form)
+      res.on = true;
+      for (const std::string& path : run.files) {
+        res.on = res.on && is_plain_input(path, run.files.size() > 1);
+      }
       const char* cap = getenv("GRP_RESIDENT_MAX_GB");
       res.max_bytes = (uint64_t)((cap ? atof(cap) : 100.0) * (double)(1ull << 30));
     }
@@ -837,7 +907,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
 
   if (res.on) {
     // the classification pass over the batches the fill pass left in HBM: no second parse
-    sink.fd = res.fd;
+    sink.res = &res;
     std::unordered_set<uint64_t> filtered_hash;
     for (const std::string& name : run.filter_out_reads) {
       filtered_hash.insert(fnv1a(name.data(), name.size()));
@@ -856,7 +926,8 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
         for (uint32_t i = 0; i < n; ++i) {
           if (filtered_hash.count(rb.name_hash[i])) {
             name.resize(rb.loc[i].id_len);
-            if (pread(res.fd, &name[0], name.size(), (off_t)rb.loc[i].off) == (ssize_t)name.size() && run.filter_out_reads.count(name)) {
+            const int fd = res.fd_of(run, rb.loc[i].file);
+            if (fd >= 0 && pread(fd, &name[0], name.size(), (off_t)rb.loc[i].off) == (ssize_t)name.size() && run.filter_out_reads.count(name)) {
               drop[i] = 1;
               any_drop = true;
             }

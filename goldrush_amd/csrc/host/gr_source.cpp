@@ -6,6 +6,7 @@
 #include "gr_params.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
@@ -61,15 +62,23 @@ class HostSource : public RecordSource
 public:
   HostSource(PathRun& run)
     : run_(run)
-    , fq_(run.opt.input)
+    , fq_(new FastqStream(run.files[0]))
   {}
-  bool ok() const override { return fq_.ok(); }
-  bool is_fastq() override { return fq_.is_fastq(); }
+  // (several files: check_inputs has looked at every one of them before the first pass)
+  bool ok() const override { return run_.files.size() > 1 || fq_->ok(); }
+  bool is_fastq() override { return run_.files.size() > 1 || fq_->is_fastq(); }
   bool next(Batch& b) override
   {
-    if (!fq_.next_batch(rb_, BATCH_RECORDS, BATCH_BASES)) {
-      return false;
+    // a file's reader hands out that file's records to its end — as it would on its own — and the next file's takes over
+    while (!fq_->next_batch(rb_, BATCH_RECORDS, BATCH_BASES)) {
+      if (file_ + 1 >= run_.files.size() || input_failed()) {
+        return false;
+      }
+      fq_.reset(new FastqStream(run_.files[++file_]));
     }
+    b.file = file_;
+    b.base_off = 0;
+    b.bam = false;
     b.text = rb_.text.data();
     b.rec.resize(rb_.rec.size());
     for (size_t i = 0; i < rb_.rec.size(); ++i) {
@@ -109,6 +118,7 @@ public:
   int upload(Batch& b, const std::vector<uint32_t>& sel, std::vector<uint32_t>& lens, void** reads) override
   {
     const size_t n = sel.size();
+    lens.reserve(1); // (a file whose every record is filtered out is a batch without a read: still an array to point at)
     lens.resize(n);
     word_off_.resize(n + 1);
     uint64_t w = 0;
@@ -130,7 +140,8 @@ public:
 
 private:
   PathRun& run_;
-  FastqStream fq_;
+  size_t file_ = 0; // the file being read
+  std::unique_ptr<FastqStream> fq_;
   RecordBatch rb_;
   std::vector<uint32_t> packed_;
   std::vector<uint64_t> word_off_;
@@ -165,13 +176,17 @@ public:
     uint64_t bgzf_blocks = 0, gzip_segs = 0;
   };
   virtual ~Feed() {}
-  // once, before the first fill: the slots will have these sizes (a feed sizes its per-slot tables here)
-  virtual Sizes layout(size_t chunk, int /*n_slots*/) { return Sizes{ chunk, 0, 0 }; }
+  // once, before the first fill: the slots have these sizes — what the feeds of all the pass's files asked for
+  // (FilePlan::want), so at least what this one did (a feed sizes its per-slot tables here)
+  virtual void layout(const Sizes& /*slot*/, int /*n_slots*/) {}
   // reader thread: the next up to `chunk` bytes of text for the slot; eof: the data ends with them
   virtual size_t fill(int slot, const SlotBuf& b, size_t chunk, bool& eof) = 0;
   // consumer thread: the slot's text is there; false: the engine refused it (the failure is noted)
   virtual bool inflate(int /*slot*/, const SlotBuf&, size_t /*chunk*/) { return true; }
   virtual Counts counts() const { return Counts{}; }
+  // the first byte of the data without consuming it (-1: none; a feed of compressed bytes does not look: -2)
+  virtual int peek() { return -2; }
+  virtual bool ok() const { return true; } // the file could be opened
 };
 
 // `want` bytes at `off`; fewer: the file ends there (*err 0) or the read failed (*err: errno)
@@ -200,30 +215,34 @@ pread_full(int fd, unsigned char* dst, size_t want, uint64_t off, int* err)
 class TextFeed : public Feed
 {
 public:
-  TextFeed(PathRun& run, InputFile& in, std::unique_ptr<GzIndexReader> build)
+  TextFeed(PathRun& run, size_t file, std::unique_ptr<InputFile> in, std::unique_ptr<GzIndexReader> build)
     : run_(run)
-    , in_(in)
+    , file_(file)
+    , in_(std::move(in))
     , build_(std::move(build))
   {}
+  int peek() override { return in_->peek(); }
+  bool ok() const override { return in_->ok(); }
   size_t fill(int, const SlotBuf& b, size_t chunk, bool& eof) override
   {
     size_t got = 0;
     while (!eof && got < chunk) {
-      const size_t k = build_ ? build_->read(b.text + got, chunk - got) : in_.read(b.text + got, chunk - got);
+      const size_t k = build_ ? build_->read(b.text + got, chunk - got) : in_->read(b.text + got, chunk - got);
       if (k == 0) {
         eof = true;
       }
       got += k;
     }
     if (eof && build_ && build_->complete()) {
-      run_.gzidx = build_->take(); // (read by the next pass's source, which begins behind this thread's end)
+      run_.gzidx[file_] = build_->take(); // (read by the next pass's source, which begins behind this thread's end)
     }
     return got;
   }
 
 private:
   PathRun& run_;
-  InputFile& in_;
+  const size_t file_; // which of the run's files (its index goes to PathRun::gzidx[file_])
+  std::unique_ptr<InputFile> in_;
   std::unique_ptr<GzIndexReader> build_;
 };
 
@@ -234,21 +253,26 @@ private:
 class BgzfFeed : public Feed
 {
 public:
-  BgzfFeed(PathRun& run, int fd)
+  BgzfFeed(PathRun& run, size_t file, int fd)
     : run_(run)
+    , file_(file)
+    , path_(run.files[file])
     , fd_(fd)
   {}
   ~BgzfFeed() override { ::close(fd_); }
-  Sizes layout(size_t chunk, int n_slots) override
+  static Sizes want(size_t chunk)
   {
     chunk = std::max<size_t>(chunk, BGZF_MAX_TEXT); // a tiny GRP_INGEST_CHUNK still holds one member
-    comp_cap_ = std::max<size_t>(chunk / 2, BGZF_MAX_MEMBER);
-    tab_cap_ = std::max<size_t>(chunk / 4096, 64);
+    return Sizes{ chunk, std::max<size_t>(chunk / 2, BGZF_MAX_MEMBER), 0 };
+  }
+  void layout(const Sizes& slot, int n_slots) override
+  {
+    comp_cap_ = slot.comp;
+    tab_cap_ = std::max<size_t>(slot.chunk / 4096, 64);
     slot_.resize((size_t)n_slots);
     for (Table& t : slot_) {
       t.blocks.resize(tab_cap_);
     }
-    return Sizes{ chunk, comp_cap_, 0 };
   }
   size_t fill(int i, const SlotBuf& b, size_t chunk, bool& eof) override
   {
@@ -275,7 +299,7 @@ public:
       if (bad != UINT32_MAX && bad > 0 && bad < sl.n_blocks) {
         at += sl.blocks[bad - 1].comp_off + sl.blocks[bad - 1].comp_len + 8;
       }
-      note_input_failure("reading " + run_.opt.input + " failed: BGZF member " + (bad != UINT32_MAX ? "at byte " + std::to_string(at) : "in the chunk at byte " + std::to_string(at)) + ": " +
+      note_input_failure("reading " + path_ + " failed: BGZF member " + (bad != UINT32_MAX ? "at byte " + std::to_string(at) : "in the chunk at byte " + std::to_string(at)) + ": " +
                          (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
       return false;
     }
@@ -309,7 +333,7 @@ private:
           int err = 0;
           const size_t k = pread_full(fd_, comp + have, want, off_ + have, &err);
           if (err) {
-            note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(off_ + have + k) + ": " + strerror(err));
+            note_input_failure("reading " + path_ + " failed at byte " + std::to_string(off_ + have + k) + ": " + strerror(err));
           }
           file_end = k < want;
           have += k;
@@ -338,7 +362,7 @@ private:
           break;
         } else if (file_end) { // (why 0: bytes of a member are missing; 1: the members end with the file)
           if (have > pos) {
-            note_input_failure("reading " + run_.opt.input + " failed: the file ends inside the BGZF member at byte " + std::to_string(off_ + pos) + " (truncated)");
+            note_input_failure("reading " + path_ + " failed: the file ends inside the BGZF member at byte " + std::to_string(off_ + pos) + " (truncated)");
           }
           eof = true;
           break;
@@ -351,16 +375,17 @@ private:
       sl.comp_n = pos;
       if (other) {
         // from this member on zlib reads, from a descriptor of its own that stands there
-        const int fd = ::open(run_.opt.input.c_str(), O_RDONLY | O_CLOEXEC);
+        const int fd = ::open(path_.c_str(), O_RDONLY | O_CLOEXEC);
+        std::unique_ptr<InputFile> tail_in;
         if (fd >= 0 && lseek(fd, (off_t)off_, SEEK_SET) == (off_t)off_) {
-          tail_in_.reset(new InputFile(run_.opt.input, fd));
+          tail_in.reset(new InputFile(path_, fd));
         } else if (fd >= 0) {
           ::close(fd);
         }
-        if (tail_in_ && tail_in_->ok()) {
-          tail_.reset(new TextFeed(run_, *tail_in_, nullptr));
+        if (tail_in && tail_in->ok()) {
+          tail_.reset(new TextFeed(run_, file_, std::move(tail_in), nullptr));
         } else {
-          note_input_failure("reading " + run_.opt.input + " failed: cannot read on behind the BGZF members at byte " + std::to_string(off_));
+          note_input_failure("reading " + path_ + " failed: cannot read on behind the BGZF members at byte " + std::to_string(off_));
           eof = true;
         }
       }
@@ -370,12 +395,13 @@ private:
     }
   }
   PathRun& run_;
+  const size_t file_;
+  const std::string path_;
   int fd_;           // the reader's descriptor ...
   uint64_t off_ = 0; // ... and how far it has come
   size_t comp_cap_ = 0, tab_cap_ = 0;
   std::vector<Table> slot_;
-  std::unique_ptr<InputFile> tail_in_; // what follows the BGZF members ...
-  std::unique_ptr<TextFeed> tail_;     // ... read as text
+  std::unique_ptr<TextFeed> tail_; // what follows the BGZF members, read as text
   uint64_t n_blocks_ = 0;
 };
 
@@ -386,22 +412,26 @@ private:
 class GzipSegFeed : public Feed
 {
 public:
-  GzipSegFeed(PathRun& run, int fd)
+  GzipSegFeed(PathRun& run, size_t file, int fd)
     : run_(run)
-    , ix_(run.gzidx)
+    , path_(run.files[file])
+    , ix_(run.gzidx[file])
     , fd_(fd)
   {}
   ~GzipSegFeed() override { ::close(fd_); }
-  Sizes layout(size_t chunk, int n_slots) override
+  static Sizes want(size_t chunk, const GzIndex& ix)
   {
-    comp_cap_ = std::max<size_t>(chunk / 2, (size_t)ix_->max_comp + 8);
-    dict_cap_ = chunk / 8 + 32768; // (32 KiB per 256 KiB of text at the default span)
-    tab_cap_ = std::max<size_t>(chunk / 4096, 64);
+    return Sizes{ chunk, std::max<size_t>(chunk / 2, (size_t)ix.max_comp + 8), chunk / 8 + 32768 }; // (32 KiB of history per 256 KiB of text at the default span)
+  }
+  void layout(const Sizes& slot, int n_slots) override
+  {
+    comp_cap_ = slot.comp;
+    dict_cap_ = slot.dict;
+    tab_cap_ = std::max<size_t>(slot.chunk / 4096, 64);
     slot_.resize((size_t)n_slots);
     for (Table& t : slot_) {
       t.segs.resize(tab_cap_);
     }
-    return Sizes{ chunk, comp_cap_, dict_cap_ };
   }
   size_t fill(int i, const SlotBuf& b, size_t chunk, bool& eof) override
   {
@@ -433,7 +463,7 @@ public:
     int err = 0;
     const size_t k = pread_full(fd_, b.comp, want, byte0, &err);
     if (k < want) {
-      note_input_failure("reading " + run_.opt.input + " failed at byte " + std::to_string(byte0 + k) + ": " + (err ? strerror(err) : "the file ends in front of a segment of its index (it was written during the run)"));
+      note_input_failure("reading " + path_ + " failed at byte " + std::to_string(byte0 + k) + ": " + (err ? strerror(err) : "the file ends in front of a segment of its index (it was written during the run)"));
       eof = true;
       return 0;
     }
@@ -454,7 +484,7 @@ public:
     uint32_t bad = UINT32_MAX;
     if (run_.ext.gzip_inflate(run_.ctx, b.comp, sl.comp_n, b.dict, sl.dict_n, sl.segs.data(), (uint32_t)sl.n_segs, b.text, chunk, &bad) != GRP_OK) {
       const uint64_t bit = sl.comp_file_off * 8 + (bad < sl.n_segs ? sl.segs[bad].comp_bit : 0);
-      note_input_failure("reading " + run_.opt.input + " failed: gzip segment " + (bad < sl.n_segs ? "" : "in the chunk ") + "at byte " + std::to_string(bit >> 3) + " (bit " + std::to_string(bit & 7) + "): " +
+      note_input_failure("reading " + path_ + " failed: gzip segment " + (bad < sl.n_segs ? "" : "in the chunk ") + "at byte " + std::to_string(bit >> 3) + " (bit " + std::to_string(bit & 7) + "): " +
                          (run_.vt.last_error ? run_.vt.last_error(run_.ctx) : "the engine could not inflate it"));
       return false;
     }
@@ -472,62 +502,14 @@ private:
     uint64_t comp_file_off = 0;
   };
   PathRun& run_;
-  std::shared_ptr<GzIndex> ix_; // the run's index, as it was when this pass began
+  const std::string path_;
+  std::shared_ptr<GzIndex> ix_; // the run's index of this file, as it was when this pass began
   int fd_;
   size_t next_ = 0; // the first segment of the next slot
   size_t comp_cap_ = 0, dict_cap_ = 0, tab_cap_ = 0;
   std::vector<Table> slot_;
   uint64_t n_segs_ = 0;
 };
-
-// Which feed reads run.opt.input (`in` is the source's own view of it, `chunk` the text of a slot as asked for).
-//   BGZF (grp_engine_ext::bgzf_inflate; GRP_BGZF=off: no): the first member is a complete BGZF member.
-//   A file that is gzip from its first byte and not taken by the BGZF form (grp_engine_ext::gzip_inflate;
-//   GRP_GZIP_INDEX=off: no): its segments where the run has an index of it — a file that changed between two passes
-//   drops it, an index with a segment larger than a slot is not used — else text through GzIndexReader, which builds one.
-//   Everything else: text.
-std::unique_ptr<Feed>
-open_feed(PathRun& run, InputFile& in, size_t chunk)
-{
-  const std::string& path = run.opt.input;
-  const char* e = getenv("GRP_BGZF");
-  if (run.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
-    // is the first member a complete BGZF member?  (a member is at most 64 KiB; a pipe cannot be pread: zlib)
-    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
-    if (fd >= 0) {
-      std::vector<unsigned char> head(BGZF_MAX_MEMBER);
-      const ssize_t k = pread(fd, head.data(), head.size(), 0);
-      grp_bgzf_block b;
-      if (k > 0 && bgzf_scan(head.data(), (size_t)k, &b, 1, nullptr, nullptr) == 1) {
-        return std::unique_ptr<Feed>(new BgzfFeed(run, fd));
-      }
-      ::close(fd);
-    }
-  }
-  std::unique_ptr<GzIndexReader> build;
-  if (run.ext.gzip_inflate && gzip_index_enabled()) {
-    if (run.gzidx && !run.gzidx->matches(path)) {
-      run.gzidx.reset(); // the file was written since: this pass builds a new one
-    }
-    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
-    struct stat st;
-    unsigned char magic[2] = { 0, 0 };
-    const bool gz = fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-    if (gz && run.gzidx && run.gzidx->max_text <= chunk) { // (a larger segment: the whole pass goes through zlib)
-      return std::unique_ptr<Feed>(new GzipSegFeed(run, fd));
-    }
-    if (gz && !run.gzidx) {
-      build.reset(new GzIndexReader(path, gzip_index_span(), gzip_index_max_bytes()));
-      if (!build->ok()) {
-        build.reset();
-      }
-    }
-    if (fd >= 0) {
-      ::close(fd);
-    }
-  }
-  return std::unique_ptr<Feed>(new TextFeed(run, in, std::move(build)));
-}
 
 // What a regular file's data begins with, decompressed if it is gzip (input_format: 1 FASTQ, 2 BAM, 0 neither), through a
 // view of its own on the file; -1: not a regular file — a pipe can only be peeked at, and BAM is not looked for there.
@@ -544,6 +526,89 @@ probe_format(const std::string& path)
   return input_format(head, n);
 }
 
+// How one file of a pass is read, decided when the pass begins — the slots are allocated once, for what the feeds of all
+// its files ask for — and carried out by open_feed when the reader thread comes to the file.  No descriptor is held in
+// between: a pass may have more files than a process may have descriptors.
+//   BGZF (grp_engine_ext::bgzf_inflate; GRP_BGZF=off: no): the first member is a complete BGZF member.
+//   A file that is gzip from its first byte and not taken by the BGZF form (grp_engine_ext::gzip_inflate;
+//   GRP_GZIP_INDEX=off: no): its segments where the run has an index of it — a file that changed between two passes
+//   drops its index, an index with a segment larger than a slot is not used — else text through GzIndexReader, which
+//   builds one.
+//   Everything else: text.
+struct FilePlan
+{
+  enum Kind { TEXT, BGZF, GZSEG } kind = TEXT;
+  bool build_index = false; // TEXT: a gzip file without an index, read through GzIndexReader
+  bool plain = false;       // a plain regular file, read with pread (InputFile) ...
+  uint64_t plain_size = 0;  // ... and its bytes
+  Feed::Sizes want{ 0, 0, 0 };
+};
+
+FilePlan
+plan_feed(PathRun& run, size_t file, size_t chunk)
+{
+  const std::string& path = run.files[file];
+  FilePlan pl;
+  pl.want = Feed::Sizes{ chunk, 0, 0 };
+  const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  if (fd < 0) {
+    return pl;
+  }
+  struct stat st;
+  const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+  unsigned char magic[2] = { 0, 0 };
+  const bool gz = regular && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+  const char* e = getenv("GRP_BGZF");
+  if (run.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
+    // is the first member a complete BGZF member?  (a member is at most 64 KiB; a pipe cannot be pread: zlib)
+    std::vector<unsigned char> head(BGZF_MAX_MEMBER);
+    const ssize_t k = pread(fd, head.data(), head.size(), 0);
+    grp_bgzf_block b;
+    if (k > 0 && bgzf_scan(head.data(), (size_t)k, &b, 1, nullptr, nullptr) == 1) {
+      pl.kind = FilePlan::BGZF;
+      pl.want = BgzfFeed::want(chunk);
+    }
+  }
+  if (pl.kind == FilePlan::TEXT && run.ext.gzip_inflate && gzip_index_enabled()) {
+    std::shared_ptr<GzIndex>& ix = run.gzidx[file];
+    if (ix && !ix->matches(path)) {
+      ix.reset(); // the file was written since: this pass builds a new one
+    }
+    if (gz && ix && ix->max_text <= chunk) { // (a larger segment: the file goes through zlib in this pass too)
+      pl.kind = FilePlan::GZSEG;
+      pl.want = GzipSegFeed::want(chunk, *ix);
+    }
+    pl.build_index = gz && !ix;
+  }
+  if (pl.kind == FilePlan::TEXT && regular && !gz && !getenv("GRP_ZLIB_READER")) {
+    pl.plain = true;
+    pl.plain_size = (uint64_t)st.st_size;
+  }
+  ::close(fd);
+  return pl;
+}
+
+std::unique_ptr<Feed>
+open_feed(PathRun& run, size_t file, const FilePlan& pl)
+{
+  const std::string& path = run.files[file];
+  if (pl.kind != FilePlan::TEXT) {
+    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd >= 0) {
+      return pl.kind == FilePlan::BGZF ? std::unique_ptr<Feed>(new BgzfFeed(run, file, fd)) : std::unique_ptr<Feed>(new GzipSegFeed(run, file, fd));
+    }
+    note_input_failure("reading " + path + " failed: it cannot be opened again: " + strerror(errno));
+  }
+  std::unique_ptr<GzIndexReader> build;
+  if (pl.kind == FilePlan::TEXT && pl.build_index) {
+    build.reset(new GzIndexReader(path, gzip_index_span(), gzip_index_max_bytes()));
+    if (!build->ok()) {
+      build.reset();
+    }
+  }
+  return std::unique_ptr<Feed>(new TextFeed(run, file, std::unique_ptr<InputFile>(new InputFile(path)), std::move(build)));
+}
+
 // Raw text chunks parsed, filtered and packed on the GPU (grpath_ingest.h).  An unaligned BAM input (gr_bam.hpp) takes the
 // same way: the feeds deliver its bytes, the header is skipped in front of the first parse — it may span chunks: the
 // carry of partial records holds it until it is complete — and grp_engine_ext::bam_parse stands where fastq_parse does.
@@ -551,23 +616,46 @@ probe_format(const std::string& path)
 // inflate, upload, parse, pack, fill or classify — so a pass costs max(read, GPU) per chunk instead of their sum.  Four
 // slots in ONE page-locked buffer; every slot has room in front of the bytes read for the unconsumed tail of
 // the chunk before it (a partial record), which is copied there before the parse.
+//
+// Several files: ONE source, one buffer, one reader thread and one pin for the pass.  At a file's end the
+// reader opens the next file's feed and goes on filling slots, so the next file's first chunk is on its way while the
+// consumer still works on the last chunks of the file before.  A slot says which file it belongs to, whether it is that
+// file's first and whether it is its last; the consumer parses a file's last chunk as a final one, begins every file
+// without a carried tail (and, BAM, with its header) and takes the format from the slot.  A feed lives from the reader's
+// first fill of its file to the consumer's inflate of that file's last slot.
 class GpuSource : public RecordSource
 {
 public:
-  GpuSource(PathRun& run, int format)
+  GpuSource(PathRun& run, const std::vector<int>& format)
     : run_(run)
-    , in_(run.opt.input)
     , format_(format)
   {
+    const size_t n_files = run.files.size();
     chunk_ = std::max<size_t>(ingest_chunk_bytes(), 64);
-    feed_ = open_feed(run_, in_, chunk_);
-    const Feed::Sizes sz = feed_->layout(chunk_, kSlots);
+    plan_.resize(n_files);
+    feeds_.resize(n_files);
+    Feed::Sizes sz{ chunk_, 0, 0 };
+    uint64_t largest = 0; // plain files, all of known size: the largest of them
+    bool sized = true;
+    for (size_t f = 0; f < n_files; ++f) {
+      plan_[f] = plan_feed(run_, f, chunk_);
+      sz.chunk = std::max(sz.chunk, plan_[f].want.chunk);
+      sz.comp = std::max(sz.comp, plan_[f].want.comp);
+      sz.dict = std::max(sz.dict, plan_[f].want.dict);
+      sized = sized && plan_[f].plain;
+      largest = std::max(largest, plan_[f].plain_size);
+    }
     chunk_ = sz.chunk;
     comp_cap_ = sz.comp;
     dict_cap_ = sz.dict;
-    if (in_.plain_size() != 0) { // a small file: one slot holds it all, no 2 x 256 MiB to allocate and page-lock
-      chunk_ = std::min<size_t>(chunk_, std::max<size_t>((size_t)in_.plain_size() + 1, size_t(1) << 16));
+    if (sized && largest != 0) { // small files: one slot holds any of them, no 2 x 256 MiB to allocate and page-lock
+      chunk_ = std::min<size_t>(chunk_, std::max<size_t>((size_t)largest + 1, size_t(1) << 16));
     }
+    layout_ = Feed::Sizes{ chunk_, comp_cap_, dict_cap_ };
+    // the first file's feed now: what is no regular file says what it is through it (is_fastq)
+    feeds_[0] = open_feed(run_, 0, plan_[0]);
+    feeds_[0]->layout(layout_, kSlots);
+    opened_ = feeds_[0]->ok();
     front_ = std::min<size_t>(std::max<size_t>(chunk_ / 16, 4096), (size_t)GRP_FASTQ_PREFETCH_FRONT); // (what a prefetched body may have in front of it, grpath_ingest.h)
     buf_.resize((size_t)kSlots * (front_ + chunk_ + comp_cap_ + dict_cap_)); // (the compressed bytes of the slots behind their texts, the histories behind those: one page-locked buffer)
     const char* pin_min = getenv("GRP_PIN_MIN_BYTES"); // tests: page-lock small buffers too
@@ -589,19 +677,27 @@ public:
     if (run_.vt.fastq_prefetch) {
       (void)run_.vt.fastq_prefetch(run_.ctx, nullptr, 0); // bodies handed over ahead of a parse that never came (an early end)
     }
-    if (getenv("GRP_TRACE_INGEST")) {
-      const Feed::Counts n = feed_->counts();
-      std::cerr << "GRP_TRACE_INGEST source: " << n_pre_[0] << " chunks, next chunk not ready at " << n_pre_[1] << ", uploads started ahead " << n_pre_[2] << "; seconds waiting for the reader " << t_tr_[0]
-                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << n.bgzf_blocks
-                << ", gzip segments inflated on the device " << n.gzip_segs << std::endl;
+    for (size_t f = 0; f < feeds_.size(); ++f) {
+      close_feed(f);
     }
-    feed_.reset();
+    if (getenv("GRP_TRACE_INGEST")) {
+      std::cerr << "GRP_TRACE_INGEST source: " << n_pre_[0] << " chunks, next chunk not ready at " << n_pre_[1] << ", uploads started ahead " << n_pre_[2] << "; seconds waiting for the reader " << t_tr_[0]
+                << ", in fastq_parse " << t_tr_[1] << ", in fastq_prefetch " << t_tr_[2] << ", copying tails " << t_tr_[3] << ", BGZF blocks inflated on the device " << counts_.bgzf_blocks
+                << ", gzip segments inflated on the device " << counts_.gzip_segs;
+      if (run_.files.size() > 1) {
+        std::cerr << "; files " << run_.files.size() << ", begun " << n_files_[0] << ", parse calls " << n_files_[1];
+      }
+      std::cerr << std::endl;
+    }
     if (pinned_) {
       run_.vt.fastq_unpin(run_.ctx); // before the buffer goes away: the engine cannot know when the host frees memory
     }
   }
-  bool ok() const override { return in_.ok(); }
-  bool is_fastq() override { return format_ < 0 ? in_.peek() == '@' : format_ != 0; } // (asked before the first chunk is read)
+  bool ok() const override { return run_.files.size() > 1 || opened_; }
+  bool is_fastq() override // (asked before the first chunk is read; several files: check_inputs has looked at them all)
+  {
+    return run_.files.size() > 1 || (format_[0] < 0 ? feeds_[0] && feeds_[0]->peek() == '@' : format_[0] != 0);
+  }
   bool next(Batch& b) override
   {
     release();
@@ -626,11 +722,33 @@ public:
         held_ = take_;
         take_ = (take_ + 1) % kSlots;
       }
-      if (!inflate_slot(held_)) { // (the failure is noted: the run ends with an error behind this pass)
+      const size_t file = sl->file;
+      const bool eof = sl->eof; // the FILE ends with this chunk
+      if (sl->first) {
+        // a file begins: nothing of the file before is carried into it — its last chunk was parsed as a final one, and
+        // what that left over was its own truncation
+        carry_.clear();
+        bam_header_done_ = false;
+        ++n_files_[0];
+      }
+      if ((long)file == skip_file_) { // behind a line that is no FASTQ header the file has ended for good: what the reader had read of it already
+        if (eof) {
+          close_feed(file);
+        }
+        if (sl->last) {
+          done_ = true;
+        }
+        continue;
+      }
+      const bool inflated = inflate_slot(held_);
+      if (eof) {
+        close_feed(file); // (its last slot has been inflated: nothing reads through it any more)
+      }
+      if (!inflated) { // (the failure is noted: the run ends with an error behind this pass)
         done_ = true;
         break;
       }
-      const bool eof = sl->eof;
+      const std::string& path = run_.files[file];
       char* data = slot_data(held_);
       // the tail of the chunk before, in front of what was read
       char* text = nullptr;
@@ -649,14 +767,25 @@ public:
         memcpy(big_.data() + carry_.size(), data, sl->n);
         text = big_.data();
       }
-      uint64_t text_off = sl->file_off - carry_.size(); // stream offset of text[0]
-      if (fill == 0) {
+      uint64_t text_off = sl->file_off - carry_.size(); // offset of text[0] in the file's stream
+      if (fill == 0) { // (a file without a byte, or one whose last chunk is empty)
+        if (sl->last) {
+          done_ = true;
+        }
+        continue;
+      }
+      int format = format_[file];
+      if (format < 0) { // no regular file: FASTQ, if anything
+        format = text[0] == '@' ? 1 : 0;
+      }
+      if (format == 0 && run_.files.size() > 1) {
+        note_input_failure("reading " + path + " failed: it is neither FASTQ nor BAM");
         done_ = true;
         break;
       }
       uint64_t n_rec = 0, used = 0;
       int stopped = 0;
-      const bool bam = format_ == 2;
+      const bool bam = format == 2;
       if (bam && !bam_header_done_) {
         // the records begin behind the header; one that is not complete yet consumes nothing
         uint64_t hb = 0;
@@ -667,7 +796,7 @@ public:
           continue;
         }
         if (hrc != 1) {
-          note_bam_failure(run_.opt.input, text_off, hrc == 0 ? "the stream ends inside the BAM header (truncated)" : "not a BAM header");
+          note_bam_failure(path, text_off, hrc == 0 ? "the stream ends inside the BAM header (truncated)" : "not a BAM header");
           done_ = true;
           break;
         }
@@ -676,17 +805,21 @@ public:
         fill -= hb;
         text_off += hb;
         if (fill == 0 && eof) { // a header and no record
-          done_ = true;
-          break;
+          carry_.clear();
+          if (sl->last) {
+            done_ = true;
+          }
+          continue;
         }
       }
       const double tp0 = now_s();
       uint64_t bad_off = 0;
+      ++n_files_[1];
       const int prc = bam ? run_.ext.bam_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &bad_off)
                           : run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
       t_tr_[1] += now_s() - tp0;
       if (prc == GRP_ERR_INVALID && bam) { // a refused record: the input's failure, not the engine's
-        note_bam_failure(run_.opt.input, text_off + bad_off, run_.vt.last_error ? run_.vt.last_error(run_.ctx) : nullptr);
+        note_bam_failure(path, text_off + bad_off, run_.vt.last_error ? run_.vt.last_error(run_.ctx) : nullptr);
         done_ = true;
         break;
       }
@@ -703,7 +836,12 @@ public:
         continue;
       }
       carry_.assign(text + used, text + fill);
-      if (eof || stopped) {
+      if (stopped && !eof) {
+        // the file has ended here, like a reader at the end of its input; the reader thread leaves it at its next chunk
+        skip_file_ = (long)file;
+        abandon_.store((long)file);
+      }
+      if ((eof || stopped) && file + 1 == run_.files.size()) {
         done_ = true;
       }
       if (n_rec == 0) {
@@ -713,6 +851,7 @@ public:
       meta_.resize(n_rec);
       run_.vt.fastq_records(fq_, meta_.data());
       b.text = text;
+      b.file = file;
       b.base_off = text_off;
       b.rec.resize(n_rec);
       for (size_t i = 0; i < n_rec; ++i) {
@@ -731,7 +870,9 @@ public:
   // one after the other); issued one chunk ahead — with the tail of the chunk before copied in front first — it still lay on
   // the path of every chunk (copy 5.5 ms + parse + the host's share against a fill of 7 ms).  The body does not depend on
   // that tail: it goes up two chunks ahead, the engine leaves room in front of it and the parse uploads the tail alone
-  // (grpath_ingest.h: grp_fastq_prefetch).
+  // (grpath_ingest.h: grp_fastq_prefetch).  The bodies may be another file's, of another format: the engine is handed bytes.
+  // Not handed over ahead: the first chunk of a BAM file, nor anything behind it — its parse begins behind the header, not at
+  // the body, so the engine would take it for another text and drop every pending body (they are parsed in the order issued).
   void prefetch_next()
   {
     ++n_pre_[0];
@@ -747,13 +888,16 @@ public:
           n_pre_[1] += ahead == 0;
           return; // the reader is still at it (and the slots behind it are not ready either)
         }
-        if (slot_[j].eof && slot_[j].n == 0) {
+        if (slot_[j].last && slot_[j].n == 0) {
           return;
         }
         n = slot_[j].n; // (a READY slot is the consumer's until it releases it)
       }
-      if (slot_[j].uploaded || n == 0) {
+      if (slot_[j].uploaded || n == 0 || (long)slot_[j].file == skip_file_) {
         continue;
+      }
+      if (slot_[j].first && format_[slot_[j].file] == 2) {
+        return;
       }
       if (!inflate_slot(j)) {
         return;
@@ -797,8 +941,11 @@ private:
   {
     enum State { FREE, READY } state = FREE;
     size_t n = 0;          // bytes of text
-    uint64_t file_off = 0; // stream offset of the first of them
-    bool eof = false;      // the data ends with this chunk
+    size_t file = 0;       // which of the run's files they are from (and so their format, and the feed that inflates them)
+    uint64_t file_off = 0; // offset of the first of them in that file's stream
+    bool first = false;    // the file begins with this chunk
+    bool eof = false;      // the file ends with this chunk ...
+    bool last = false;     // ... and it is the last file: the data ends with it
     bool uploaded = false; // consumer's: the engine has been handed the body ahead of its parse (prefetch_next)
     bool inflated = false, bad = false; // consumer's: Feed::inflate has run / has failed
   };
@@ -814,13 +961,27 @@ private:
     Slot& sl = slot_[j];
     if (!sl.inflated) {
       sl.inflated = true;
-      sl.bad = !feed_->inflate(j, slot_buf(j), chunk_);
+      sl.bad = !feeds_[sl.file]->inflate(j, slot_buf(j), chunk_);
     }
     return !sl.bad;
   }
+  // consumer (or the destructor, behind the reader's end): the file's feed is done with; its counts stay
+  void close_feed(size_t f)
+  {
+    if (feeds_[f]) {
+      const Feed::Counts n = feeds_[f]->counts();
+      counts_.bgzf_blocks += n.bgzf_blocks;
+      counts_.gzip_segs += n.gzip_segs;
+      feeds_[f].reset();
+    }
+  }
+  // Slot after slot, file after file.  feeds_[f] is written here before the first slot of file f is published (under the
+  // mutex) and reset by the consumer behind its last: the two threads never hold it at the same time.
   void read_loop()
   {
+    size_t file = 0;
     uint64_t off = 0;
+    bool first = true;
     for (int i = 0;; i = (i + 1) % kSlots) {
       {
         std::unique_lock<std::mutex> g(mu_);
@@ -829,20 +990,39 @@ private:
           return;
         }
       }
+      if (!feeds_[file]) { // (the first file's is the constructor's)
+        feeds_[file] = open_feed(run_, file, plan_[file]);
+        feeds_[file]->layout(layout_, kSlots);
+      }
       bool eof = false;
       slot_[i].inflated = slot_[i].bad = false; // (a FREE slot is the reader's)
-      const size_t got = feed_->fill(i, slot_buf(i), chunk_, eof);
+      size_t got = 0;
+      if (abandon_.load() == (long)file) {
+        eof = true; // the consumer has met the file's end in front of the end of its bytes
+      } else {
+        got = feeds_[file]->fill(i, slot_buf(i), chunk_, eof);
+      }
+      const bool last = eof && file + 1 == run_.files.size();
       {
         std::lock_guard<std::mutex> g(mu_);
         slot_[i].n = got;
+        slot_[i].file = file;
         slot_[i].file_off = off;
+        slot_[i].first = first;
         slot_[i].eof = eof;
+        slot_[i].last = last;
         slot_[i].state = Slot::READY;
       }
       cv_.notify_all();
       off += got;
-      if (eof) {
+      first = false;
+      if (last) {
         return;
+      }
+      if (eof) {
+        ++file;
+        off = 0;
+        first = true;
       }
     }
   }
@@ -854,12 +1034,17 @@ private:
     }
   }
   PathRun& run_;
-  InputFile in_;
-  std::unique_ptr<Feed> feed_;
-  std::vector<char> buf_;  // kSlots x [front | chunk], then what the feed asked for beside them
+  const std::vector<int> format_;   // probe_format of every file
+  std::vector<FilePlan> plan_;      // how every file is read (decided when the pass began)
+  std::vector<std::unique_ptr<Feed>> feeds_; // the feeds of the files between the reader's first fill and the consumer's last inflate
+  Feed::Sizes layout_{ 0, 0, 0 };   // the slots, as every feed is told
+  Feed::Counts counts_;             // of the feeds that are done with
+  bool opened_ = false;             // the first file could be opened
+  std::vector<char> buf_;  // kSlots x [front | chunk], then what the feeds asked for beside them
   uint64_t n_pre_[3] = { 0, 0, 0 }; // developer trace: chunks returned, next slot not ready, prefetches the engine took
   double t_tr_[4] = { 0, 0, 0, 0 };  // developer trace: seconds waiting for the reader / in the parse call / in the prefetch calls / copying tails
-  std::vector<char> carry_; // unconsumed tail of the chunk before
+  uint64_t n_files_[2] = { 0, 0 };  // developer trace: files begun, parse calls
+  std::vector<char> carry_; // unconsumed tail of the chunk before (of the same file)
   std::vector<char> big_;
   size_t chunk_ = 0, front_ = 0;
   size_t comp_cap_ = 0, dict_cap_ = 0; // the capacities of a slot beside its text (Feed::Sizes)
@@ -875,8 +1060,9 @@ private:
   int held_ = -1; // the slot the caller's current batch lives in
   bool stop_ = false;
   bool done_ = false, failed_ = false;
-  const int format_;             // probe_format of the input
-  bool bam_header_done_ = false; // BAM: the header has been skipped
+  long skip_file_ = -1;            // consumer's: the file that ended at a line that is no FASTQ header
+  std::atomic<long> abandon_{ -1 }; // ... said to the reader thread
+  bool bam_header_done_ = false;   // BAM: the header of the file being parsed has been skipped
   void* fq_ = nullptr;
   std::vector<grp_fastq_record> meta_;
 };
@@ -886,12 +1072,38 @@ private:
 std::unique_ptr<RecordSource>
 open_source(PathRun& run)
 {
-  const bool gpu = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
-  const int format = gpu ? probe_format(run.opt.input) : 0;
-  if (gpu && !(format == 2 && !run.ext.bam_parse)) { // (a BAM file and an engine without bam_parse: the host reader)
+  if (run.files.empty()) {
+    run.files.push_back(run.opt.input);
+  }
+  run.gzidx.resize(run.files.size());
+  bool gpu = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
+  std::vector<int> format(run.files.size(), 0);
+  for (size_t f = 0; gpu && f < run.files.size(); ++f) {
+    format[f] = probe_format(run.files[f]);
+    gpu = !(format[f] == 2 && !run.ext.bam_parse); // (a BAM file and an engine without bam_parse: the host reader, for all the files)
+  }
+  if (gpu) {
     return std::unique_ptr<RecordSource>(new GpuSource(run, format));
   }
   return std::unique_ptr<RecordSource>(new HostSource(run));
+}
+
+std::string
+check_inputs(const PathRun& run)
+{
+  for (const std::string& path : run.files) {
+    struct stat st;
+    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd < 0) {
+      return path + ": cannot be opened: " + strerror(errno);
+    }
+    const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+    ::close(fd);
+    if (regular && st.st_size != 0 && probe_format(path) <= 0) {
+      return path + ": neither FASTQ nor BAM";
+    }
+  }
+  return std::string();
 }
 
 } // namespace gr

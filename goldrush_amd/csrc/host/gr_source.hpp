@@ -3,6 +3,8 @@
 // the host (engines without the ingest entry points); GpuSource hands raw text chunks to the engine (grpath_ingest.h),
 // from plain text, gzip through zlib, BGZF members or the segments of an indexed gzip file (gr_source.cpp).
 // An unaligned BAM input (gr_bam.hpp) is read as its FASTQ twin by either source.
+// A run may have several input files (PathRun::files), of any of these formats: one source reads them one after the other
+// in a pass, each to its own end, and hands out their records as those of one file that holds them in that order.
 #pragma once
 #include "../../../include/grpath_host.h"
 #include "gr_bam.hpp"
@@ -38,9 +40,12 @@ struct PathRun
   bool merge_rccl = false;   // ... merged by RCCL inside the engine (else staged through host memory and /dev/shm)
   void* shm = nullptr;       // gr_shm_allgather handle
   int32_t device = -1;       // HIP device ordinal of this rank
-  // a plain gzip input: the restart points the first complete pass over it wrote down (gr_gzidx.hpp); the passes behind
-  // it inflate its segments on the device
-  std::shared_ptr<GzIndex> gzidx;
+  // the files the run reads, in order: every -i, ".fofn" lists expanded (expand_inputs).  A pass reads them one after the
+  // other through ONE source; a batch never spans two of them
+  std::vector<std::string> files;
+  // a plain gzip input: the restart points the first pass that read that file to its end wrote down (gr_gzidx.hpp); the
+  // passes behind it inflate its segments on the device.  One per file, each built, dropped and used on its own
+  std::vector<std::shared_ptr<GzIndex>> gzidx;
 
   int fail_engine(const char* what)
   {
@@ -49,7 +54,7 @@ struct PathRun
   }
 };
 
-// A batch of consecutive FASTQ records; offsets are relative to `text`.
+// A batch of consecutive FASTQ records of one file; offsets are relative to `text`.
 struct Rec
 {
   size_t id_off, id_len, seq_off, seq_len, qual_off, qual_len;
@@ -58,7 +63,8 @@ struct Rec
 struct Batch
 {
   const char* text = nullptr;
-  uint64_t base_off = 0;            // offset of text[0] in the (decompressed) input stream
+  size_t file = 0;                  // which of PathRun::files the records come from
+  uint64_t base_off = 0;            // offset of text[0] in that file's (decompressed) stream
   std::vector<Rec> rec;
   std::vector<uint32_t> avg, delta; // calc_phred_average, valid where stats() ran
   std::vector<uint8_t> non_acgt;    // find_first_not_of("ACGTacgt") != npos
@@ -103,5 +109,9 @@ public:
 
 // GpuSource where the engine has the ingest entry points (GRP_HOST_INGEST: no), else HostSource
 std::unique_ptr<RecordSource> open_source(PathRun& run);
+// Several inputs: every one of them looked at before the first pass.  Empty: all can be read (FASTQ, BAM, a file without a
+// byte, or something that is no regular file and shows what it is when it is read); else the line that names the first
+// file that cannot be opened or is neither FASTQ nor BAM.
+std::string check_inputs(const PathRun& run);
 
 } // namespace gr

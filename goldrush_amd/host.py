@@ -132,6 +132,7 @@ SIGNATURES = {
     "gr_pack_2bit": (C.c_int, [C.c_char_p, C.c_size_t, _vp]),
     "gr_effective_cpus": (C.c_uint, []),
     "gr_process_options_dump": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t]),
+    "gr_inputs_dump": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t]),
     "gr_ntcard_sbits": (C.c_uint, [C.c_uint64]),
     "gr_ntcard_f0": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint]),
     "gr_ntcard_split": (C.c_size_t, [C.c_char_p, C.c_size_t, C.c_uint, C.c_uint, _vp, _vp, _vp, C.c_size_t]),
@@ -221,6 +222,16 @@ def process_options_dump(argv):
     buf = C.create_string_buffer(1 << 16)
     rc = load().gr_process_options_dump(len(args), arr, buf, len(buf))
     return rc, dict(l.split("=", 1) for l in buf.value.decode().splitlines() if "=" in l)
+
+
+def inputs_dump(argv):
+    """(exit code or -1, [(name, value)]) of the run's inputs: "input", every "inputs" in order, every "file" read in
+    order (".fofn" lists expanded), or the "error" that names a bad list."""
+    args = [b"goldrush_path"] + [a.encode() if isinstance(a, str) else a for a in argv]
+    arr = (C.c_char_p * (len(args) + 1))(*args, None)
+    buf = C.create_string_buffer(1 << 20)
+    rc = load().gr_inputs_dump(len(args), arr, buf, len(buf))
+    return rc, [tuple(l.split("=", 1)) for l in buf.value.decode().splitlines() if "=" in l]
 
 
 def ntcard_split(seq: bytes, k: int, h: int):

@@ -120,6 +120,10 @@ size_t gr_ntcard_split(const char* seq, size_t n, unsigned k, unsigned h, uint64
  * option into out (for the parity tests).  Returns -1 when the run would continue,
  * otherwise the exit code the reference exits with (messages go to stdout / stderr). */
 int gr_process_options_dump(int argc, char** argv, char* out, size_t cap);
+/* The inputs of a run as process_options and the expansion of ".fofn" lists see them: "input=" (the last -i), one
+ * "inputs=" line per -i in command-line order, one "file=" line per file read, in order — or "error=" and the text that
+ * names the list that is unreadable, empty or nested.  Returns as above, 1 for such a list. */
+int gr_inputs_dump(int argc, char** argv, char* out, size_t cap);
 /* CPUs this process may use: min(affinity mask, cgroup cpu.max quota) */
 unsigned gr_effective_cpus(void);
 
