@@ -818,8 +818,11 @@ launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, 
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, THREADS, g.lds));
     // Round 6: a window that applies inserts itself keeps the probes' fingerprints of the tile in progress and of the
     // tile before it in LDS (DevStreamCtl::n_fp) — as many of the two buffers as fit WITHOUT costing a resident workgroup
-    // (three per CU is what the launch runs at, below): C2's geometry 27.9 + 2 x 12.3 KB, three of them in the CU's 160 KB;
-    // h = 5 with tiles of 1000 (48 KB of count table) has no room: such a window hands everything behind an insert out again.
+    // (three per CU is what the launch runs at, below — or fewer, where the kernel's registers allow no more): C2's geometry
+    // 27.9 + 2 x 12.3 KB, three of them in the CU's 160 KB; h = 5 with tiles of 1000 (48 KB of count table) would have no
+    // room beside three, but it does keep on the MI355X (its instance must be resident twice per CU there: ONE buffer, 25 KB,
+    // fits beside that).  h = 5 with tiles of 1500 (one buffer: 36 KB) has no room: such a window hands everything behind an insert out
+    // again (tests/test_gpu_stream_striped.py holds both).
     DevStreamCtl sc_fit = *stream_ctl;
     QueryGeom g_fit = g;
     sc_fit.n_fp = 0;

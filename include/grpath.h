@@ -377,8 +377,8 @@ int grp_classify_reads_end(grp_ctx* ctx, uint32_t slot, grp_read_decision* decis
  *           — the caller aborts it and issues grp_insert_read as before.
  *   _end    returns 1 or 2 instead of GRP_OK when the launch ended WITHOUT applying the insert posted
  *           last: nothing was inserted, the caller issues grp_insert_read for it.  1: the launch had left
- *           before the command reached it (an abort overtook it; a striped window whose own stripes were
- *           all decided) — nothing is wrong.  2: its workgroups were not all resident (a shared device) and
+ *           before the command reached it (an abort overtook it; a striped window does not leave by itself,
+ *           below) — nothing is wrong.  2: its workgroups were not all resident (a shared device) and
  *           the first grid-wide wait ran into its time limit — parked windows do not work here.
  * Stream-ordered like every other call: an insert issued after _abort runs behind the
  * (draining) window.
@@ -409,10 +409,11 @@ int grp_classify_stream_begin_resumable(grp_ctx* ctx, const grp_reads* reads, ui
 int grp_classify_stream_begin_striped_resumable(grp_ctx* ctx, const grp_reads* reads, uint32_t first, uint32_t count, const grp_decide_params* params, uint32_t slot, uint32_t stripe_reads, uint32_t n_owners, uint32_t owner, const grp_read_decision** decisions);
 int grp_classify_stream_resumable(grp_ctx* ctx, uint32_t slot);
 /* ... and whether the insert posted last has been applied: 1 yes, 0 not yet, 2 the launch has ended (or given up) without
- * it — a striped window's launch leaves when its own stripes are decided, and the read that inserts may be another
- * rank's: the caller then ends the window (grp_classify_stream_end says 1 or 2) and issues grp_insert_read.  A rank of
- * several waits for this before it goes on, so that no window queued behind this one starts on a replica without
- * the insert unnoticed. */
+ * it — an abort overtook the command, a grid-wide wait ran into its time limit, or nobody answered the parked window
+ * for its idle limit.  (A striped window's launch does NOT leave when its own stripes are decided: it stays for the
+ * other ranks' inserts until _abort, see above.)  On 2 the caller ends the window (grp_classify_stream_end says 1 or 2)
+ * and issues grp_insert_read.  A rank of several waits for this before it goes on, so that no window queued behind this
+ * one starts on a replica without the insert unnoticed. */
 int grp_classify_stream_insert_done(grp_ctx* ctx, uint32_t slot);
 int grp_classify_stream_insert(grp_ctx* ctx, uint32_t slot, uint32_t read_idx, uint32_t tile_start, uint32_t tile_end, uint32_t block_tiles, uint32_t first_id, uint32_t id_offset, uint32_t* generation);
 int grp_classify_stream_abort(grp_ctx* ctx, uint32_t slot);

@@ -380,10 +380,11 @@ class OracleEngine:
         return vt
 
 
-def serial_reference(orc, m, seeds, tile, k, reads, block=10, threshold=10, u=5, a=1, silver=False, target_bases=0, max_paths=1):
+def serial_reference(orc, m, seeds, tile, k, reads, block=10, threshold=10, u=5, a=1, silver=False, target_bases=0, max_paths=1, counters=None):
     """The reference's serial loop (process_read, goldrush_path.cpp:892-1094)
     stated with oracle primitives; returns the commit tuples the classifier
-    should produce: (read, kind, num_tiles, num_assigned, trim_start, trim_end, first_id, path)."""
+    should produce: (read, kind, num_tiles, num_assigned, trim_start, trim_end, first_id, path).
+    `counters`: a list that takes (hits, misses) of every read's query, at the ID state the loop queried it in."""
     oseeds = orc.Seeds(seeds)
     mf = orc.MiBF(m, oseeds, tile, k)
     for s in reads:
@@ -409,6 +410,8 @@ def serial_reference(orc, m, seeds, tile, k, reads, block=10, threshold=10, u=5,
     for ri, seq in enumerate(reads):
         res = mf.query_read(seq)
         n = len(res)
+        if counters is not None:
+            counters.append((sum(r[3][1] for r in res), sum(r[3][2] for r in res)))
         o_ids, o_b, na = orc.smooth_tiles([r[0] for r in res], [r[2] for r in res], threshold)
         wpath = path
         if n - na >= u and na <= a:
