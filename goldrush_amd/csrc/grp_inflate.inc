@@ -742,6 +742,148 @@ k_inflate_crc(const Entry* __restrict__ entries, const uint64_t* __restrict__ to
     status[i] = INF_CRC_MISMATCH;
   }
 }
+
+// ---- grp_records_fetch: records out of the inflated text, formatted as the host program writes them ---------------------
+// Copy-and-translate work beside a decoder that costs some 300 cycles per byte: one workgroup per record, no LDS, no
+// barrier (no thread reads what another wrote).  Every part of a record — id, bases, qualities — is a span of the output
+// that is filled from a span of the text: single bytes up to the destination's first 16-byte boundary, 16-byte stores
+// behind it (their source read as 16-byte words where it happens to share the destination's alignment, as bytes where
+// not), single bytes for what is left.  No load leaves the record's own id, bases or qualities, no store its output range.
+constexpr int EMIT_THREADS = 256;
+
+enum EmitMode
+{
+  EMIT_COPY = 0,   // ids, qualities of FASTQ text
+  EMIT_UPPER = 1,  // bases of FASTQ text: a-z folded to upper case, as SeqReader folds what the reference later writes
+  EMIT_PLUS33 = 2, // raw Phred bytes of a BAM record
+  EMIT_BAM_SEQ = 3 // 4-bit codes, high half first: src is the byte of base 0, `first` the first base written
+};
+
+template <int MODE>
+__device__ __forceinline__ uint8_t
+emit_byte(const uint8_t* __restrict__ src, uint32_t first, uint32_t j)
+{
+  if constexpr (MODE == EMIT_BAM_SEQ) {
+    const uint32_t b = first + j;
+    const uint32_t code = (b & 1u) ? (src[b >> 1] & 15u) : (uint32_t)(src[b >> 1] >> 4);
+    // "=ACMGRSVTWYHKDBN", eight characters to a word
+    const uint64_t w = code < 8 ? 0x56535247'4d43413dull : 0x4e42444b'48595754ull;
+    return (uint8_t)(w >> (8 * (code & 7u)));
+  } else {
+    const uint8_t ch = src[j];
+    if constexpr (MODE == EMIT_UPPER) {
+      return (ch >= 'a' && ch <= 'z') ? (uint8_t)(ch - 32) : ch;
+    } else if constexpr (MODE == EMIT_PLUS33) {
+      return (uint8_t)(ch + 33);
+    } else {
+      return ch;
+    }
+  }
+}
+
+template <int MODE>
+__device__ __forceinline__ uint32_t
+emit_word(uint32_t w)
+{
+  uint32_t r = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const uint8_t ch = (uint8_t)(w >> (8 * b));
+    r |= (uint32_t)emit_byte<MODE>(&ch, 0, 0) << (8 * b);
+  }
+  return r;
+}
+
+// dst[0, n) from src (text modes: its bytes [0, n); EMIT_BAM_SEQ: bases [first, first + n) of the codes at src)
+template <int MODE>
+__device__ __forceinline__ void
+emit_span(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t first, uint32_t n)
+{
+  const uint32_t tid = threadIdx.x;
+  uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15u)) & 15u);
+  head = head < n ? head : n;
+  const uint32_t n16 = (n - head) >> 4, tail0 = head + 16 * n16;
+  for (uint32_t j = tid; j < head; j += EMIT_THREADS) {
+    dst[j] = emit_byte<MODE>(src, first, j);
+  }
+  uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+  if (MODE != EMIT_BAM_SEQ && ((uintptr_t)(src + head) & 15u) == 0) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(src + head); // (words inside src[head, tail0))
+    for (uint32_t i = tid; i < n16; i += EMIT_THREADS) {
+      const uint4 v = s4[i];
+      d4[i] = make_uint4(emit_word<MODE>(v.x), emit_word<MODE>(v.y), emit_word<MODE>(v.z), emit_word<MODE>(v.w));
+    }
+  } else {
+    for (uint32_t i = tid; i < n16; i += EMIT_THREADS) {
+      uint32_t w[4] = { 0, 0, 0, 0 };
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        w[k >> 2] |= (uint32_t)emit_byte<MODE>(src, first, head + 16 * i + (uint32_t)k) << (8 * (k & 3));
+      }
+      d4[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  for (uint32_t j = tail0 + tid; j < n; j += EMIT_THREADS) {
+    dst[j] = emit_byte<MODE>(src, first, j);
+  }
+}
+
+// out_base: the offset in the caller's buffer that out[0] stands for (a multiple of 16, so that a record's alignment is
+// that of its out_off); delog: the ingest's table for the format's quality bytes (ingest_phred_table)
+__global__ void __launch_bounds__(EMIT_THREADS)
+k_emit_records(const uint8_t* __restrict__ text, const grp_fetch_record* __restrict__ recs, uint32_t n_recs, uint32_t out_flags, uint64_t out_base, uint8_t* __restrict__ out, const double* __restrict__ delog, double* __restrict__ sums)
+{
+  const uint32_t r = blockIdx.x;
+  if (r >= n_recs) {
+    return;
+  }
+  const grp_fetch_record rec = recs[r];
+  const bool fastq = (out_flags & GRP_FETCH_FASTQ) != 0, bam = (out_flags & GRP_FETCH_BAM) != 0, trimmed = (rec.flags & GRP_FETCH_REC_TRIMMED) != 0;
+  const uint32_t tid = threadIdx.x;
+  uint8_t* o = out + (rec.out_off - out_base);
+  if (tid == 0) {
+    o[0] = fastq ? '@' : '>';
+  }
+  emit_span<EMIT_COPY>(o + 1, text + rec.id_off, 0, rec.id_len);
+  const char* suffix = trimmed ? "_trimmed\n" : "_untrimmed\n";
+  const uint32_t n_suffix = trimmed ? 9u : 11u;
+  if (tid < n_suffix) {
+    o[1 + rec.id_len + tid] = (uint8_t)suffix[tid];
+  }
+  uint8_t* ob = o + 1 + rec.id_len + n_suffix;
+  if (bam) {
+    emit_span<EMIT_BAM_SEQ>(ob, text + rec.seq_off, rec.seq_from, rec.n_seq);
+  } else {
+    emit_span<EMIT_UPPER>(ob, text + rec.seq_off + rec.seq_from, 0, rec.n_seq);
+  }
+  if (tid == 0) {
+    ob[rec.n_seq] = '\n';
+  }
+  const uint8_t* q = text + rec.qual_off + rec.qual_from;
+  if (fastq) {
+    uint8_t* oq = ob + rec.n_seq + 1;
+    if (tid == 0) {
+      oq[0] = '+';
+      oq[1] = '\n';
+      oq[2 + rec.n_qual] = '\n';
+    }
+    if (bam) {
+      emit_span<EMIT_PLUS33>(oq + 2, q, 0, rec.n_qual);
+    } else {
+      emit_span<EMIT_COPY>(oq + 2, q, 0, rec.n_qual);
+    }
+  }
+  if (tid == 0) { // one dependent chain of additions, as in k_fq_phred
+    // The chain's loads must be VECTOR loads, so the address goes through a VGPR the compiler cannot see through.  q is
+    // the same in every lane, and left to itself the compiler read the qualities through the scalar unit: one
+    // s_load_dwordx16 with q as its base and the byte index as its offset, which for a q that is not dword-aligned fetched
+    // (q & ~3) + (index & ~3) — the 64 bytes that begin up to 4 in front of the ones asked for (seen on the MI355X: the sum of
+    // a slice that begins 1 byte behind a 16-byte boundary; the emitted bytes, all vector loads, were right).
+    uintptr_t qa = reinterpret_cast<uintptr_t>(q);
+    asm volatile("" : "+v"(qa));
+    sums[r] = phred_chain(reinterpret_cast<const uint8_t*>(qa), 0, rec.n_qual, 0.0, delog);
+  }
+}
 #endif
 
 // tab[4][256] (slicing by 4) and x2n[32] of the reflected gzip polynomial
@@ -849,17 +991,16 @@ inflate_crc_tables(grp_ctx* c)
   return GRP_OK;
 }
 
-// grp_bgzf_inflate and grp_gzip_inflate (a BGZF call has no histories: dict == nullptr, n_dict == 0)
+// the checks of a table that are made before anything is launched; *total = the bytes of text its entries hold
 template <class Entry>
 int
-inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const Entry* entries, uint32_t n, char* text_out, uint64_t text_cap, uint32_t* bad)
+inflate_check_table(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const Entry* entries, uint32_t n, uint32_t* bad, uint64_t* total)
 {
   using F = InfFormat<Entry>;
   if ((!comp && n_comp) || (!dict && n_dict) || (!entries && n) || n_comp > (1ull << 32) || n_dict > (1ull << 32) || n > MAX_GRID_WGS) {
     return set_err(c, GRP_ERR_INVALID, "%s: bad argument (%s)", F::fn, F::limits);
   }
-  // the table is checked before anything is launched
-  uint64_t total = 0;
+  *total = 0;
   for (uint32_t i = 0; i < n; ++i) {
     if (const char* why = F::check_entry(entries[i], n_comp, n_dict)) {
       if (bad) {
@@ -867,9 +1008,25 @@ inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp,
       }
       return F::refuse_entry(c, i, why, entries[i], n_comp, n_dict);
     }
-    total += entries[i].text_len;
+    *total += entries[i].text_len;
   }
-  if (total > text_cap || (total && !text_out)) {
+  return GRP_OK;
+}
+
+// grp_bgzf_inflate and grp_gzip_inflate (a BGZF call has no histories: dict == nullptr, n_dict == 0).  `keep_text`: the
+// text is not copied to the caller (text_out and text_cap are not looked at): it is in p.d_text, entry i's at p.h_toff[i],
+// when the call returns GRP_OK (grp_records_fetch)
+template <class Entry>
+int
+inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const Entry* entries, uint32_t n, char* text_out, uint64_t text_cap, uint32_t* bad, bool keep_text = false)
+{
+  using F = InfFormat<Entry>;
+  // the table is checked before anything is launched
+  uint64_t total = 0;
+  if (const int rc = inflate_check_table(c, comp, n_comp, dict, n_dict, entries, n, bad, &total)) {
+    return rc;
+  }
+  if (!keep_text && (total > text_cap || (total && !text_out))) {
     return set_err(c, GRP_ERR_INVALID, "%s: the %s hold %llu bytes of text, the caller's buffer %llu", F::fn, F::nouns, (unsigned long long)total, (unsigned long long)text_cap);
   }
   if (n == 0) {
@@ -918,7 +1075,7 @@ inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp,
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(p.ev1, st));
   HIP_TRY(c, hipMemcpyAsync(p.h_status.p, p.d_status, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (total) {
+  if (total && !keep_text) {
     HIP_TRY(c, hipMemcpyAsync(text_out, p.d_text, total, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -979,6 +1136,123 @@ grp_gzip_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t
     *bad_seg = UINT32_MAX;
   }
   return inflate_entries(c, c->gzip, comp, n_comp, dict, n_dict, segs, n_segs, text_out, text_cap, bad_seg);
+}
+
+namespace {
+
+// grp_records_fetch for either kind of unit
+template <class Entry>
+int
+records_fetch(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const Entry* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs,
+              uint32_t out_flags, char* out, uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record)
+{
+  // both tables are checked before anything is launched
+  uint64_t total = 0;
+  if (const int rc = inflate_check_table(c, comp, n_comp, dict, n_dict, units, n_units, bad_unit, &total)) {
+    return rc;
+  }
+  if ((!recs && n_recs) || n_recs > MAX_GRID_WGS || (out_flags & ~(GRP_FETCH_FASTQ | GRP_FETCH_BAM)) || (n_recs && (!out || !sums))) {
+    return set_err(c, GRP_ERR_INVALID, "grp_records_fetch: bad argument (at most 2^22 records per call, out_flags 0 .. 3)");
+  }
+  const bool fastq = (out_flags & GRP_FETCH_FASTQ) != 0, bam = (out_flags & GRP_FETCH_BAM) != 0;
+  const auto inside = [total](uint64_t off, uint64_t len) { return off <= total && len <= total - off; };
+  std::vector<std::pair<uint64_t, uint64_t>> span(n_recs); // [begin, end) in `out`
+  for (uint32_t i = 0; i < n_recs; ++i) {
+    const grp_fetch_record& r = recs[i];
+    // the bytes the written bases are read from (BAM: two bases to a byte)
+    const uint64_t seq_first = bam ? r.seq_from / 2 : r.seq_from;
+    const uint64_t seq_bytes = !bam ? r.n_seq : r.n_seq ? ((uint64_t)r.seq_from + r.n_seq + 1) / 2 - seq_first : 0;
+    const uint64_t size = 1 + (uint64_t)r.id_len + ((r.flags & GRP_FETCH_REC_TRIMMED) ? 9 : 11) + r.n_seq + 1 + (fastq ? 3 + (uint64_t)r.n_qual : 0);
+    const char* why = (r.flags & ~GRP_FETCH_REC_TRIMMED)                                        ? "an unknown flag"
+                      : !inside(r.id_off, r.id_len)                                               ? "its id does not lie inside the units' text"
+                      : r.seq_off > total || !inside(r.seq_off + seq_first, seq_bytes)            ? "its bases do not lie inside the units' text"
+                      : r.qual_off > total || !inside(r.qual_off + r.qual_from, r.n_qual)         ? "its qualities do not lie inside the units' text"
+                      : r.out_off > out_cap || size > out_cap - r.out_off                         ? "its output does not lie inside the caller's buffer"
+                                                                                                  : nullptr;
+    if (why) {
+      if (bad_record) {
+        *bad_record = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_records_fetch: record %u: %s (id [%llu, +%u), bases %llu + [%u, +%u), qualities %llu + [%u, +%u) of %llu bytes of text; output [%llu, +%llu) of %llu, flags %u)", i, why,
+                     (unsigned long long)r.id_off, r.id_len, (unsigned long long)r.seq_off, r.seq_from, r.n_seq, (unsigned long long)r.qual_off, r.qual_from, r.n_qual, (unsigned long long)total, (unsigned long long)r.out_off,
+                     (unsigned long long)size, (unsigned long long)out_cap, r.flags);
+    }
+    span[i] = { r.out_off, r.out_off + size };
+  }
+  std::vector<uint32_t> order(n_recs);
+  for (uint32_t i = 0; i < n_recs; ++i) {
+    order[i] = i;
+  }
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return span[a].first != span[b].first ? span[a].first < span[b].first : a < b; });
+  for (uint32_t k = 1; k < n_recs; ++k) {
+    if (span[order[k]].first < span[order[k - 1]].second) {
+      if (bad_record) {
+        *bad_record = order[k];
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_records_fetch: record %u: its output [%llu, %llu) overlaps that of record %u, [%llu, %llu)", order[k], (unsigned long long)span[order[k]].first, (unsigned long long)span[order[k]].second,
+                     order[k - 1], (unsigned long long)span[order[k - 1]].first, (unsigned long long)span[order[k - 1]].second);
+    }
+  }
+  if (n_recs == 0) {
+    return GRP_OK; // (nothing is asked for: nothing is inflated)
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (const int rc = inflate_entries(c, p, comp, n_comp, dict, n_dict, units, n_units, nullptr, 0, bad_unit, true)) {
+    return rc;
+  }
+  // the units' text is in p.d_text now, every unit with its CRC32
+  if (const int rc = bam ? ingest_phred_table(c, c->d_delog_raw, 0, "grp_records_fetch") : ingest_phred_table(c, c->d_delog, 33, "grp_records_fetch")) {
+    return rc;
+  }
+  hipStream_t st = c->stream2;
+  grp_ctx::FetchPool& f = c->fetch;
+  const uint64_t out_lo = span[order[0]].first & ~15ull; // (the device buffer begins at a 16-byte boundary of the caller's)
+  uint64_t out_hi = 0;
+  for (uint32_t i = 0; i < n_recs; ++i) {
+    out_hi = std::max(out_hi, span[i].second);
+  }
+  HIP_TRY(c, f.d_out.ensure(out_hi - out_lo));
+  HIP_TRY(c, f.d_recs.ensure(n_recs));
+  HIP_TRY(c, f.d_sums.ensure(n_recs));
+  HIP_TRY(c, hipMemcpyAsync(f.d_recs, recs, (size_t)n_recs * sizeof(grp_fetch_record), hipMemcpyHostToDevice, st));
+  k_emit_records<<<n_recs, EMIT_THREADS, 0, st>>>(p.d_text, f.d_recs, n_recs, out_flags, out_lo, f.d_out, bam ? c->d_delog_raw : c->d_delog, f.d_sums);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(sums, f.d_sums, (size_t)n_recs * sizeof(double), hipMemcpyDeviceToHost, st));
+  // the records alone come down: one copy per run of records that lie back to back (a caller that packs them: one copy)
+  for (uint32_t k = 0; k < n_recs;) {
+    const uint64_t b = span[order[k]].first;
+    uint64_t e = span[order[k]].second;
+    for (++k; k < n_recs && span[order[k]].first == e; ++k) {
+      e = span[order[k]].second;
+    }
+    HIP_TRY(c, hipMemcpyAsync(out + b, f.d_out + (b - out_lo), e - b, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return GRP_OK;
+}
+
+} // namespace
+
+extern "C" int
+grp_records_fetch(grp_ctx* c, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags, char* out,
+                  uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record)
+{
+  if (!c) {
+    return GRP_ERR_INVALID;
+  }
+  if (bad_unit) {
+    *bad_unit = UINT32_MAX;
+  }
+  if (bad_record) {
+    *bad_record = UINT32_MAX;
+  }
+  if (unit_kind == GRP_FETCH_UNITS_BGZF) {
+    return records_fetch(c, c->bgzf, comp, n_comp, nullptr, 0, static_cast<const grp_bgzf_block*>(units), n_units, recs, n_recs, out_flags, out, out_cap, sums, bad_unit, bad_record);
+  }
+  if (unit_kind == GRP_FETCH_UNITS_GZIP) {
+    return records_fetch(c, c->gzip, comp, n_comp, dict, n_dict, static_cast<const grp_gzip_segment*>(units), n_units, recs, n_recs, out_flags, out, out_cap, sums, bad_unit, bad_record);
+  }
+  return set_err(c, GRP_ERR_INVALID, "grp_records_fetch: unit_kind %d is neither GRP_FETCH_UNITS_BGZF nor GRP_FETCH_UNITS_GZIP", unit_kind);
 }
 
 extern "C" int

@@ -322,6 +322,13 @@ struct grp_ctx : CtxStreams
   };
   InflatePool<grp_bgzf_block> bgzf;
   InflatePool<grp_gzip_segment> gzip;
+  // grp_records_fetch: the record table, the formatted records and their Phred sums of one call; grown, never shrunk
+  struct FetchPool
+  {
+    DevBuf<grp_fetch_record> d_recs;
+    DevBuf<uint8_t> d_out;
+    DevBuf<double> d_sums;
+  } fetch;
   DevBuf<uint32_t> d_crc_tab; // CRC32 slicing tables and x^(2^k), of both (inflate_crc_tables)
   const char* reg_text = nullptr; // the caller's text buffer, page-locked by grp_fastq_pin
   size_t reg_bytes = 0;

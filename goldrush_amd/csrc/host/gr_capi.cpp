@@ -258,6 +258,14 @@ gr_classifier_set_debug(gr_classifier* c, gr_debug_fn fn)
 }
 
 void
+gr_classifier_set_settle(gr_classifier* c, gr_settle_fn fn, void* user)
+{
+  if (c) {
+    c->impl.set_settle(fn, user);
+  }
+}
+
+void
 gr_classifier_set_allgather(gr_classifier* c, gr_allgather_fn allgather, void* allgather_user)
 {
   if (c) {

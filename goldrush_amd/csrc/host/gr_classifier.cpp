@@ -101,6 +101,31 @@ Classifier::emit_commit(const gr_commit& ev)
   return commit_cb_ ? commit_cb_(user_, &ev) : 0.0;
 }
 
+void
+Classifier::add_phred(double ph)
+{
+  if (settle_cb_) {
+    ++unsettled_; // (what the commit callback returned is not looked at)
+  } else {
+    phred_sum_in_path_ += ph;
+  }
+}
+
+// the sums of the insert commits since the last call, from the host, added left to right as add_phred would have
+void
+Classifier::settle()
+{
+  if (!settle_cb_ || unsettled_ == 0) {
+    return;
+  }
+  settle_sums_.assign(unsettled_, 0.0);
+  settle_cb_(settle_user_, settle_sums_.data(), unsettled_);
+  for (const double ph : settle_sums_) {
+    phred_sum_in_path_ += ph;
+  }
+  unsettled_ = 0;
+}
+
 int
 Classifier::engine_failed(const char* what, int rc)
 {
@@ -485,6 +510,7 @@ Classifier::silver_path_check(int& rc)
 {
   // goldrush_path.cpp:156-187
   if (p_.target_bases < inserted_bases_) {
+    settle(); // (in front of the log, the callback and the path's zeroed sum; the run may finish here)
     if (p_.verbose && p_.rank == 0) {
       log_path_stat();
     }
@@ -607,7 +633,7 @@ Classifier::commit(void* reads, const uint32_t* lens, uint32_t r, const gr_read_
       const double ph = emit_commit(ev);
       inserted_bases_ += len;
       ++num_reads_in_path_;
-      phred_sum_in_path_ += ph;
+      add_phred(ph);
       if (p_.silver_path) {
         silver_path_check(rc);
       }
@@ -650,7 +676,7 @@ Classifier::commit(void* reads, const uint32_t* lens, uint32_t r, const gr_read_
       inserted_bases_ += n_out;
       const double ph = emit_commit(ev);
       ++num_reads_in_path_;
-      phred_sum_in_path_ += ph;
+      add_phred(ph);
       if (p_.silver_path) {
         silver_path_check(rc);
       }
@@ -817,6 +843,7 @@ Classifier::run(void* reads, const uint32_t* lens, uint32_t first, uint32_t n, c
   if (!finished_) {
     skip_reads(skipped_after);
   }
+  settle();
   finished = finished_;
   return GRP_OK;
 }

@@ -37,6 +37,14 @@ public:
   void set_callbacks(gr_commit_fn commit, gr_rollover_fn rollover, gr_allgather_fn allgather, void* user);
   void set_allgather(gr_allgather_fn allgather, void* allgather_user);
   void set_debug(gr_debug_fn fn) { debug_cb_ = fn; }
+  // The Phred sums of the insert commits come later, through `fn`, instead of from the commit callback (a host that writes
+  // its records in batches knows them only then): asked for where the sum is looked at or zeroed — in front of a rollover's
+  // log and callback, where the run finishes, at the end of run() — and added in commit order, the same additions
+  void set_settle(gr_settle_fn fn, void* user)
+  {
+    settle_cb_ = fn;
+    settle_user_ = user;
+  }
   // commits of the reads [first0, first0 + count0) and [first1, first1 + count1) (numbers in the batch of reads) are kept
   void keep_commits(uint32_t first0, uint32_t count0, uint32_t first1, uint32_t count1);
   const std::vector<gr_commit>& kept_commits() const { return kept_; }
@@ -67,6 +75,8 @@ private:
   void skip_reads(uint32_t n);
   void bump_id();
   double emit_commit(const gr_commit& ev);
+  void add_phred(double ph); // an insert commit's sum: added now, or counted for settle()
+  void settle();
   int engine_failed(const char* what, int rc); // err_ = "<what>: <the engine's last error>"; returns rc
   struct Plan
   {
@@ -156,6 +166,10 @@ private:
   void* user_ = nullptr;
   void* ag_user_ = nullptr;
   gr_debug_fn debug_cb_ = nullptr;
+  gr_settle_fn settle_cb_ = nullptr;
+  void* settle_user_ = nullptr;
+  uint32_t unsettled_ = 0; // insert commits since the last settle()
+  std::vector<double> settle_sums_;
   std::vector<std::string> debug_text_; // --debug: the tile-state dumps of the window's reads
   uint32_t debug_window_pos_ = 0;       // ... and the window's first read
 

@@ -107,5 +107,9 @@ main(int argc, char** argv)
   ext.bam_parse = [](void* c, const char* bytes, uint64_t n, int fin, void** out, uint64_t* nrec, uint64_t* used, uint64_t* bad) {
     return grp_bam_parse(static_cast<grp_ctx*>(c), bytes, n, fin, reinterpret_cast<grp_fastq**>(out), nrec, used, bad);
   };
+  ext.records_fetch = [](void* c, int kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t flags, char* out,
+                         uint64_t cap, double* sums, uint32_t* bad_unit, uint32_t* bad_rec) {
+    return grp_records_fetch(static_cast<grp_ctx*>(c), kind, comp, n_comp, dict, n_dict, units, n_units, recs, n_recs, flags, out, cap, sums, bad_unit, bad_rec);
+  };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <deque>
 #include <cstddef>
 #include <cstring>
 #include <fstream>
@@ -192,7 +193,8 @@ calc_min_phred_threshold(PathRun& run)
 // the classification pass runs over those batches; the text of a read that is written out
 // (an inserted read) is fetched from the input file by offset.  Plain, seekable input without
 // a -f list only (gzip / pipes / --debug take the two-pass form); GRP_RESIDENT=off switches it
-// off, GRP_RESIDENT_MAX_GB caps the packed bytes kept (default 100).
+// off, GRP_RESIDENT_MAX_GB caps the packed bytes kept (default 100).  GRP_RESIDENT=all: BGZF, indexed gzip and BAM inputs
+// stay too, their written records are fetched through the units that hold them (below: Deferred).
 struct RecLoc
 {
   uint32_t file;    // which of the run's files
@@ -210,7 +212,9 @@ struct ResidentBatch
   std::vector<uint32_t> lens, skipped_before;
   uint32_t skipped_after = 0;
   std::vector<RecLoc> loc;
-  std::vector<uint64_t> name_hash; // FNV-1a of the id: candidates for filter_out_reads (names are compared through the file)
+  std::vector<uint64_t> name_hash; // FNV-1a of the id: candidates for filter_out_reads (names are compared through the file ...
+  std::string ids;                 // ... or, the records of a compressed file, here: their ids one after the other,
+  std::vector<uint64_t> id_at;     //     read i's at ids[id_at[i]], loc[i].id_len long)
 };
 
 uint64_t
@@ -228,6 +232,21 @@ struct Resident
   bool on = false;
   uint64_t packed_bytes = 0, max_bytes = 0;
   std::vector<ResidentBatch> batches;
+  // GRP_RESIDENT=all: files that are not plain may stay too.  Per file: how its records are read back — PLAIN by pread;
+  // the members of a BGZF file or the segments of a gzip file's index through the fetch (UNKNOWN until the fill pass has
+  // read the file to its end: resolve_units) — and whether its text is BAM records
+  bool all = false;
+  enum Kind : uint8_t { PLAIN = 0, BGZF = 1, GZIP = 2, UNKNOWN = 3 };
+  std::vector<uint8_t> kind, bam;
+  std::vector<std::vector<uint64_t>> gz_text_off; // a GZIP file: the running text offset of its index's segments (n + 1)
+  bool any_compressed() const { return std::any_of(kind.begin(), kind.end(), [](uint8_t k) { return k != PLAIN; }); }
+  // ... and gave up (the run goes on in the two-pass form): the line that says why
+  void say_dropped(const PathRun& run, const std::string& why, const std::string& file = std::string()) const
+  {
+    if (all && run.rank == 0) {
+      std::cerr << "GRP_RESIDENT=all: the reads are not kept on the device" << (file.empty() ? "" : " (" + file + ")") << ": " << why << std::endl;
+    }
+  }
   // The files the records are read back from: at most kMaxOpen descriptors at once, the others opened when a record of
   // theirs is asked for (the one used longest ago makes room).
   static constexpr size_t kMaxOpen = 64;
@@ -282,6 +301,37 @@ struct Resident
   }
 };
 
+struct SinkState;
+
+// The insert commits of a resident run with compressed inputs, written in batches (below: "the written records of
+// compressed inputs")
+struct Deferred
+{
+  struct Pending
+  {
+    RecLoc loc;
+    uint32_t kind, trim_start, trim_end, num_tiles;
+  };
+  static constexpr uint64_t kTextCap = 64ull << 20; // text of the units of one fetch call (a file with a larger unit is not resident)
+  static constexpr size_t kMaxUnits = size_t(1) << 20;
+  std::vector<Pending> pend; // in commit order
+  std::deque<double> sums;   // of the records written, not yet asked for by the settle hook
+  void flush(SinkState& st);
+  bool fetch_some(SinkState& st, size_t& i, size_t e);
+  // GRP_TRACE_INGEST
+  uint64_t n_flushes = 0, n_units_inflated = 0, n_text_bytes = 0, n_records = 0, n_trimmed = 0, n_straddling = 0, n_out_bytes = 0;
+
+private:
+  std::vector<FetchItem> items;
+  FetchPlan plan;
+  std::vector<uint8_t> comp, dict;
+  std::vector<grp_bgzf_block> blocks;
+  std::vector<grp_gzip_segment> segs;
+  std::vector<grp_fetch_record> recs;
+  std::vector<char> out, text;
+  std::vector<double> got_sums;
+};
+
 // plain regular file (no gzip magic) whose records can be read back with pread?  `may_be_empty`: one of several files
 // may hold no byte (no record is ever read back from it).
 bool
@@ -299,6 +349,74 @@ is_plain_input(const std::string& path, bool may_be_empty)
   }
   close(fd);
   return plain;
+}
+
+// GRP_RESIDENT=all, a file that is not plain: could its records be fetched through inflatable units?  A regular file of
+// gzip members (BGZF among them); whether its units are known is seen behind the fill pass (resolve_units).  Else why not.
+bool
+compressed_candidate(const std::string& path, std::string& why)
+{
+  const int fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  if (fd < 0) {
+    why = "it cannot be opened";
+    return false;
+  }
+  struct stat st;
+  unsigned char magic[4] = { 0, 0, 0, 0 };
+  const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+  const ssize_t k = regular ? pread(fd, magic, 4, 0) : 0;
+  close(fd);
+  if (!regular) {
+    why = "it is no regular file";
+  } else if (k == 4 && !memcmp(magic, "BAM\1", 4)) {
+    why = "it is an uncompressed BAM file";
+  } else if (!(k >= 2 && magic[0] == 0x1f && magic[1] == 0x8b)) {
+    why = "it is neither plain FASTQ nor gzip data";
+  }
+  return why.empty();
+}
+
+// Behind the fill pass: the units of every compressed file, as the pass left them in the run.  false (the reads are
+// dropped, the run goes on in two passes): a file without them — a BGZF file that fell over to zlib at a member that is
+// not BGZF, a gzip file whose index was not built, was dropped or is not complete — or with a unit larger than a fetch takes,
+// or an engine without the entry point that inflates them.
+bool
+resolve_units(PathRun& run, Resident& res)
+{
+  res.gz_text_off.assign(run.files.size(), std::vector<uint64_t>());
+  for (size_t f = 0; f < run.files.size(); ++f) {
+    if (res.kind[f] != Resident::UNKNOWN) {
+      continue;
+    }
+    std::string why;
+    if (run.bgzf_map[f]) {
+      res.kind[f] = Resident::BGZF;
+      if (!run.ext.records_fetch && !run.ext.bgzf_inflate) {
+        why = "the engine cannot inflate BGZF members";
+      }
+    } else if (run.gzidx[f] && run.gzidx[f]->matches(run.files[f])) {
+      res.kind[f] = Resident::GZIP;
+      const GzIndex& ix = *run.gzidx[f];
+      std::vector<uint64_t>& toff = res.gz_text_off[f];
+      toff.assign(1, 0);
+      for (const GzSegment& g : ix.segs) {
+        toff.push_back(toff.back() + g.text_len);
+      }
+      if (!run.ext.records_fetch && !run.ext.gzip_inflate) {
+        why = "the engine cannot inflate gzip segments";
+      } else if (ix.max_text > Deferred::kTextCap) {
+        why = "a segment of its index holds more text (" + std::to_string(ix.max_text) + " bytes) than a fetch takes";
+      }
+    } else {
+      why = "the fill pass left neither a table of its BGZF members (a member that is not BGZF hands the file to zlib) nor a complete gzip index (GRP_GZIP_INDEX=off, dropped at GRP_GZIP_INDEX_MAX_GB, bytes behind the last member)";
+    }
+    if (!why.empty()) {
+      res.say_dropped(run, why, run.files[f]);
+      res.drop(run);
+      return false;
+    }
+  }
+  return true;
 }
 
 int
@@ -366,6 +484,12 @@ fill_bit_vector(PathRun& run, Resident& res)
         keep.skipped_before.push_back(skipped - 1);
         keep.loc.push_back(RecLoc{ (uint32_t)b.file, b.base_off + r.id_off, (uint32_t)r.id_len, (uint32_t)(r.seq_off - r.id_off), (uint32_t)r.seq_len, (uint64_t)(r.qual_off - r.id_off), (uint32_t)r.qual_len });
         keep.name_hash.push_back(fnv1a(b.text + r.id_off, r.id_len));
+        res.bam[b.file] = b.bam ? 1 : 0;
+        if (res.kind[b.file] != Resident::PLAIN) { // (no pread finds this id again)
+          keep.id_at.resize(keep.loc.size(), 0);
+          keep.id_at.back() = keep.ids.size();
+          keep.ids.append(b.text + r.id_off, r.id_len);
+        }
       }
       skipped = 0;
     }
@@ -400,6 +524,7 @@ fill_bit_vector(PathRun& run, Resident& res)
           res.packed_bytes += ((uint64_t)l + 15) / 16 * 4;
         }
         if (res.packed_bytes > res.max_bytes) {
+          res.say_dropped(run, "the packed reads exceed GRP_RESIDENT_MAX_GB", run.files[b.file]);
           res.drop(run); // too much to keep: the classification pass parses the input again
           prev = h;
         } else {
@@ -474,6 +599,7 @@ struct SinkState
   // reads kept on the device: the record's text comes from the input file
   const ResidentBatch* resident = nullptr;
   Resident* res = nullptr;
+  Deferred* deferred = nullptr; // the resident run has compressed inputs: the commits are written in batches
   std::vector<char> text;
   std::string upper;
   std::string bam_seq, bam_qual; // a BAM record's written slice as text
@@ -510,57 +636,41 @@ debug_sink(void* user, uint32_t read)
   std::cerr << "num tiles: " << b.rec[i].seq_len / st.run->opt.tile_length << std::endl;
 }
 
-double
-commit_sink(void* user, const gr_commit* c)
+// The slice of a committed read that is written (goldrush_path.cpp:996-1002, 1055-1070): bases [off, off + n_seq), qualities
+// [qoff, qoff + n_qual); a read inserted whole is written whole
+struct WrittenSlice
 {
-  SinkState& st = *static_cast<SinkState*>(user);
+  size_t off, n_seq, qoff, n_qual;
+  bool trimmed;
+};
+
+WrittenSlice
+written_slice(const Opts& opt, size_t seq_len, size_t qual_len, uint32_t kind, uint32_t trim_start, uint32_t trim_end, uint32_t num_tiles)
+{
+  WrittenSlice w{ 0, seq_len, 0, qual_len, kind == DEC_INSERT_TRIMMED };
+  if (w.trimmed) {
+    const size_t tile = opt.tile_length;
+    w.off = (size_t)trim_start * tile;
+    const size_t end_pos = (trim_end == num_tiles - 1) ? std::string::npos : (size_t)(trim_end - trim_start + 1) * tile;
+    w.n_seq = std::min(end_pos, seq_len - w.off);
+    w.n_qual = (w.off <= qual_len) ? std::min(end_pos, qual_len - w.off) : 0;
+  }
+  w.qoff = std::min(w.off, qual_len);
+  return w;
+}
+
+// One committed read, whose text is in `b`, to the output file; returns sum_phred of the qualities it wrote
+double
+write_record(SinkState& st, const Batch& b, const Rec& r, uint32_t kind, uint32_t trim_start, uint32_t trim_end, uint32_t num_tiles)
+{
   PathRun& run = *st.run;
-  if (c->dec.kind != DEC_INSERT_WHOLE && c->dec.kind != DEC_INSERT_TRIMMED) {
-    return 0.0;
-  }
-  if (input_failed()) {
-    return 0.0;
-  }
-  Batch fetched; // resident mode: one record read back from the file
-  Rec fetched_rec{};
-  if (st.resident) {
-    const RecLoc& l = st.resident->loc[c->read];
-    const size_t n = (size_t)l.qual_rel + l.qual_len;
-    st.text.resize(n);
-    size_t got = 0;
-    const int fd = st.res->fd_of(run, l.file);
-    while (got < n) {
-      const ssize_t k = fd < 0 ? -1 : pread(fd, st.text.data() + got, n - got, (off_t)(l.off + got));
-      if (k <= 0) {
-        // not exit(1) from inside the commit callback (a streaming window may be parked on this thread's word,
-        // ADVICE r03): the failure is noted, this and the later records are not written, and the program ends with
-        // an error behind the pass
-        note_input_failure("cannot read the record at byte " + std::to_string(l.off) + " back from " + run.files[l.file]);
-        return 0.0;
-      }
-      got += (size_t)k;
-    }
-    fetched.text = st.text.data();
-    fetched.seq_is_upper = false;
-    fetched_rec = Rec{ 0, l.id_len, l.seq_rel, l.seq_len, (size_t)l.qual_rel, l.qual_len };
-  }
-  const Batch& b = st.resident ? fetched : *st.batch;
-  const Rec& r = st.resident ? fetched_rec : b.rec[(*st.sel)[c->read]];
   const char first = run.opt.silver_path ? '@' : '>';
-  size_t off = 0, n_seq = r.seq_len, n_qual = r.qual_len;
-  const char* suffix = "_untrimmed\n";
-  if (c->dec.kind == DEC_INSERT_TRIMMED) {
-    suffix = "_trimmed\n";
-    const size_t tile = run.opt.tile_length;
-    off = (size_t)c->dec.trim_start * tile;
-    const size_t end_pos = (c->dec.trim_end == c->dec.num_tiles - 1) ? std::string::npos : (size_t)(c->dec.trim_end - c->dec.trim_start + 1) * tile;
-    n_seq = std::min(end_pos, r.seq_len - off);
-    n_qual = (off <= r.qual_len) ? std::min(end_pos, r.qual_len - off) : 0;
-  }
-  const size_t qoff = std::min(off, r.qual_len);
+  const WrittenSlice w = written_slice(run.opt, r.seq_len, r.qual_len, kind, trim_start, trim_end, num_tiles);
+  const char* suffix = w.trimmed ? "_trimmed\n" : "_untrimmed\n";
+  const size_t n_seq = w.n_seq, n_qual = w.n_qual;
   // the written slice (a BAM batch: it alone is decoded — bases through the code table, qualities + 33)
-  const char* seq = b.seq_text(r, off, n_seq, st.bam_seq);
-  const char* qual = b.qual_text(r, qoff, n_qual, st.bam_qual);
+  const char* seq = b.seq_text(r, w.off, n_seq, st.bam_seq);
+  const char* qual = b.qual_text(r, w.qoff, n_qual, st.bam_qual);
   std::ofstream& o = run.out;
   o.put(first);
   o.write(b.text + r.id_off, (std::streamsize)r.id_len);
@@ -586,11 +696,240 @@ commit_sink(void* user, const gr_commit* c)
   return sum_phred(qual, n_qual);
 }
 
+// resident mode, a plain file: one record read back from the file and written
+double
+write_plain_record(SinkState& st, const RecLoc& l, uint32_t kind, uint32_t trim_start, uint32_t trim_end, uint32_t num_tiles)
+{
+  PathRun& run = *st.run;
+  const size_t n = (size_t)l.qual_rel + l.qual_len;
+  st.text.resize(n);
+  size_t got = 0;
+  const int fd = st.res->fd_of(run, l.file);
+  while (got < n) {
+    const ssize_t k = fd < 0 ? -1 : pread(fd, st.text.data() + got, n - got, (off_t)(l.off + got));
+    if (k <= 0) {
+      // not exit(1) from inside the commit callback (a streaming window may be parked on this thread's word,
+      // ADVICE r03): the failure is noted, this and the later records are not written, and the program ends with
+      // an error behind the pass
+      note_input_failure("cannot read the record at byte " + std::to_string(l.off) + " back from " + run.files[l.file]);
+      return 0.0;
+    }
+    got += (size_t)k;
+  }
+  Batch fetched;
+  fetched.text = st.text.data();
+  fetched.seq_is_upper = false;
+  const Rec rec{ 0, l.id_len, l.seq_rel, l.seq_len, (size_t)l.qual_rel, l.qual_len };
+  return write_record(st, fetched, rec, kind, trim_start, trim_end, num_tiles);
+}
+
+// ---- the written records of compressed inputs, fetched in batches (GRP_RESIDENT=all) ------------------------------------
+// A record of a plain file is read back with one pread.  The text of a BGZF / gzip / BAM input exists only behind an
+// inflate, and one record at a time through zlib is out of the question, so the commits are only written down and the
+// records of many of them are fetched together: the units that hold them (gr_units.hpp) are read from the file, and the
+// engine inflates them and hands back the formatted records with their Phred sums (grp_records_fetch; without that entry
+// point the host inflates the units through bgzf_inflate / gzip_inflate and formats with write_record).
+//
+// WHERE a flush runs is the one constraint: it launches kernels and waits for them, and a streaming window that is parked
+// on this thread's word holds the device with its persistent launch.  A flush therefore runs from the classifier's settle
+// hook and from the rollover callback alone — the top of a rolling-over silver_path_check, where the committing read has
+// ended the streaming launches in front of its insert (gr_classifier.cpp: `rolls_over` means stream_abort on both; a
+// window of several ranks and one that is not resumable were aborted in front of the commit; batch and pipelined windows
+// are ordinary launches that end by themselves), and the end of Classifier::run, behind drop_streams — never from
+// commit_sink, a timer or the size of the list.  One run is one ingest chunk, which bounds the list.  The rollover
+// callback follows the settle hook at once, so the list is empty when the output file changes: it holds no path
+// boundaries.  Ranks other than 0 write nothing: they queue nothing and have no hook.
+void
+Deferred::flush(SinkState& st)
+{
+  Resident& res = *st.res;
+  if (pend.empty()) {
+    return;
+  }
+  ++n_flushes;
+  const size_t want = sums.size() + pend.size(); // one sum per record of the list, written or not
+  size_t i = 0;
+  while (i < pend.size() && !input_failed()) {
+    const uint32_t f = pend[i].loc.file;
+    size_t e = i + 1;
+    while (e < pend.size() && pend[e].loc.file == f) {
+      ++e;
+    }
+    if (res.kind[f] == Resident::PLAIN) {
+      for (; i < e && !input_failed(); ++i) {
+        sums.push_back(write_plain_record(st, pend[i].loc, pend[i].kind, pend[i].trim_start, pend[i].trim_end, pend[i].num_tiles));
+      }
+    } else {
+      while (i < e && fetch_some(st, i, e)) {
+      }
+      if (i < e) {
+        break; // (the failure is noted)
+      }
+    }
+  }
+  while (sums.size() < want) { // (an input failure: what was not written counts nothing)
+    sums.push_back(0.0);
+  }
+  pend.clear();
+}
+
+// one call of the fetch for records [i, e) of the list, all of one compressed file: as many as its buffers take; i moves
+// behind them.  false: a failure was noted.
+bool
+Deferred::fetch_some(SinkState& st, size_t& i, size_t e)
+{
+  PathRun& run = *st.run;
+  Resident& res = *st.res;
+  const uint32_t f = pend[i].loc.file;
+  const bool gz = res.kind[f] == Resident::GZIP, bam = res.bam[f] != 0, fastq = run.opt.silver_path;
+  const std::vector<uint64_t>& toff = gz ? res.gz_text_off[f] : run.bgzf_map[f]->text_off;
+  items.clear();
+  for (size_t j = i; j < e; ++j) {
+    items.push_back(FetchItem{ pend[j].loc.off, pend[j].loc.qual_rel + pend[j].loc.qual_len });
+  }
+  if (!plan_fetch(toff, items.data(), items.size(), kTextCap, kMaxUnits, plan)) {
+    note_input_failure("the record at byte " + std::to_string(pend[i].loc.off) + " of the text of " + run.files[f] + " does not lie inside the units the fill pass wrote down");
+    return false;
+  }
+  // the units' compressed bytes (and histories), one after the other
+  comp.clear();
+  dict.clear();
+  blocks.clear();
+  segs.clear();
+  const int fd = res.fd_of(run, f);
+  for (const size_t u : plan.units) {
+    uint64_t at, n;
+    if (gz) {
+      const GzSegment& g = run.gzidx[f]->segs[u];
+      at = g.first_byte();
+      n = g.end_byte() - at;
+      segs.push_back(grp_gzip_segment{ g.comp_bit - at * 8 + (uint64_t)comp.size() * 8, g.n_bits, (uint64_t)dict.size(), g.dict_len, g.text_len, g.crc32, g.flags });
+      dict.insert(dict.end(), run.gzidx[f]->dict(g), run.gzidx[f]->dict(g) + g.dict_len);
+      dict.resize((dict.size() + 3) & ~size_t(3));
+    } else {
+      const grp_bgzf_block& b = run.bgzf_map[f]->blocks[u];
+      at = b.comp_off;
+      n = b.comp_len;
+      blocks.push_back(grp_bgzf_block{ (uint64_t)comp.size(), b.comp_len, b.text_len, b.crc32, 0 });
+    }
+    const size_t have = comp.size();
+    comp.resize(have + (size_t)n);
+    size_t got = 0;
+    while (got < n) {
+      const ssize_t k = fd < 0 ? -1 : pread(fd, comp.data() + have + got, (size_t)n - got, (off_t)(at + got));
+      if (k <= 0) {
+        note_input_failure("cannot read the compressed bytes at byte " + std::to_string(at) + " back from " + run.files[f]);
+        return false;
+      }
+      got += (size_t)k;
+    }
+  }
+  const uint32_t n_units = (uint32_t)plan.units.size();
+  const void* units = gz ? static_cast<const void*>(segs.data()) : static_cast<const void*>(blocks.data());
+  const auto engine_says = [&](const char* what) {
+    note_input_failure(std::string("reading ") + run.files[f] + " failed: " + what + ": " + (run.vt.last_error ? run.vt.last_error(run.ctx) : "the engine refused"));
+    return false;
+  };
+  if (run.ext.records_fetch) {
+    recs.clear();
+    uint64_t out_n = 0;
+    for (size_t j = 0; j < plan.n_recs; ++j) {
+      const Pending& p = pend[i + j];
+      const RecLoc& l = p.loc;
+      const WrittenSlice w = written_slice(run.opt, l.seq_len, l.qual_len, p.kind, p.trim_start, p.trim_end, p.num_tiles);
+      const uint64_t t0 = plan.rec_text_off[j];
+      recs.push_back(grp_fetch_record{ t0, t0 + l.seq_rel, t0 + l.qual_rel, out_n, l.id_len, (uint32_t)w.off, (uint32_t)w.n_seq, (uint32_t)w.qoff, (uint32_t)w.n_qual, w.trimmed ? GRP_FETCH_REC_TRIMMED : 0u });
+      out_n += 1 + (uint64_t)l.id_len + (w.trimmed ? 9 : 11) + w.n_seq + 1 + (fastq ? 3 + (uint64_t)w.n_qual : 0);
+    }
+    out.resize((size_t)out_n);
+    got_sums.assign(plan.n_recs, 0.0);
+    uint32_t bad_unit = UINT32_MAX, bad_rec = UINT32_MAX;
+    if (run.ext.records_fetch(run.ctx, gz ? GRP_FETCH_UNITS_GZIP : GRP_FETCH_UNITS_BGZF, comp.data(), comp.size(), dict.data(), dict.size(), units, n_units, recs.data(), (uint32_t)recs.size(),
+                              (fastq ? GRP_FETCH_FASTQ : 0u) | (bam ? GRP_FETCH_BAM : 0u), out.data(), out.size(), got_sums.data(), &bad_unit, &bad_rec) != GRP_OK) {
+      return engine_says("the written records could not be fetched");
+    }
+    run.out.write(out.data(), (std::streamsize)out.size());
+    sums.insert(sums.end(), got_sums.begin(), got_sums.end());
+    n_out_bytes += out.size();
+  } else {
+    // the host's own fetch: the units' text through the inflate entry points, formatted by write_record
+    text.resize((size_t)plan.text_bytes + 8);
+    uint32_t bad = UINT32_MAX;
+    const int rc = gz ? run.ext.gzip_inflate(run.ctx, comp.data(), comp.size(), dict.data(), dict.size(), segs.data(), n_units, text.data(), plan.text_bytes, &bad)
+                      : run.ext.bgzf_inflate(run.ctx, comp.data(), comp.size(), blocks.data(), n_units, text.data(), plan.text_bytes, &bad);
+    if (rc != GRP_OK) {
+      return engine_says("the units of the written records could not be inflated");
+    }
+    Batch b;
+    b.text = text.data();
+    b.bam = bam;
+    const std::streampos before = run.out.tellp();
+    for (size_t j = 0; j < plan.n_recs; ++j) {
+      const Pending& p = pend[i + j];
+      const RecLoc& l = p.loc;
+      const size_t t0 = (size_t)plan.rec_text_off[j];
+      const Rec rec{ t0, l.id_len, t0 + l.seq_rel, l.seq_len, t0 + (size_t)l.qual_rel, l.qual_len };
+      sums.push_back(write_record(st, b, rec, p.kind, p.trim_start, p.trim_end, p.num_tiles));
+    }
+    n_out_bytes += (uint64_t)(run.out.tellp() - before);
+  }
+  n_units_inflated += n_units;
+  n_text_bytes += plan.text_bytes;
+  n_records += plan.n_recs;
+  n_straddling += plan.straddling;
+  for (size_t j = 0; j < plan.n_recs; ++j) {
+    n_trimmed += pend[i + j].kind == DEC_INSERT_TRIMMED ? 1 : 0;
+  }
+  i += plan.n_recs;
+  return true;
+}
+
+// the classifier's settle hook: the sums of the n insert commits since the last call, in commit order
+void
+settle_sink(void* user, double* out_sums, uint32_t n)
+{
+  SinkState& st = *static_cast<SinkState*>(user);
+  Deferred& d = *st.deferred;
+  d.flush(st);
+  for (uint32_t k = 0; k < n && !d.sums.empty(); ++k) {
+    out_sums[k] = d.sums.front();
+    d.sums.pop_front();
+  }
+}
+
+double
+commit_sink(void* user, const gr_commit* c)
+{
+  SinkState& st = *static_cast<SinkState*>(user);
+  if (c->dec.kind != DEC_INSERT_WHOLE && c->dec.kind != DEC_INSERT_TRIMMED) {
+    return 0.0;
+  }
+  if (input_failed()) {
+    return 0.0;
+  }
+  if (st.resident && st.deferred) {
+    // (ranks other than 0 write nothing and print nothing: nothing to fetch)
+    if (st.run->rank == 0) {
+      st.deferred->pend.push_back(Deferred::Pending{ st.resident->loc[c->read], c->dec.kind, c->dec.trim_start, c->dec.trim_end, c->dec.num_tiles });
+    }
+    return 0.0; // (the sum comes through the settle hook)
+  }
+  if (st.resident) {
+    return write_plain_record(st, st.resident->loc[c->read], c->dec.kind, c->dec.trim_start, c->dec.trim_end, c->dec.num_tiles);
+  }
+  const Batch& b = *st.batch;
+  return write_record(st, b, b.rec[(*st.sel)[c->read]], c->dec.kind, c->dec.trim_start, c->dec.trim_end, c->dec.num_tiles);
+}
+
 void
 rollover_sink(void* user, uint64_t new_path)
 {
   // golden_path_vec.pop_back(); emplace_back(ofstream(prefix + "_" + path + ".fq"))  (:182-184)
-  PathRun& run = *static_cast<SinkState*>(user)->run;
+  SinkState& st = *static_cast<SinkState*>(user);
+  PathRun& run = *st.run;
+  if (st.deferred) {
+    st.deferred->flush(st); // (the settle hook has run in front of this callback: nothing is left — the records of a path go to its file)
+  }
   run.out.close();
   run.out.open(run.rank == 0 ? run.opt.prefix_file + "_" + std::to_string(new_path) + ".fq" : std::string("/dev/null"));
 }
@@ -618,6 +957,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   }
   if (ext && ext->struct_size >= offsetof(grp_engine_ext, bam_parse) + sizeof(ext->bam_parse)) {
     run.ext.bam_parse = ext->bam_parse;
+  }
+  if (ext && ext->struct_size >= offsetof(grp_engine_ext, records_fetch) + sizeof(ext->records_fetch)) {
+    run.ext.records_fetch = ext->records_fetch;
   }
   Opts& opt = run.opt;
   // Several GPUs of one node: one process per GPU (GRP_WORLD / GRP_RANK, or the launcher's
@@ -681,6 +1023,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
       run.files.push_back(opt.input);
     }
     run.gzidx.resize(run.files.size());
+    run.bgzf_map.resize(run.files.size());
   }
   struct ShmGuard
   {
@@ -841,14 +1184,30 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   {
     const char* e = getenv("GRP_RESIDENT");
     const bool gpu_ingest = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
+    res.all = e && !strcmp(e, "all");
+    res.kind.assign(run.files.size(), Resident::PLAIN);
+    res.bam.assign(run.files.size(), 0);
     if (!(e && !strcmp(e, "off")) && gpu_ingest && !opt.debug) {
-      // (every input a plain seekable file — else the whole run takes the two-pass form)
+      // (every input a plain seekable file — else the whole run takes the two-pass form; GRP_RESIDENT=all: or a file of
+      // gzip members, whose records can be fetched through its BGZF members or the segments of its gzip index)
       res.on = true;
-      for (const std::string& path : run.files) {
-        res.on = res.on && is_plain_input(path, run.files.size() > 1);
+      for (size_t f = 0; f < run.files.size() && res.on; ++f) {
+        const std::string& path = run.files[f];
+        if (is_plain_input(path, run.files.size() > 1)) {
+          continue;
+        }
+        std::string why;
+        if (res.all && compressed_candidate(path, why)) {
+          res.kind[f] = Resident::UNKNOWN;
+        } else {
+          res.on = false;
+          res.say_dropped(run, why, path);
+        }
       }
       const char* cap = getenv("GRP_RESIDENT_MAX_GB");
       res.max_bytes = (uint64_t)((cap ? atof(cap) : 100.0) * (double)(1ull << 30));
+    } else {
+      res.say_dropped(run, opt.debug ? "--debug" : getenv("GRP_HOST_INGEST") ? "GRP_HOST_INGEST" : "the engine has no ingest entry points");
     }
   }
   ec = fill_bit_vector(run, res);
@@ -857,6 +1216,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   }
   if (input_error()) {
     return 1;
+  }
+  if (res.on && res.any_compressed()) {
+    (void)resolve_units(run, res); // (false: dropped, with its reason line)
   }
   uint64_t pop = 0;
   if (run.vt.finalize(run.ctx, &pop) != GRP_OK) {
@@ -905,9 +1267,23 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     cls.set_debug(debug_sink);
   }
 
+  Deferred deferred;
+  const auto trace_fetch = [&] {
+    if (getenv("GRP_TRACE_INGEST") && sink.deferred && run.rank == 0) {
+      std::cerr << "GRP_TRACE_INGEST resident fetch: " << deferred.n_flushes << " flushes, units inflated " << deferred.n_units_inflated << ", text bytes inflated " << deferred.n_text_bytes << ", records fetched "
+                << deferred.n_records << " (trimmed " << deferred.n_trimmed << ", in two or more units " << deferred.n_straddling << "), output bytes " << deferred.n_out_bytes
+                << (run.ext.records_fetch ? " (formatted on the device)" : " (inflated through the engine, formatted on the host)") << std::endl;
+    }
+  };
   if (res.on) {
     // the classification pass over the batches the fill pass left in HBM: no second parse
     sink.res = &res;
+    if (res.any_compressed()) {
+      sink.deferred = &deferred;
+      if (run.rank == 0) {
+        cls.set_settle(settle_sink, &sink);
+      }
+    }
     std::unordered_set<uint64_t> filtered_hash;
     for (const std::string& name : run.filter_out_reads) {
       filtered_hash.insert(fnv1a(name.data(), name.size()));
@@ -926,8 +1302,15 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
         for (uint32_t i = 0; i < n; ++i) {
           if (filtered_hash.count(rb.name_hash[i])) {
             name.resize(rb.loc[i].id_len);
-            const int fd = res.fd_of(run, rb.loc[i].file);
-            if (fd >= 0 && pread(fd, &name[0], name.size(), (off_t)rb.loc[i].off) == (ssize_t)name.size() && run.filter_out_reads.count(name)) {
+            bool have = false;
+            if (res.kind[rb.loc[i].file] != Resident::PLAIN) {
+              name.assign(rb.ids, (size_t)rb.id_at[i], rb.loc[i].id_len);
+              have = true;
+            } else {
+              const int fd = res.fd_of(run, rb.loc[i].file);
+              have = fd >= 0 && pread(fd, &name[0], name.size(), (off_t)rb.loc[i].off) == (ssize_t)name.size();
+            }
+            if (have && run.filter_out_reads.count(name)) {
               drop[i] = 1;
               any_drop = true;
             }
@@ -974,9 +1357,10 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
       }
     }
     sink.resident = nullptr;
+    trace_fetch();
     if (finished) {
       run.out.flush();
-      return 0; // exit(0) inside silver_path_check (:173-176)
+      return sink.deferred && input_error() ? 1 : 0; // exit(0) inside silver_path_check (:173-176); (a fetch that failed is an error)
     }
   } else {
     auto src = open_source(run);

@@ -258,6 +258,7 @@ public:
     , file_(file)
     , path_(run.files[file])
     , fd_(fd)
+    , map_(new BgzfMap)
   {}
   ~BgzfFeed() override { ::close(fd_); }
   static Sizes want(size_t chunk)
@@ -370,9 +371,17 @@ private:
           full = true;
         }
       }
+      for (size_t t = 0; map_ && t < nb; ++t) { // (comp_off: in the slot's bytes, which begin at off_ in the file)
+        map_->add(off_ + sl.blocks[t].comp_off, sl.blocks[t].comp_len, sl.blocks[t].text_len, sl.blocks[t].crc32);
+      }
       off_ += pos;
       sl.n_blocks = nb;
       sl.comp_n = pos;
+      if (other) {
+        map_.reset(); // (the rest of the file is zlib's: no random access into it)
+      } else if (eof && map_ && !input_failed()) {
+        run_.bgzf_map[file_] = std::move(map_); // (read behind this pass, like PathRun::gzidx)
+      }
       if (other) {
         // from this member on zlib reads, from a descriptor of its own that stands there
         const int fd = ::open(path_.c_str(), O_RDONLY | O_CLOEXEC);
@@ -402,6 +411,7 @@ private:
   size_t comp_cap_ = 0, tab_cap_ = 0;
   std::vector<Table> slot_;
   std::unique_ptr<TextFeed> tail_; // what follows the BGZF members, read as text
+  std::shared_ptr<BgzfMap> map_;   // the members walked so far; published in the run at the file's end
   uint64_t n_blocks_ = 0;
 };
 
@@ -592,6 +602,7 @@ std::unique_ptr<Feed>
 open_feed(PathRun& run, size_t file, const FilePlan& pl)
 {
   const std::string& path = run.files[file];
+  run.bgzf_map[file].reset(); // (the map of the pass before: this pass writes its own, or the file has none)
   if (pl.kind != FilePlan::TEXT) {
     const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
     if (fd >= 0) {
@@ -1076,6 +1087,7 @@ open_source(PathRun& run)
     run.files.push_back(run.opt.input);
   }
   run.gzidx.resize(run.files.size());
+  run.bgzf_map.resize(run.files.size());
   bool gpu = run.vt.fastq_parse && run.vt.fastq_records && run.vt.fastq_pack && run.vt.fastq_free && !getenv("GRP_HOST_INGEST");
   std::vector<int> format(run.files.size(), 0);
   for (size_t f = 0; gpu && f < run.files.size(); ++f) {

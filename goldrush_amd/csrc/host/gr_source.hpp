@@ -10,6 +10,7 @@
 #include "gr_bam.hpp"
 #include "gr_gzidx.hpp"
 #include "gr_opts.hpp"
+#include "gr_units.hpp"
 
 #include <cstddef>
 #include <cstdint>
@@ -46,6 +47,9 @@ struct PathRun
   // a plain gzip input: the restart points the first pass that read that file to its end wrote down (gr_gzidx.hpp); the
   // passes behind it inflate its segments on the device.  One per file, each built, dropped and used on its own
   std::vector<std::shared_ptr<GzIndex>> gzidx;
+  // a BGZF input: the members the last pass over that file walked, if it walked them to the file's end (BgzfFeed); a file
+  // whose last pass did not go through the member feed, or left it for zlib at a member that is not BGZF, has none
+  std::vector<std::shared_ptr<BgzfMap>> bgzf_map;
 
   int fail_engine(const char* what)
   {

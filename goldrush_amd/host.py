@@ -110,8 +110,12 @@ GZIP_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _v
 BAM_PARSE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 
+RECORDS_FETCH_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_double),
+                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+
+
 class grp_engine_ext(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN)]
+    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN), ("records_fetch", RECORDS_FETCH_FN)]
 
 
 class gr_bam_record(C.Structure):
@@ -122,6 +126,7 @@ class gr_bam_record(C.Structure):
 COMMIT_FN = C.CFUNCTYPE(C.c_double, _vp, C.POINTER(gr_commit))
 ROLLOVER_FN = C.CFUNCTYPE(None, _vp, C.c_uint64)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp)
+SETTLE_FN = C.CFUNCTYPE(None, _vp, C.POINTER(C.c_double), C.c_uint32)
 
 SIGNATURES = {
     "gr_make_seed_pattern": (C.c_int, [C.c_char_p, C.c_uint, C.c_uint, C.c_uint, _vp, C.c_size_t, C.c_int]),
@@ -144,6 +149,7 @@ SIGNATURES = {
     "gr_classifier_destroy": (None, [_vp]),
     "gr_classifier_set_allgather": (None, [_vp, _vp, _vp]),
     "gr_classifier_set_debug": (None, [_vp, _vp]),
+    "gr_classifier_set_settle": (None, [_vp, SETTLE_FN, _vp]),
     "gr_classifier_keep_commits": (None, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gr_classifier_kept_commits": (C.c_size_t, [_vp, _vp, C.c_size_t]),
     "gr_shm_allgather_open": (_vp, [C.c_uint32, C.c_uint32, C.c_char_p, C.c_double]),
@@ -358,6 +364,7 @@ def hip_engine_ext() -> grp_engine_ext:
     ext.bgzf_inflate = C.cast(lib.grp_bgzf_inflate, BGZF_INFLATE_FN)
     ext.gzip_inflate = C.cast(lib.grp_gzip_inflate, GZIP_INFLATE_FN)
     ext.bam_parse = C.cast(lib.grp_bam_parse, BAM_PARSE_FN)
+    ext.records_fetch = C.cast(lib.grp_records_fetch, RECORDS_FETCH_FN)
     return ext
 
 
@@ -378,8 +385,10 @@ class Classifier:
     """gr_classifier over an engine (HIP engine by default)."""
 
     def __init__(self, engine_handle, vt: grp_engine_vt, tile=1000, block=10, threshold=10, unassigned_min=5, assigned_max=1, k=22, h=3,
-                 target_bases=0, max_paths=1, silver_path=False, verbose=False, max_window=0, world=1, rank=0, allgather=None, record=True, span0=0):
+                 target_bases=0, max_paths=1, silver_path=False, verbose=False, max_window=0, world=1, rank=0, allgather=None, record=True, span0=0,
+                 commit_phred=None):
         # span0: the span of seed 0 (k - 1 for make_seed_pattern's seeds at odd k); 0 = k
+        # commit_phred: what the commit callback returns for a commit (its tuple -> float; default 0.0)
         self.lib = load()
         self.vt = vt
         p = gr_classifier_params(C.sizeof(gr_classifier_params), tile, block, threshold, unassigned_min, assigned_max, k, h, target_bases, max_paths,
@@ -396,7 +405,7 @@ class Classifier:
             c = c.contents
             d = c.dec
             self.commits.append((c.read, d.kind, d.num_tiles, d.num_assigned, d.trim_start, d.trim_end, c.first_id, c.path, d.hits, d.misses))
-            return 0.0
+            return float(commit_phred(self.commits[-1])) if commit_phred else 0.0
 
         def _roll(user, path):
             self.rollovers.append(path)
@@ -404,6 +413,16 @@ class Classifier:
         self._cb = (COMMIT_FN(_commit) if record else C.cast(None, COMMIT_FN), ROLLOVER_FN(_roll),
                     ALLGATHER_FN(allgather) if allgather else C.cast(None, ALLGATHER_FN))
         self.lib.gr_classifier_set_callbacks(self._h, self._cb[0], self._cb[1], self._cb[2], None)
+
+    def set_settle(self, fn):
+        """gr_classifier_set_settle: fn(n) -> the Phred sums of the n insert commits since the last call, oldest first (None: the
+        commit callback's return values count again)"""
+        def _settle(user, sums, n):
+            for i, v in enumerate(fn(n)):
+                sums[i] = v
+
+        self._settle_cb = SETTLE_FN(_settle) if fn else C.cast(None, SETTLE_FN)
+        self.lib.gr_classifier_set_settle(self._h, self._settle_cb, None)
 
     def run(self, reads_handle, lens, skipped_before=None, skipped_after=0):
         lens = np.ascontiguousarray(lens, dtype=np.uint32)

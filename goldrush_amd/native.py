@@ -133,6 +133,7 @@ SIGNATURES = {
     "grp_debug_bgzf_stats": (C.c_int, [_vp, _vp]),
     "grp_gzip_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
     "grp_debug_gzip_stats": (C.c_int, [_vp, _vp]),
+    "grp_records_fetch": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "grp_dev_hooks": (C.c_int, []),
     "grp_set_timing": (C.c_int, [_vp, C.c_int]),
     "grp_get_kernel_stats": (C.c_int, [_vp, C.POINTER(grp_kernel_stat)]),
@@ -162,6 +163,12 @@ fastq_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off
 bgzf_block_dtype = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 # grp_gzip_segment: a run of whole DEFLATE blocks out of a serial stream, from bit comp_bit on, with dict_len bytes of history
 gzip_segment_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_off", "<u8"), ("dict_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("flags", "<u4")])
+# grp_fetch_record: one record to format out of the units' text (offsets count in the concatenated text of the call's units)
+fetch_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("out_off", "<u8"), ("id_len", "<u4"), ("seq_from", "<u4"), ("n_seq", "<u4"),
+                              ("qual_from", "<u4"), ("n_qual", "<u4"), ("flags", "<u4")])
+FETCH_REC_TRIMMED = 1
+FETCH_UNITS_BGZF, FETCH_UNITS_GZIP = 0, 1
+FETCH_FASTQ, FETCH_BAM = 1, 2
 
 # include/grpath_ingest.h
 SIGNATURES.update({
@@ -450,6 +457,30 @@ class Engine:
             e.bad_seg = None if bad.value == 0xFFFFFFFF else bad.value
             raise e
         return out[:total].tobytes()
+
+    # -- records fetched out of members / segments and formatted on the device (include/grpath_ingest.h)
+    def records_fetch(self, unit_kind: int, comp, dict_bytes, units, recs, out_flags: int, out: np.ndarray, out_cap: "int | None" = None):
+        """grp_records_fetch: units = bgzf_block_dtype (FETCH_UNITS_BGZF) or gzip_segment_dtype (FETCH_UNITS_GZIP) records over
+        comp (and dict_bytes), recs = fetch_record_dtype records, out = a caller-owned uint8 array the records' bytes are
+        written into (out_cap: its capacity as the call is told, default out.size).  Returns the Phred sums (float64, one per
+        record).  A refusal raises GrpError with .bad_unit / .bad_record set (None where the call named none)."""
+        buf = np.frombuffer(comp, dtype=np.uint8) if len(comp) else np.zeros(1, dtype=np.uint8)
+        dic = np.frombuffer(dict_bytes, dtype=np.uint8) if len(dict_bytes) else np.zeros(1, dtype=np.uint8)
+        if not (isinstance(units, np.ndarray) and units.dtype in (bgzf_block_dtype, gzip_segment_dtype)):
+            units = np.array([tuple(u) for u in units], dtype=gzip_segment_dtype if unit_kind == FETCH_UNITS_GZIP else bgzf_block_dtype)
+        units = np.ascontiguousarray(units)
+        recs = np.ascontiguousarray(recs, dtype=fetch_record_dtype)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+        sums = np.zeros(max(len(recs), 1), dtype=np.float64)
+        bad_unit, bad_rec = C.c_uint32(0xFFFFFFFF), C.c_uint32(0xFFFFFFFF)
+        rc = self.lib.grp_records_fetch(self._h, unit_kind, _ptr(buf), len(comp), _ptr(dic), len(dict_bytes), _ptr(units) if len(units) else None, len(units), _ptr(recs) if len(recs) else None, len(recs),
+                                        out_flags, _ptr(out), out.size if out_cap is None else out_cap, _ptr(sums), C.byref(bad_unit), C.byref(bad_rec))
+        if rc != GRP_OK:
+            e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
+            e.bad_unit = None if bad_unit.value == 0xFFFFFFFF else bad_unit.value
+            e.bad_record = None if bad_rec.value == 0xFFFFFFFF else bad_rec.value
+            raise e
+        return sums[:len(recs)]
 
     def gzip_stats(self) -> dict:
         """segments, compressed bytes, text bytes and kernel microseconds of all gzip_inflate calls of this engine"""

@@ -214,6 +214,16 @@ void gr_classifier_set_callbacks(gr_classifier* c, gr_commit_fn commit, gr_rollo
  * the host prints what the reference prints there — the skipped records before it, "name:", "num tiles:" */
 typedef void (*gr_debug_fn)(void* user, uint32_t read);
 void gr_classifier_set_debug(gr_classifier* c, gr_debug_fn fn);
+/* The Phred sums of the insert commits handed over later than their commits (a host that writes its records in batches —
+ * fetched from a compressed input, say — knows them only once a batch is written).  With `fn` set the commit callback's
+ * return value is ignored; the classifier counts the insert commits (kinds 2 and 4: the reads that are written) and calls
+ * fn(user, sums, n) for the n of them since the last call, oldest first, wherever the path's sum is looked at or zeroed: at
+ * the top of a silver path's rollover (in front of its log line and the rollover callback; the run may finish there) and
+ * at the end of every gr_classifier_run[_range].  fn fills sums[0, n) (zeroed before the call); they are added left to
+ * right — the additions the undeferred form makes, in its order, so phred_sum_in_path and "Average Phred" are
+ * bit-identical to it.  fn == NULL: the commit callback's return value is added at the commit, as before. */
+typedef void (*gr_settle_fn)(void* user, double* sums, uint32_t n);
+void gr_classifier_set_settle(gr_classifier* c, gr_settle_fn fn, void* user);
 /* A witness of the decisions that costs nothing per read: the commits of the reads [first0, first0 + count0) and
  * [first1, first1 + count1) — numbers in the batch of reads handed to gr_classifier_run[_range] — are kept inside
  * the classifier (whether or not a commit callback is set) and handed out by gr_classifier_kept_commits (returns
@@ -329,6 +339,11 @@ typedef struct
    * through fastq_parse (the handle is served by the table's fastq_records / fastq_pack / fastq_free); without it a BAM
    * file takes the host reader */
   int (*bam_parse)(void* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, void** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
+  /* grp_records_fetch: with it (and GRP_RESIDENT=all), the written records of a compressed input whose reads stayed on the
+   * device are inflated, cut and formatted there; without it the host inflates their units through bgzf_inflate /
+   * gzip_inflate above and formats them itself */
+  int (*records_fetch)(void* ctx, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags,
+                       char* out, uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record);
 } grp_engine_ext;
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */

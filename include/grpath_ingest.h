@@ -168,6 +168,57 @@ int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
  */
 int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
 
+/*
+ * ---- records of a compressed input, fetched and formatted on the device ----------------------------------------------
+ * What the host program writes for an inserted read (goldrush_path.cpp:996-1002, 1055-1070) is
+ *     <'@' | '>'> id <"_untrimmed\n" | "_trimmed\n"> bases of the written slice '\n'   [ "+\n" qualities of the slice '\n' ]
+ * and the record's text is all it needs of the input.  For a compressed input that text lies inside a few inflatable units
+ * (BGZF members, or the segments of a plain gzip file's index): grp_records_fetch inflates those units into device memory
+ * and checks their CRC32 as grp_bgzf_inflate / grp_gzip_inflate do, leaves the text there, and emits only the records —
+ * formatted, with the Phred sum of each written quality slice — so that neither the text around them nor the records' own
+ * text is copied down and formatted by the host.
+ *
+ * All offsets of a record count in the CONCATENATED text of the call's units (unit i's text begins at the sum of the
+ * text_len in front of it); a record may straddle any number of units.
+ */
+struct grp_fetch_record
+{
+  uint64_t id_off;    /* the id: text[id_off, id_off + id_len) */
+  uint64_t seq_off;   /* the record's first base (BAM: the first byte of its 4-bit codes, high half first) */
+  uint64_t qual_off;  /* the record's first quality (FASTQ text: the character; BAM: the raw Phred byte) */
+  uint64_t out_off;   /* where the record's bytes go in `out` */
+  uint32_t id_len;
+  uint32_t seq_from;  /* the written slice: first base written, counted from seq_off in BASES ... */
+  uint32_t n_seq;     /* ... and how many */
+  uint32_t qual_from; /* first quality written, counted from qual_off ... */
+  uint32_t n_qual;    /* ... and how many (ignored for the output without GRP_FETCH_FASTQ; the sum covers them all the same) */
+  uint32_t flags;     /* GRP_FETCH_REC_TRIMMED: the id gets "_trimmed", else "_untrimmed" */
+}; /* (the typedef is in grpath.h) */
+#define GRP_FETCH_REC_TRIMMED 1u
+/* unit_kind: what `units` points at */
+#define GRP_FETCH_UNITS_BGZF 0 /* grp_bgzf_block[]; dict is not looked at */
+#define GRP_FETCH_UNITS_GZIP 1 /* grp_gzip_segment[] with their histories in dict */
+/* out_flags */
+#define GRP_FETCH_FASTQ 1u /* '@', and "+\n" with the quality line; without it '>' and no quality lines (FASTA) */
+#define GRP_FETCH_BAM 2u   /* the text is BAM: bases through =ACMGRSVTWYHKDBN from any base index, qualities + 33 */
+/*
+ * The bytes of record r go to out[out_off, out_off + size), size = 1 + id_len + (trimmed ? 9 : 11) + n_seq + 1, and with
+ * GRP_FETCH_FASTQ + 2 + n_qual + 1 more; no other byte of `out` is written.  FASTQ text: a-z of the bases folded to upper
+ * case, every other byte as it is.  sums[r] = the left-to-right double sum of 10^(-Q/10) over the written quality slice,
+ * with the table the ingest uses for the format: bit-identical to the host's gr_sum_phred of the written quality characters
+ * (computed without GRP_FETCH_FASTQ too).
+ * Synchronous, on the side stream, with the threading rules of grp_bgzf_inflate.  Both tables are checked before anything
+ * is launched: the units as grp_bgzf_inflate / grp_gzip_inflate check theirs (GRP_ERR_INVALID, *bad_unit = the entry); of a
+ * record the id, the bases' and the qualities' ranges inside the units' text, no flag but GRP_FETCH_REC_TRIMMED, its output
+ * range inside out_cap and disjoint from every other record's (GRP_ERR_INVALID, *bad_record = the entry; of two
+ * overlapping records the one that begins later).  A unit that is not a valid stream with its CRC32 is refused as by
+ * grp_bgzf_inflate (*bad_unit); `out` and `sums` are then untouched.  The call relies on no padding behind the text or
+ * behind `out`.  `out` is host memory (page-locked memory makes its copies DMA), `sums` has one double per record.
+ * At most 2^22 units and 2^22 records per call.
+ */
+int grp_records_fetch(grp_ctx* ctx, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags,
+                      char* out, uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record);
+
 #ifdef __cplusplus
 }
 #endif
