@@ -756,7 +756,11 @@ enum EmitMode
   EMIT_COPY = 0,   // ids, qualities of FASTQ text
   EMIT_UPPER = 1,  // bases of FASTQ text: a-z folded to upper case, as SeqReader folds what the reference later writes
   EMIT_PLUS33 = 2, // raw Phred bytes of a BAM record
-  EMIT_BAM_SEQ = 3 // 4-bit codes, high half first: src is the byte of base 0, `first` the first base written
+  EMIT_BAM_SEQ = 3, // 4-bit codes, high half first: src is the byte of base 0, `first` the first base written
+  // a reverse-strand BAM record (GRP_FETCH_REC_REVERSED), written last element first: `first` is the LAST element of the
+  // stored range, output byte j comes from element first - j
+  EMIT_BAM_SEQ_REV = 4, // ... the complement of the code: its bit reversal
+  EMIT_PLUS33_REV = 5   // ... raw Phred bytes: src is the record's first quality
 };
 
 template <int MODE>
@@ -769,6 +773,14 @@ emit_byte(const uint8_t* __restrict__ src, uint32_t first, uint32_t j)
     // "=ACMGRSVTWYHKDBN", eight characters to a word
     const uint64_t w = code < 8 ? 0x56535247'4d43413dull : 0x4e42444b'48595754ull;
     return (uint8_t)(w >> (8 * (code & 7u)));
+  } else if constexpr (MODE == EMIT_BAM_SEQ_REV) {
+    const uint32_t b = first - j;
+    const uint32_t code = (b & 1u) ? (src[b >> 1] & 15u) : (uint32_t)(src[b >> 1] >> 4);
+    // "=TGKCYSBAWRDMHVN": the character of the bit-reversed code
+    const uint64_t w = code < 8 ? 0x42535943'4b47543dull : 0x4e56484d'44525741ull;
+    return (uint8_t)(w >> (8 * (code & 7u)));
+  } else if constexpr (MODE == EMIT_PLUS33_REV) {
+    return (uint8_t)(src[first - j] + 33);
   } else {
     const uint8_t ch = src[j];
     if constexpr (MODE == EMIT_UPPER) {
@@ -807,7 +819,7 @@ emit_span(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t f
     dst[j] = emit_byte<MODE>(src, first, j);
   }
   uint4* d4 = reinterpret_cast<uint4*>(dst + head);
-  if (MODE != EMIT_BAM_SEQ && ((uintptr_t)(src + head) & 15u) == 0) {
+  if (MODE != EMIT_BAM_SEQ && MODE != EMIT_BAM_SEQ_REV && MODE != EMIT_PLUS33_REV && ((uintptr_t)(src + head) & 15u) == 0) {
     const uint4* s4 = reinterpret_cast<const uint4*>(src + head); // (words inside src[head, tail0))
     for (uint32_t i = tid; i < n16; i += EMIT_THREADS) {
       const uint4 v = s4[i];
@@ -839,6 +851,7 @@ k_emit_records(const uint8_t* __restrict__ text, const grp_fetch_record* __restr
   }
   const grp_fetch_record rec = recs[r];
   const bool fastq = (out_flags & GRP_FETCH_FASTQ) != 0, bam = (out_flags & GRP_FETCH_BAM) != 0, trimmed = (rec.flags & GRP_FETCH_REC_TRIMMED) != 0;
+  const bool reversed = bam && (rec.flags & GRP_FETCH_REC_REVERSED) != 0; // seq_from / qual_from name the stored range, written backwards
   const uint32_t tid = threadIdx.x;
   uint8_t* o = out + (rec.out_off - out_base);
   if (tid == 0) {
@@ -851,7 +864,9 @@ k_emit_records(const uint8_t* __restrict__ text, const grp_fetch_record* __restr
     o[1 + rec.id_len + tid] = (uint8_t)suffix[tid];
   }
   uint8_t* ob = o + 1 + rec.id_len + n_suffix;
-  if (bam) {
+  if (reversed) {
+    emit_span<EMIT_BAM_SEQ_REV>(ob, text + rec.seq_off, rec.seq_from + rec.n_seq - 1u, rec.n_seq); // (n_seq 0: nothing is read)
+  } else if (bam) {
     emit_span<EMIT_BAM_SEQ>(ob, text + rec.seq_off, rec.seq_from, rec.n_seq);
   } else {
     emit_span<EMIT_UPPER>(ob, text + rec.seq_off + rec.seq_from, 0, rec.n_seq);
@@ -867,7 +882,9 @@ k_emit_records(const uint8_t* __restrict__ text, const grp_fetch_record* __restr
       oq[1] = '\n';
       oq[2 + rec.n_qual] = '\n';
     }
-    if (bam) {
+    if (reversed) {
+      emit_span<EMIT_PLUS33_REV>(oq + 2, q, rec.n_qual - 1u, rec.n_qual);
+    } else if (bam) {
       emit_span<EMIT_PLUS33>(oq + 2, q, 0, rec.n_qual);
     } else {
       emit_span<EMIT_COPY>(oq + 2, q, 0, rec.n_qual);
@@ -881,7 +898,8 @@ k_emit_records(const uint8_t* __restrict__ text, const grp_fetch_record* __restr
     // a slice that begins 1 byte behind a 16-byte boundary; the emitted bytes, all vector loads, were right).
     uintptr_t qa = reinterpret_cast<uintptr_t>(q);
     asm volatile("" : "+v"(qa));
-    sums[r] = phred_chain(reinterpret_cast<const uint8_t*>(qa), 0, rec.n_qual, 0.0, delog);
+    // (a reversed record: the written line is the stored range read backwards, and so is its chain)
+    sums[r] = reversed ? phred_chain_back(reinterpret_cast<const uint8_t*>(qa), 0, rec.n_qual, 0.0, delog) : phred_chain(reinterpret_cast<const uint8_t*>(qa), 0, rec.n_qual, 0.0, delog);
   }
 }
 #endif
@@ -1163,7 +1181,7 @@ records_fetch(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp, u
     const uint64_t seq_first = bam ? r.seq_from / 2 : r.seq_from;
     const uint64_t seq_bytes = !bam ? r.n_seq : r.n_seq ? ((uint64_t)r.seq_from + r.n_seq + 1) / 2 - seq_first : 0;
     const uint64_t size = 1 + (uint64_t)r.id_len + ((r.flags & GRP_FETCH_REC_TRIMMED) ? 9 : 11) + r.n_seq + 1 + (fastq ? 3 + (uint64_t)r.n_qual : 0);
-    const char* why = (r.flags & ~GRP_FETCH_REC_TRIMMED)                                        ? "an unknown flag"
+    const char* why = (r.flags & ~(GRP_FETCH_REC_TRIMMED | (bam ? GRP_FETCH_REC_REVERSED : 0u)))  ? "an unknown flag"
                       : !inside(r.id_off, r.id_len)                                               ? "its id does not lie inside the units' text"
                       : r.seq_off > total || !inside(r.seq_off + seq_first, seq_bytes)            ? "its bases do not lie inside the units' text"
                       : r.qual_off > total || !inside(r.qual_off + r.qual_from, r.n_qual)         ? "its qualities do not lie inside the units' text"

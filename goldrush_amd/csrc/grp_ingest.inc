@@ -6,8 +6,9 @@
 //                               check (ballot)
 //   k_fq_phred                  one lane per record: left-to-right double Phred sums
 //   k_fq_pack                   2 bits per base for the selected records
-//   k_bam_records / k_bam_pack  the same table and the same packed words from unaligned BAM records
-//                               (grp_bam_parse: the record chain is walked on the host, host/gr_bam.hpp)
+//   k_bam_records / k_bam_pack  the same table and the same packed words from BAM records
+//                               (grp_bam_parse[_ex]: the record chain is walked on the host, host/gr_bam.hpp); a
+//                               reverse-strand record of an aligned file is summed and packed backwards
 
 #include "../../include/grpath_ingest.h"
 
@@ -243,6 +244,61 @@ phred_chain(const uint8_t* __restrict__ q, uint32_t from, uint32_t to, double to
   return total;
 }
 
+// The same chain from the other end: q[to - 1], q[to - 2] ... q[from], in that order — the left-to-right chain of a line
+// that is read backwards (a reverse-strand BAM record, GRP_FQ_REVERSED).  The same table, the same additions, the same
+// structure: single bytes down to a 16-byte boundary, lines of 64 bytes downwards with the line below requested ahead,
+// single bytes for what is left.  No load leaves q[from, to).
+__device__ inline double
+phred_chain_back(const uint8_t* __restrict__ q, uint32_t from, uint32_t to, double total, const double* sTab)
+{
+  uint32_t i = to; // what is left is q[from, i)
+  while (i > from && ((uintptr_t)(q + i) & 15u)) {
+    --i;
+    total += sTab[q[i]];
+  }
+  if (i - from >= 64) {
+    const uint4* p = reinterpret_cast<const uint4*>(q + i) - 4; // the line q[i - 64, i)
+    uint4 cur[4] = { p[0], p[1], p[2], p[3] };
+    for (;;) {
+      const bool more = i - from >= 128;
+      uint4 nxt[4];
+      if (more) {
+        nxt[0] = p[-4];
+        nxt[1] = p[-3];
+        nxt[2] = p[-2];
+        nxt[3] = p[-1];
+      }
+#pragma unroll
+      for (int v = 3; v >= 0; --v) {
+        const uint32_t w[4] = { cur[v].x, cur[v].y, cur[v].z, cur[v].w };
+#pragma unroll
+        for (int k = 3; k >= 0; --k) {
+#pragma unroll
+          for (int b = 3; b >= 0; --b) {
+            total += sTab[(w[k] >> (8 * b)) & 0xFFu];
+          }
+        }
+      }
+      i -= 64;
+      if (!more) {
+        break;
+      }
+      p -= 4;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        cur[v] = nxt[v];
+      }
+    }
+  }
+  while (i > from) {
+    --i;
+    total += sTab[q[i]];
+  }
+  return total;
+}
+
+// REV: records with GRP_FQ_REVERSED (k_bam_records, where flag 0x10 is accepted) get the sums of the line read backwards
+template <bool REV>
 __global__ void __launch_bounds__(64)
 k_fq_phred(const uint8_t* __restrict__ text, uint64_t n_records, const double* __restrict__ delog, grp_fastq_record* __restrict__ recs)
 {
@@ -258,7 +314,15 @@ k_fq_phred(const uint8_t* __restrict__ text, uint64_t n_records, const double* _
   const uint8_t* q = text + recs[r].qual_off;
   const uint32_t qn = recs[r].qual_len;
   double first = 0.0, total = 0.0;
-  if (qn >= 2) { // (the reference's n/2 - 1 wraps for n < 2: its "first" sum is never taken)
+  if (REV && (recs[r].flags & GRP_FQ_REVERSED)) {
+    // the twin's line is q read backwards: its first half (n/2 qualities) is the stored bytes qn-1 ... qn - qn/2
+    if (qn >= 2) {
+      first = phred_chain_back(q, qn - qn / 2, qn, 0.0, sTab);
+      total = phred_chain_back(q, 0, qn - qn / 2, first, sTab);
+    } else {
+      total = phred_chain_back(q, 0, qn, 0.0, sTab);
+    }
+  } else if (qn >= 2) { // (the reference's n/2 - 1 wraps for n < 2: its "first" sum is never taken)
     const uint32_t half = qn / 2 - 1;
     first = phred_chain(q, 0, half + 1, 0.0, sTab);
     total = phred_chain(q, half + 1, qn, first, sTab);
@@ -367,9 +431,10 @@ bam_scan_bad(const uint8_t* __restrict__ text, uint64_t s0, uint64_t e0, uint32_
 
 // one wave per record: the table entry from the fixed 32 bytes, the name's length, the ACGT test over the 4-bit codes and
 // the range test over the qualities.  rec_off[r] = the record's block_size field, counted from `text` like every offset
-// written here (the caller takes `lead` off).
+// written here (the caller takes `lead` off).  accept & 0x10: a reverse-strand record gets GRP_FQ_REVERSED (its offsets still
+// name the stored bytes; both tests below do not depend on the order).
 __global__ void __launch_bounds__(THREADS)
-k_bam_records(const uint8_t* __restrict__ text, const uint64_t* __restrict__ rec_off, uint64_t n_records, grp_fastq_record* __restrict__ out)
+k_bam_records(const uint8_t* __restrict__ text, const uint64_t* __restrict__ rec_off, uint64_t n_records, uint32_t accept, grp_fastq_record* __restrict__ out)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t r = (uint64_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
@@ -398,7 +463,7 @@ k_bam_records(const uint8_t* __restrict__ text, const uint64_t* __restrict__ rec
     }
   }
   grp_fastq_record rec;
-  rec.flags = 0;
+  rec.flags = (accept & f[14] & gr::BAM_FLAG_REVERSE) ? GRP_FQ_REVERSED : 0u;
   rec.id_off = name;
   rec.id_len = id_len;
   rec.seq_off = name + l_name + 4ull * n_cigar;
@@ -429,29 +494,42 @@ k_bam_records(const uint8_t* __restrict__ text, const uint64_t* __restrict__ rec
   }
 }
 
-// 16 bases of 4-bit codes (8 bytes, the first base in the high half of the first byte) as a word of grp_reads: 1, 2, 4, 8
-// -> 0, 1, 2, 3, base j at bits 2j
-__device__ inline uint32_t
-bam_pack16(uint64_t x)
-{
-  const uint64_t c = ((x >> 1) & 0x7777777777777777ull) - ((x >> 3) & 0x1111111111111111ull); // per code: 1, 2, 4, 8 -> 0, 1, 2, 3 (never a borrow: n >> 1 >= n >> 3)
-  uint64_t t = ((c >> 4) & 0x0303030303030303ull) | ((c & 0x0303030303030303ull) << 2);      // per byte: its two bases in the low four bits
-  t = (t | (t >> 4)) & 0x00FF00FF00FF00FFull;
-  t = (t | (t >> 8)) & 0x0000FFFF0000FFFFull;
-  return (uint32_t)(t | (t >> 16));
-}
+// (gr::bam_pack16 and the word functions of the reversed pack: host/gr_bam.hpp, where they compile for the host too)
+constexpr uint64_t BAM_PACK_REVERSED = 1ull << 63; // in a seq_off handed to k_bam_pack: the record is packed backwards (a chunk has < 2^36 bytes)
 
-// one workgroup per selected record (k_fq_pack's geometry); a word's 8 source bytes begin wherever the name left them
+// one workgroup per selected record (k_fq_pack's geometry); a word's 8 source bytes begin wherever the name left them.
+// A reversed record (BAM_PACK_REVERSED): word w holds the twin's bases 16w ... 16w + cnt - 1, which are the stored bases
+// n - 16w - cnt ... n - 16w - 1, last first and complemented — the 8 bytes that hold them (9 where the first of them is
+// the low half of its byte: the parity of n), packed as they stand and turned round as a word.  No load goes in front
+// of seq_off or behind the record's last code byte.
 __global__ void __launch_bounds__(THREADS)
 k_bam_pack(const uint8_t* __restrict__ text, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ len, const uint64_t* __restrict__ word_off, uint32_t* __restrict__ packed)
 {
   const uint32_t r = blockIdx.x;
-  const uint8_t* src = text + seq_off[r];
+  const bool reversed = (seq_off[r] & BAM_PACK_REVERSED) != 0;
+  const uint8_t* src = text + (seq_off[r] & ~BAM_PACK_REVERSED);
   const uint32_t n = len[r];
   const uint32_t nw = (n + 15u) / 16u;
   uint32_t* dst = packed + word_off[r];
   for (uint32_t w = threadIdx.x; w < nw; w += THREADS) {
     const uint32_t cnt = min(16u, n - w * 16u);
+    if (reversed) {
+      const uint32_t s0 = n - w * 16u - cnt; // the first stored base of the word (0 for the record's last word, where cnt < 16)
+      const uint8_t* s = src + (s0 >> 1);
+      uint64_t x = 0;
+      if (cnt == 16u) {
+        __builtin_memcpy(&x, s, 8);
+        if (s0 & 1u) {
+          x = gr::bam_shift_nibble(x, s[8]); // (base s0 + 15 is the high half of the ninth byte: inside the record)
+        }
+      } else {
+        for (uint32_t j = 0; j < (cnt + 1u) / 2u; ++j) {
+          x |= (uint64_t)s[j] << (8u * j);
+        }
+      }
+      dst[w] = gr::bam_revcomp16(gr::bam_pack16(x), cnt);
+      continue;
+    }
     const uint8_t* s = src + (uint64_t)w * 8u;
     uint64_t x = 0;
     if (cnt == 16u) {
@@ -461,7 +539,7 @@ k_bam_pack(const uint8_t* __restrict__ text, const uint64_t* __restrict__ seq_of
         x |= (uint64_t)s[j] << (8u * j);
       }
     }
-    uint32_t v = bam_pack16(x);
+    uint32_t v = gr::bam_pack16(x);
     if (cnt < 16u) {
       v &= (1u << (2u * cnt)) - 1u; // (the padding code behind an odd length is not a base)
     }
@@ -730,7 +808,7 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
     }
     grp_fastq_record* const d_rec = reinterpret_cast<grp_fastq_record*>(ip.d_rec.p);
     k_fq_records<<<dim3((uint32_t)((n_rec + (THREADS / 64) - 1) / (THREADS / 64))), dim3(THREADS), 0, ps>>>(fq->d_text, d_nl, n_rec, lead, d_rec);
-    k_fq_phred<<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog, d_rec);
+    k_fq_phred<false><<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog, d_rec);
     FQ_TRY2(hipGetLastError());
     static_assert(sizeof(grp_fastq_record) % 8 == 0, "the record table goes down as 64-bit words");
     const uint64_t rec_words = n_rec * sizeof(grp_fastq_record) / 8;
@@ -771,21 +849,32 @@ grp_fastq_parse(grp_ctx* c, const char* text, uint64_t n_bytes, int final_chunk,
 int
 grp_bam_parse(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset)
 {
-  if (!c || !out || !n_records || !bytes_consumed || !bad_offset || (!bytes && n_bytes)) {
+  uint64_t n_skipped = 0;
+  return grp_bam_parse_ex(c, bytes, n_bytes, final_chunk, 0u, out, n_records, bytes_consumed, bad_offset, &n_skipped);
+}
+
+int
+grp_bam_parse_ex(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, uint32_t accept, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset, uint64_t* n_skipped)
+{
+  if (!c || !out || !n_records || !bytes_consumed || !bad_offset || !n_skipped || (!bytes && n_bytes)) {
     return set_err(c, GRP_ERR_INVALID, "grp_bam_parse: bad argument");
   }
   *out = nullptr;
   *n_records = 0;
   *bytes_consumed = 0;
   *bad_offset = 0;
+  *n_skipped = 0;
+  if (accept & ~gr::BAM_REFUSED_FLAGS) {
+    return set_err(c, GRP_ERR_INVALID, "grp_bam_parse_ex: accept 0x%x holds other bits than 0x10, 0x100 and 0x800", accept);
+  }
   if (n_bytes >= (1ull << 36)) {
     return set_err(c, GRP_ERR_INVALID, "grp_bam_parse: chunk too large");
   }
   // the record chain, on the host (gr_bam.hpp): where the complete records begin, or the record that is refused
   std::vector<uint64_t> offs;
-  uint64_t used = 0, bad = 0;
+  uint64_t used = 0, bad = 0, skipped = 0;
   const char* why = nullptr;
-  if (gr::bam_walk(reinterpret_cast<const uint8_t*>(bytes), n_bytes, final_chunk != 0, &used, &bad, &why, [&](const gr::BamRecord& r) {
+  if (gr::bam_walk(reinterpret_cast<const uint8_t*>(bytes), n_bytes, final_chunk != 0, accept, &used, &skipped, &bad, &why, [&](const gr::BamRecord& r) {
         offs.push_back(r.off);
         return true;
       }) != 0) {
@@ -798,6 +887,7 @@ grp_bam_parse(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, 
   fq->bam = true;
   fq->n_bytes = n_bytes;
   *bytes_consumed = used;
+  *n_skipped = skipped;
   if (n_bytes == 0) {
     *out = fq;
     return GRP_OK;
@@ -805,6 +895,7 @@ grp_bam_parse(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, 
   auto fail = [&](int code) {
     grp_fastq_free(fq);
     *bytes_consumed = 0;
+    *n_skipped = 0;
     return code;
   };
 #define BAM_TRY(expr)                                                                                                  \
@@ -842,8 +933,12 @@ grp_bam_parse(grp_ctx* c, const char* bytes, uint64_t n_bytes, int final_chunk, 
       ip.h_bam_off[i] = offs[i] + fq->lead;
     }
     grp_fastq_record* const d_rec = reinterpret_cast<grp_fastq_record*>(ip.d_rec.p);
-    k_bam_records<<<dim3((uint32_t)((n_rec + (THREADS / 64) - 1) / (THREADS / 64))), dim3(THREADS), 0, ps>>>(fq->d_text, ip.h_bam_off.dev, n_rec, d_rec);
-    k_fq_phred<<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog_raw, d_rec);
+    k_bam_records<<<dim3((uint32_t)((n_rec + (THREADS / 64) - 1) / (THREADS / 64))), dim3(THREADS), 0, ps>>>(fq->d_text, ip.h_bam_off.dev, n_rec, accept, d_rec);
+    if (accept & gr::BAM_FLAG_REVERSE) {
+      k_fq_phred<true><<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog_raw, d_rec);
+    } else {
+      k_fq_phred<false><<<dim3((uint32_t)((n_rec + 63) / 64)), dim3(64), 0, ps>>>(fq->d_text, n_rec, c->d_delog_raw, d_rec);
+    }
     BAM_TRY(hipGetLastError());
     const uint64_t rec_words = n_rec * sizeof(grp_fastq_record) / 8;
     k_ing_words<<<dim3((uint32_t)std::min<uint64_t>((rec_words + THREADS - 1) / THREADS, 256)), dim3(THREADS), 0, ps>>>(reinterpret_cast<unsigned long long*>(ip.h_rec.dev), reinterpret_cast<const unsigned long long*>(d_rec), rec_words);
@@ -970,7 +1065,7 @@ grp_fastq_pack(grp_ctx* c, grp_fastq* fq, const uint32_t* sel, uint32_t n_sel, g
       delete rd;
       return set_err(c, GRP_ERR_INVALID, "grp_fastq_pack: record %u holds a non-ACGT base", sel[i]);
     }
-    seq_off[i] = r.seq_off;
+    seq_off[i] = r.seq_off | ((fq->bam && (r.flags & GRP_FQ_REVERSED)) ? BAM_PACK_REVERSED : 0ull);
     len[i] = r.seq_len;
     word_off[i] = w;
     w += (r.seq_len + 15u) / 16u;

@@ -228,8 +228,9 @@ InputFile::peek()
   return c;
 }
 
-FastqStream::FastqStream(const std::string& path)
+FastqStream::FastqStream(const std::string& path, uint32_t bam_accept)
   : path_(path)
+  , bam_accept_(bam_accept)
   , in_(path)
 {
   buf_.resize(size_t(8) << 20);
@@ -296,10 +297,10 @@ FastqStream::next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bas
       bam_header_done_ = true;
       continue;
     }
-    uint64_t used = 0, bad = 0;
+    uint64_t used = 0, bad = 0, skipped = 0;
     const char* why = nullptr;
     bool full = false;
-    int rc = bam_walk(p, end_ - pos_, eof_, &used, &bad, &why, [&](const BamRecord& b) {
+    int rc = bam_walk(p, end_ - pos_, eof_, bam_accept_, &used, &skipped, &bad, &why, [&](const BamRecord& b) {
       if (out.rec.size() >= max_records || out.bases >= max_bases) {
         full = true;
         return false;
@@ -313,8 +314,16 @@ FastqStream::next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bas
       r.seq_len = r.qual_len = b.l_seq;
       out.text.resize(r.seq_off + 2 * (size_t)b.l_seq + 2, '\0');
       r.qual_off = r.seq_off + b.l_seq + 1;
-      bam_decode_bases(p + b.seq_off, 0, b.l_seq, out.text.data() + r.seq_off);
-      if (!bam_decode_quals(p + b.qual_off, b.l_seq, out.text.data() + r.qual_off)) {
+      const bool reversed = (b.flag & BAM_FLAG_REVERSE) != 0; // (accepted, or the walk had refused it: the twin's orientation)
+      bool quals_ok;
+      if (reversed) {
+        bam_decode_bases_rev(p + b.seq_off, b.l_seq, 0, b.l_seq, out.text.data() + r.seq_off);
+        quals_ok = bam_decode_quals_rev(p + b.qual_off, b.l_seq, 0, b.l_seq, out.text.data() + r.qual_off);
+      } else {
+        bam_decode_bases(p + b.seq_off, 0, b.l_seq, out.text.data() + r.seq_off);
+        quals_ok = bam_decode_quals(p + b.qual_off, b.l_seq, out.text.data() + r.qual_off);
+      }
+      if (!quals_ok) {
         out.text.resize(r.id_off);
         bad = b.off;
         why = "a quality without a FASTQ character (absent: 0xFF, or above 93)";
@@ -323,6 +332,7 @@ FastqStream::next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bas
       }
       out.rec.push_back(r);
       out.bases += r.seq_len;
+      bam_reversed_ += reversed ? 1 : 0;
       return true;
     });
     if (rc == 0 && why) {
@@ -333,6 +343,7 @@ FastqStream::next_batch_bam(RecordBatch& out, size_t max_records, size_t max_bas
       stopped_ = true;
       break;
     }
+    bam_skipped_ += skipped;
     pos_ += used;
     stream_off_ += used;
     if (full || eof_) {

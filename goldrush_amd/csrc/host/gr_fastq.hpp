@@ -78,8 +78,13 @@ struct RecordBatch
 class FastqStream
 {
 public:
-  explicit FastqStream(const std::string& path);
+  // bam_accept (gr_bam.hpp: the walk's `accept`): the flags of 0x910 that a BAM input is read with instead of refused —
+  // 0x910 hands out the records of the aligned twin (GRP_BAM_ALIGNED=on), 0 reads unaligned BAM only
+  explicit FastqStream(const std::string& path, uint32_t bam_accept = 0);
   ~FastqStream();
+  // BAM: the secondary / supplementary records passed over and the reverse-strand records handed out so far
+  uint64_t bam_skipped() const { return bam_skipped_; }
+  uint64_t bam_reversed() const { return bam_reversed_; }
   bool ok() const { return in_.ok(); }
   // SeqReader::get_format() == FASTQ  <=>  first byte of the file is '@'; unaligned BAM (the data begins with "BAM\1")
   // is read as its FASTQ twin (gr_bam.hpp): a format this program reads
@@ -94,6 +99,8 @@ private:
   std::string path_;
   int format_ = -1;          // input_format of the data (-1: not looked at yet)
   bool bam_header_done_ = false;
+  uint32_t bam_accept_ = 0;
+  uint64_t bam_skipped_ = 0, bam_reversed_ = 0;
   uint64_t stream_off_ = 0;  // BAM: offset of buf_[pos_] in the decompressed stream
   InputFile in_;
   std::vector<char> buf_;

@@ -111,5 +111,8 @@ main(int argc, char** argv)
                          uint64_t cap, double* sums, uint32_t* bad_unit, uint32_t* bad_rec) {
     return grp_records_fetch(static_cast<grp_ctx*>(c), kind, comp, n_comp, dict, n_dict, units, n_units, recs, n_recs, flags, out, cap, sums, bad_unit, bad_rec);
   };
+  ext.bam_parse_ex = [](void* c, const char* bytes, uint64_t n, int fin, uint32_t accept, void** out, uint64_t* nrec, uint64_t* used, uint64_t* bad, uint64_t* skipped) {
+    return grp_bam_parse_ex(static_cast<grp_ctx*>(c), bytes, n, fin, accept, reinterpret_cast<grp_fastq**>(out), nrec, used, bad, skipped);
+  };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

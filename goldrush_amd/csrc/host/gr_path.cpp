@@ -204,6 +204,7 @@ struct RecLoc
   uint32_t seq_len;
   uint64_t qual_rel;
   uint32_t qual_len;
+  uint8_t reversed; // a reverse-strand record of an aligned BAM file: written backwards (seq_rel / qual_rel: the stored bytes)
 };
 
 struct ResidentBatch
@@ -482,7 +483,7 @@ fill_bit_vector(PathRun& run, Resident& res)
         // not in filter_out_reads (read_hashing.cpp:35-42) — without a -f list exactly the reads selected here
         const Rec& r = b.rec[i];
         keep.skipped_before.push_back(skipped - 1);
-        keep.loc.push_back(RecLoc{ (uint32_t)b.file, b.base_off + r.id_off, (uint32_t)r.id_len, (uint32_t)(r.seq_off - r.id_off), (uint32_t)r.seq_len, (uint64_t)(r.qual_off - r.id_off), (uint32_t)r.qual_len });
+        keep.loc.push_back(RecLoc{ (uint32_t)b.file, b.base_off + r.id_off, (uint32_t)r.id_len, (uint32_t)(r.seq_off - r.id_off), (uint32_t)r.seq_len, (uint64_t)(r.qual_off - r.id_off), (uint32_t)r.qual_len, (uint8_t)(r.reversed ? 1 : 0) });
         keep.name_hash.push_back(fnv1a(b.text + r.id_off, r.id_len));
         res.bam[b.file] = b.bam ? 1 : 0;
         if (res.kind[b.file] != Resident::PLAIN) { // (no pread finds this id again)
@@ -838,7 +839,10 @@ Deferred::fetch_some(SinkState& st, size_t& i, size_t e)
       const RecLoc& l = p.loc;
       const WrittenSlice w = written_slice(run.opt, l.seq_len, l.qual_len, p.kind, p.trim_start, p.trim_end, p.num_tiles);
       const uint64_t t0 = plan.rec_text_off[j];
-      recs.push_back(grp_fetch_record{ t0, t0 + l.seq_rel, t0 + l.qual_rel, out_n, l.id_len, (uint32_t)w.off, (uint32_t)w.n_seq, (uint32_t)w.qoff, (uint32_t)w.n_qual, w.trimmed ? GRP_FETCH_REC_TRIMMED : 0u });
+      // (a reversed record: the written slice counts in the twin's coordinates, the fetch takes the stored range and writes it backwards)
+      const uint32_t seq_from = l.reversed ? (uint32_t)(l.seq_len - w.off - w.n_seq) : (uint32_t)w.off, qual_from = l.reversed ? (uint32_t)(l.qual_len - w.qoff - w.n_qual) : (uint32_t)w.qoff;
+      recs.push_back(grp_fetch_record{ t0, t0 + l.seq_rel, t0 + l.qual_rel, out_n, l.id_len, seq_from, (uint32_t)w.n_seq, qual_from, (uint32_t)w.n_qual,
+                                       (w.trimmed ? GRP_FETCH_REC_TRIMMED : 0u) | (l.reversed ? GRP_FETCH_REC_REVERSED : 0u) });
       out_n += 1 + (uint64_t)l.id_len + (w.trimmed ? 9 : 11) + w.n_seq + 1 + (fastq ? 3 + (uint64_t)w.n_qual : 0);
     }
     out.resize((size_t)out_n);
@@ -868,7 +872,7 @@ Deferred::fetch_some(SinkState& st, size_t& i, size_t e)
       const Pending& p = pend[i + j];
       const RecLoc& l = p.loc;
       const size_t t0 = (size_t)plan.rec_text_off[j];
-      const Rec rec{ t0, l.id_len, t0 + l.seq_rel, l.seq_len, t0 + (size_t)l.qual_rel, l.qual_len };
+      const Rec rec{ t0, l.id_len, t0 + l.seq_rel, l.seq_len, t0 + (size_t)l.qual_rel, l.qual_len, l.reversed != 0 };
       sums.push_back(write_record(st, b, rec, p.kind, p.trim_start, p.trim_end, p.num_tiles));
     }
     n_out_bytes += (uint64_t)(run.out.tellp() - before);
@@ -961,6 +965,9 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   if (ext && ext->struct_size >= offsetof(grp_engine_ext, records_fetch) + sizeof(ext->records_fetch)) {
     run.ext.records_fetch = ext->records_fetch;
   }
+  if (ext && ext->struct_size >= offsetof(grp_engine_ext, bam_parse_ex) + sizeof(ext->bam_parse_ex)) {
+    run.ext.bam_parse_ex = ext->bam_parse_ex;
+  }
   Opts& opt = run.opt;
   // Several GPUs of one node: one process per GPU (GRP_WORLD / GRP_RANK, or the launcher's
   // WORLD_SIZE / RANK; LOCAL_RANK picks the device).  Every rank runs the whole program on
@@ -1024,6 +1031,18 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     }
     run.gzidx.resize(run.files.size());
     run.bgzf_map.resize(run.files.size());
+    run.bam_aligned.resize(run.files.size());
+  }
+  {
+    // GRP_BAM_ALIGNED=on: a BAM input is read as its aligned twin — what `samtools fastq -n` writes for it with its default
+    // filters (gr_bam.hpp).  Read here, once, in front of the first pass; opt-in, because records are dropped
+    const char* e = getenv("GRP_BAM_ALIGNED");
+    if (e && !strcmp(e, "on")) {
+      run.bam_accept = BAM_REFUSED_FLAGS;
+    } else if (e && strcmp(e, "off")) {
+      std::cerr << "goldrush-path: GRP_BAM_ALIGNED=" << e << ": the switch takes on or off" << std::endl;
+      return 1;
+    }
   }
   struct ShmGuard
   {
@@ -1100,6 +1119,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   if (use_ntcard) {
     uint64_t genome_size = 0;
     ec = calc_ntcard_genome_size(run, genome_size);
+    run.say_bam_aligned();
     if (ec >= 0) {
       return ec;
     }
@@ -1132,6 +1152,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     run.shard_fill = plan != GR_MERGE_NONE;
   }
   ec = calc_min_phred_threshold(run);
+  run.say_bam_aligned();
   if (ec >= 0) {
     return ec;
   }
@@ -1211,6 +1232,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     }
   }
   ec = fill_bit_vector(run, res);
+  run.say_bam_aligned();
   if (ec >= 0) {
     return ec;
   }
@@ -1412,6 +1434,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
         return 1;
       }
     }
+    run.say_bam_aligned();
     if (finished) {
       run.out.flush();
       return input_error() ? 1 : 0; // exit(0) inside silver_path_check (:173-176)

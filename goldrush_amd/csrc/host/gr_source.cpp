@@ -62,7 +62,7 @@ class HostSource : public RecordSource
 public:
   HostSource(PathRun& run)
     : run_(run)
-    , fq_(new FastqStream(run.files[0]))
+    , fq_(new FastqStream(run.files[0], run.bam_accept))
   {}
   // (several files: check_inputs has looked at every one of them before the first pass)
   bool ok() const override { return run_.files.size() > 1 || fq_->ok(); }
@@ -71,10 +71,13 @@ public:
   {
     // a file's reader hands out that file's records to its end — as it would on its own — and the next file's takes over
     while (!fq_->next_batch(rb_, BATCH_RECORDS, BATCH_BASES)) {
+      if (!input_failed()) { // the file has been read to its end
+        run_.note_bam_aligned(file_, fq_->bam_skipped(), fq_->bam_reversed());
+      }
       if (file_ + 1 >= run_.files.size() || input_failed()) {
         return false;
       }
-      fq_.reset(new FastqStream(run_.files[++file_]));
+      fq_.reset(new FastqStream(run_.files[++file_], run_.bam_accept));
     }
     b.file = file_;
     b.base_off = 0;
@@ -622,7 +625,9 @@ open_feed(PathRun& run, size_t file, const FilePlan& pl)
 
 // Raw text chunks parsed, filtered and packed on the GPU (grpath_ingest.h).  An unaligned BAM input (gr_bam.hpp) takes the
 // same way: the feeds deliver its bytes, the header is skipped in front of the first parse — it may span chunks: the
-// carry of partial records holds it until it is complete — and grp_engine_ext::bam_parse stands where fastq_parse does.
+// carry of partial records holds it until it is complete — and grp_engine_ext::bam_parse stands where fastq_parse does
+// (bam_parse_ex with GRP_BAM_ALIGNED=on: reverse-strand records come back with GRP_FQ_REVERSED, secondary and supplementary
+// ones are consumed without an entry).
 // A reader thread keeps the NEXT chunk of the input coming (Feed::fill) while the caller works on the current one —
 // inflate, upload, parse, pack, fill or classify — so a pass costs max(read, GPU) per chunk instead of their sum.  Four
 // slots in ONE page-locked buffer; every slot has room in front of the bytes read for the unconsumed tail of
@@ -740,6 +745,7 @@ public:
         // what that left over was its own truncation
         carry_.clear();
         bam_header_done_ = false;
+        bam_skipped_ = bam_reversed_ = 0;
         ++n_files_[0];
       }
       if ((long)file == skip_file_) { // behind a line that is no FASTQ header the file has ended for good: what the reader had read of it already
@@ -780,6 +786,9 @@ public:
       }
       uint64_t text_off = sl->file_off - carry_.size(); // offset of text[0] in the file's stream
       if (fill == 0) { // (a file without a byte, or one whose last chunk is empty)
+        if (eof && format_[file] == 2) {
+          run_.note_bam_aligned(file, bam_skipped_, bam_reversed_);
+        }
         if (sl->last) {
           done_ = true;
         }
@@ -824,10 +833,11 @@ public:
         }
       }
       const double tp0 = now_s();
-      uint64_t bad_off = 0;
+      uint64_t bad_off = 0, n_skipped = 0;
       ++n_files_[1];
-      const int prc = bam ? run_.ext.bam_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &bad_off)
-                          : run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
+      const int prc = bam && run_.bam_accept ? run_.ext.bam_parse_ex(run_.ctx, text, fill, eof ? 1 : 0, run_.bam_accept, &fq_, &n_rec, &used, &bad_off, &n_skipped)
+                      : bam                  ? run_.ext.bam_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &bad_off)
+                                             : run_.vt.fastq_parse(run_.ctx, text, fill, eof ? 1 : 0, &fq_, &n_rec, &used, &stopped);
       t_tr_[1] += now_s() - tp0;
       if (prc == GRP_ERR_INVALID && bam) { // a refused record: the input's failure, not the engine's
         note_bam_failure(path, text_off + bad_off, run_.vt.last_error ? run_.vt.last_error(run_.ctx) : nullptr);
@@ -840,12 +850,14 @@ public:
         done_ = true;
         break;
       }
-      if (n_rec == 0 && !eof && !stopped) {
+      if (n_rec == 0 && used == 0 && !eof && !stopped) {
         // not one complete record yet: everything is carried into the next chunk
         release();
         carry_.assign(text, text + fill);
         continue;
       }
+      // (an aligned BAM chunk may consume bytes and hand out no record: secondary / supplementary records alone)
+      bam_skipped_ += n_skipped;
       carry_.assign(text + used, text + fill);
       if (stopped && !eof) {
         // the file has ended here, like a reader at the end of its input; the reader thread leaves it at its next chunk
@@ -855,19 +867,27 @@ public:
       if ((eof || stopped) && file + 1 == run_.files.size()) {
         done_ = true;
       }
+      if (n_rec) {
+        meta_.resize(n_rec);
+        run_.vt.fastq_records(fq_, meta_.data());
+        for (size_t i = 0; bam && i < n_rec; ++i) {
+          bam_reversed_ += (meta_[i].flags & GRP_FQ_REVERSED) ? 1 : 0;
+        }
+      }
+      if (bam && eof) { // the file has been read to its end
+        run_.note_bam_aligned(file, bam_skipped_, bam_reversed_);
+      }
       if (n_rec == 0) {
         release();
         continue;
       }
-      meta_.resize(n_rec);
-      run_.vt.fastq_records(fq_, meta_.data());
       b.text = text;
       b.file = file;
       b.base_off = text_off;
       b.rec.resize(n_rec);
       for (size_t i = 0; i < n_rec; ++i) {
         const grp_fastq_record& m = meta_[i];
-        b.rec[i] = Rec{ (size_t)m.id_off, m.id_len, (size_t)m.seq_off, m.seq_len, (size_t)m.qual_off, m.qual_len };
+        b.rec[i] = Rec{ (size_t)m.id_off, m.id_len, (size_t)m.seq_off, m.seq_len, (size_t)m.qual_off, m.qual_len, bam && (m.flags & GRP_FQ_REVERSED) != 0 };
       }
       b.seq_is_upper = false;
       b.bam = bam;
@@ -1074,6 +1094,7 @@ private:
   long skip_file_ = -1;            // consumer's: the file that ended at a line that is no FASTQ header
   std::atomic<long> abandon_{ -1 }; // ... said to the reader thread
   bool bam_header_done_ = false;   // BAM: the header of the file being parsed has been skipped
+  uint64_t bam_skipped_ = 0, bam_reversed_ = 0; // ... and what the parses of that file have met of an aligned file's records
   void* fq_ = nullptr;
   std::vector<grp_fastq_record> meta_;
 };
@@ -1092,7 +1113,8 @@ open_source(PathRun& run)
   std::vector<int> format(run.files.size(), 0);
   for (size_t f = 0; gpu && f < run.files.size(); ++f) {
     format[f] = probe_format(run.files[f]);
-    gpu = !(format[f] == 2 && !run.ext.bam_parse); // (a BAM file and an engine without bam_parse: the host reader, for all the files)
+    // (a BAM file and an engine without bam_parse — GRP_BAM_ALIGNED=on: without bam_parse_ex: the host reader, for all the files)
+    gpu = !(format[f] == 2 && !(run.bam_accept ? run.ext.bam_parse_ex != nullptr : run.ext.bam_parse != nullptr));
   }
   if (gpu) {
     return std::unique_ptr<RecordSource>(new GpuSource(run, format));

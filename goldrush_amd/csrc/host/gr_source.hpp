@@ -2,7 +2,8 @@
 // records, their Phred statistics and the selected ones as packed reads on the device.  HostSource reads and packs on
 // the host (engines without the ingest entry points); GpuSource hands raw text chunks to the engine (grpath_ingest.h),
 // from plain text, gzip through zlib, BGZF members or the segments of an indexed gzip file (gr_source.cpp).
-// An unaligned BAM input (gr_bam.hpp) is read as its FASTQ twin by either source.
+// A BAM input (gr_bam.hpp) is read as its FASTQ twin by either source — with GRP_BAM_ALIGNED=on (PathRun::bam_accept) as
+// its aligned twin: secondary and supplementary records passed over, reverse-strand records read backwards.
 // A run may have several input files (PathRun::files), of any of these formats: one source reads them one after the other
 // in a pass, each to its own end, and hands out their records as those of one file that holds them in that order.
 #pragma once
@@ -50,6 +51,38 @@ struct PathRun
   // a BGZF input: the members the last pass over that file walked, if it walked them to the file's end (BgzfFeed); a file
   // whose last pass did not go through the member feed, or left it for zlib at a member that is not BGZF, has none
   std::vector<std::shared_ptr<BgzfMap>> bgzf_map;
+  // GRP_BAM_ALIGNED=on: BAM_REFUSED_FLAGS, the flags a BAM input is read with instead of refused (0: unaligned BAM only).
+  // Per file, what the first pass that read it to its end met of them: said once, on rank 0, behind that pass
+  uint32_t bam_accept = 0;
+  struct BamAligned
+  {
+    uint64_t skipped = 0, reversed = 0; // secondary / supplementary records passed over, reverse-strand records read backwards
+    bool counted = false, said = false; // a pass has read the file to its end; its line has been written
+  };
+  std::vector<BamAligned> bam_aligned;
+  // a source, at the end of a file it has read from its first byte to its last
+  void note_bam_aligned(size_t file, uint64_t skipped, uint64_t reversed)
+  {
+    if (bam_aligned.size() < files.size()) {
+      bam_aligned.resize(files.size());
+    }
+    if (!bam_aligned[file].counted) {
+      bam_aligned[file].counted = true;
+      bam_aligned[file].skipped = skipped;
+      bam_aligned[file].reversed = reversed;
+    }
+  }
+  // behind a pass: one line per BAM file that held such records (ranks other than 0 are silent)
+  void say_bam_aligned()
+  {
+    for (size_t f = 0; f < bam_aligned.size(); ++f) {
+      BamAligned& a = bam_aligned[f];
+      if (a.counted && !a.said && (a.skipped || a.reversed)) {
+        std::cerr << "GRP_BAM_ALIGNED: " << files[f] << ": " << a.skipped << " secondary or supplementary records skipped, " << a.reversed << " reverse-strand records read as their reverse complement" << std::endl;
+      }
+      a.said = a.said || a.counted;
+    }
+  }
 
   int fail_engine(const char* what)
   {
@@ -62,6 +95,7 @@ struct PathRun
 struct Rec
 {
   size_t id_off, id_len, seq_off, seq_len, qual_off, qual_len;
+  bool reversed = false; // a BAM batch: a reverse-strand record of an aligned file, read backwards (seq_off / qual_off: the stored bytes)
 };
 
 struct Batch
@@ -77,14 +111,19 @@ struct Batch
   // name is text as it stands.  What reads a record's bases or qualities goes through seq_text / qual_text.
   bool bam = false;
   std::string id_str(size_t i) const { return std::string(text + rec[i].id_off, rec[i].id_len); }
-  // bases [from, from + n) of a record as the characters of its FASTQ form (`tmp`: where they are decoded to, if they must be)
+  // bases [from, from + n) of a record as the characters of its FASTQ form (`tmp`: where they are decoded to, if they must
+  // be); a reversed record: the slice counts in the twin's coordinates
   const char* seq_text(const Rec& r, size_t from, size_t n, std::string& tmp) const
   {
     if (!bam) {
       return text + r.seq_off + from;
     }
     tmp.resize(n);
-    bam_decode_bases(reinterpret_cast<const uint8_t*>(text + r.seq_off), from, n, &tmp[0]);
+    if (r.reversed) {
+      bam_decode_bases_rev(reinterpret_cast<const uint8_t*>(text + r.seq_off), r.seq_len, from, n, &tmp[0]);
+    } else {
+      bam_decode_bases(reinterpret_cast<const uint8_t*>(text + r.seq_off), from, n, &tmp[0]);
+    }
     return tmp.data();
   }
   const char* qual_text(const Rec& r, size_t from, size_t n, std::string& tmp) const
@@ -93,7 +132,11 @@ struct Batch
       return text + r.qual_off + from;
     }
     tmp.resize(n);
-    (void)bam_decode_quals(reinterpret_cast<const uint8_t*>(text + r.qual_off) + from, n, &tmp[0]); // (the parse has refused what has no character)
+    if (r.reversed) {
+      (void)bam_decode_quals_rev(reinterpret_cast<const uint8_t*>(text + r.qual_off), r.qual_len, from, n, &tmp[0]);
+    } else {
+      (void)bam_decode_quals(reinterpret_cast<const uint8_t*>(text + r.qual_off) + from, n, &tmp[0]); // (the parse has refused what has no character)
+    }
     return tmp.data();
   }
 };

@@ -110,12 +110,16 @@ GZIP_INFLATE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _v
 BAM_PARSE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 
+BAM_PARSE_EX_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+
+
 RECORDS_FETCH_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_double),
                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
 
 class grp_engine_ext(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN), ("records_fetch", RECORDS_FETCH_FN)]
+    _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN), ("records_fetch", RECORDS_FETCH_FN),
+                ("bam_parse_ex", BAM_PARSE_EX_FN)]
 
 
 class gr_bam_record(C.Structure):
@@ -170,6 +174,8 @@ SIGNATURES = {
     "gr_bam_header": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "gr_bam_walk": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]),
     "gr_bam_decode": (C.c_int, [_vp, C.POINTER(gr_bam_record), _vp, _vp]),
+    "gr_bam_walk_ex": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]),
+    "gr_bam_decode_twin": (C.c_int, [_vp, C.POINTER(gr_bam_record), C.c_uint64, C.c_uint64, _vp, _vp]),
     "gr_input_read": (C.c_uint64, [C.c_char_p, C.c_uint64, _vp, C.c_uint64]),
     "gr_gzidx_build": (_vp, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
     "gr_gzidx_info": (None, [_vp, _vp]),
@@ -320,6 +326,26 @@ def bam_walk(buf: bytes, final_chunk: bool = True, cap: int = 1 << 16):
     return rc, list(recs[:min(n.value, cap)]), n.value, used.value, bad.value, (why.value or b"").decode()
 
 
+def bam_walk_ex(buf: bytes, final_chunk: bool = True, accept: int = 0, cap: int = 1 << 16):
+    """gr_bam_walk_ex: the walk that reads the flags of `accept` (a subset of 0x910) instead of refusing them
+    -> (rc, [gr_bam_record], records found, consumed, bad_offset, why, skipped)"""
+    raw = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+    recs = (gr_bam_record * max(cap, 1))()
+    n, used, bad, why, skipped = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_char_p(), C.c_uint64()
+    rc = load().gr_bam_walk_ex(_p(raw), len(buf), 1 if final_chunk else 0, accept, recs, cap, C.byref(n), C.byref(used), C.byref(bad), C.byref(why), C.byref(skipped))
+    return rc, list(recs[:min(n.value, cap)]), n.value, used.value, bad.value, (why.value or b"").decode(), skipped.value
+
+
+def bam_decode_twin(buf: bytes, rec: gr_bam_record, start: int = 0, n: "int | None" = None):
+    """gr_bam_decode_twin -> (rc, bases, quality characters): the slice [start, start + n) of one record as the aligned twin
+    has it (flag 0x10: the reverse complement, the slice in twin coordinates)"""
+    raw = np.frombuffer(buf, dtype=np.uint8)
+    n = rec.l_seq - start if n is None else n
+    seq, qual = C.create_string_buffer(max(n, 0) + 1), C.create_string_buffer(max(n, 0) + 1)
+    rc = load().gr_bam_decode_twin(_p(raw), C.byref(rec), start, n, seq, qual)
+    return rc, seq.raw[:max(n, 0)], qual.raw[:max(n, 0)]
+
+
 def bam_decode(buf: bytes, rec: gr_bam_record):
     """gr_bam_decode -> (rc, bases, quality characters) of one record of bam_walk"""
     raw = np.frombuffer(buf, dtype=np.uint8)
@@ -365,6 +391,7 @@ def hip_engine_ext() -> grp_engine_ext:
     ext.gzip_inflate = C.cast(lib.grp_gzip_inflate, GZIP_INFLATE_FN)
     ext.bam_parse = C.cast(lib.grp_bam_parse, BAM_PARSE_FN)
     ext.records_fetch = C.cast(lib.grp_records_fetch, RECORDS_FETCH_FN)
+    ext.bam_parse_ex = C.cast(lib.grp_bam_parse_ex, BAM_PARSE_EX_FN)
     return ext
 
 

@@ -166,7 +166,8 @@ gzip_segment_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_of
 # grp_fetch_record: one record to format out of the units' text (offsets count in the concatenated text of the call's units)
 fetch_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("out_off", "<u8"), ("id_len", "<u4"), ("seq_from", "<u4"), ("n_seq", "<u4"),
                               ("qual_from", "<u4"), ("n_qual", "<u4"), ("flags", "<u4")])
-FETCH_REC_TRIMMED = 1
+FETCH_REC_TRIMMED, FETCH_REC_REVERSED = 1, 2
+FQ_NON_ACGT, FQ_REVERSED = 1, 2
 FETCH_UNITS_BGZF, FETCH_UNITS_GZIP = 0, 1
 FETCH_FASTQ, FETCH_BAM = 1, 2
 
@@ -175,6 +176,7 @@ SIGNATURES.update({
     "grp_fastq_prefetch": (C.c_int, [_vp, _vp, C.c_uint64]),
     "grp_fastq_parse": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "grp_bam_parse": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "grp_bam_parse_ex": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "grp_fastq_records": (C.c_int, [_vp, _vp]),
     "grp_fastq_pack": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "grp_fastq_free": (None, [_vp]),
@@ -391,18 +393,24 @@ class Engine:
             self._check(self.lib.grp_fastq_records(out, _ptr(rec)))
         return out, rec, used.value, bool(stopped.value)
 
-    def bam_parse(self, data, final_chunk: bool = True, n_bytes: "int | None" = None):
+    def bam_parse(self, data, final_chunk: bool = True, n_bytes: "int | None" = None, accept: "int | None" = None):
         """grp_bam_parse: the records of an unaligned BAM stream, `data` beginning at a record (the header skipped).  `data` is
         bytes, or a caller-owned uint8 array of which the first n_bytes are parsed in place (what a pinned or prefetched
         buffer needs).  Returns (handle, records[fastq_record_dtype], bytes_consumed); the handle is served by fastq_pack /
-        fastq_free.  A refused record raises GrpError with .bad_offset = its offset in `data`."""
+        fastq_free.  A refused record raises GrpError with .bad_offset = its offset in `data`.
+        accept (a subset of 0x910): grp_bam_parse_ex, the records of an aligned stream as its aligned twin has them; returns
+        (handle, records, bytes_consumed, n_skipped)."""
         if isinstance(data, np.ndarray):
             buf, n = data, data.size if n_bytes is None else n_bytes
         else:
             buf, n = (np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)), len(data)
         out = C.c_void_p()
         n_rec, used, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        rc = self.lib.grp_bam_parse(self._h, _ptr(buf), n, 1 if final_chunk else 0, C.byref(out), C.byref(n_rec), C.byref(used), C.byref(bad))
+        skipped = C.c_uint64()
+        if accept is None:
+            rc = self.lib.grp_bam_parse(self._h, _ptr(buf), n, 1 if final_chunk else 0, C.byref(out), C.byref(n_rec), C.byref(used), C.byref(bad))
+        else:
+            rc = self.lib.grp_bam_parse_ex(self._h, _ptr(buf), n, 1 if final_chunk else 0, accept, C.byref(out), C.byref(n_rec), C.byref(used), C.byref(bad), C.byref(skipped))
         if rc != GRP_OK:
             e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
             e.bad_offset = bad.value
@@ -410,7 +418,7 @@ class Engine:
         rec = np.zeros(n_rec.value, dtype=fastq_record_dtype)
         if n_rec.value:
             self._check(self.lib.grp_fastq_records(out, _ptr(rec)))
-        return out, rec, used.value
+        return (out, rec, used.value) if accept is None else (out, rec, used.value, skipped.value)
 
     # -- BGZF members inflated on the device (include/grpath_ingest.h)
     def bgzf_inflate(self, comp, blocks, text_cap: "int | None" = None) -> bytes:

@@ -627,6 +627,8 @@ int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
 /* ... and the records of an unaligned BAM stream, parsed where FASTQ text is (grpath_ingest.h) */
 typedef struct grp_fastq grp_fastq;
 int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
+/* ... of an aligned one, read as `samtools fastq` reads it: `accept` says which of flag 0x10 / 0x100 / 0x800 are read (grpath_ingest.h) */
+int grp_bam_parse_ex(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, uint32_t accept, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset, uint64_t* n_skipped);
 /* ... and records fetched out of members or segments and formatted for the output files on the device (grpath_ingest.h) */
 typedef struct grp_fetch_record grp_fetch_record;
 int grp_records_fetch(grp_ctx* ctx, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags,

@@ -314,7 +314,15 @@ void gr_gzidx_free(gr_gzidx* h);
  * *consumed = the bytes they span; 0, or -1 with *bad_offset = the refused record and *why = the reason: a block_size
  * smaller than the record's fields, l_read_name 0, a name without NUL, flag 0x10 / 0x100 / 0x800, and with final_chunk a
  * stream that ends inside a record.  gr_bam_decode: l_seq bases and l_seq quality characters of one record; -1: a
- * quality without a FASTQ character (0xFF, above 93). */
+ * quality without a FASTQ character (0xFF, above 93).
+ * The aligned twin (GRP_BAM_ALIGNED=on; what `samtools fastq -n` writes with its default filters, written down from the SAM
+ * specification and samtools' documented behaviour): gr_bam_walk_ex is the walk with `accept`, a subset of 0x910 (any other
+ * bit: -1) — a record with a flag bit of 0x910 outside `accept` is refused as by gr_bam_walk (accept 0 is gr_bam_walk), one
+ * with an accepted 0x100 / 0x800 is checked, consumed, counted in *skipped and not written to recs (*consumed may be > 0
+ * with *n_records 0), one with an accepted 0x10 is written with its flag.  gr_bam_decode_twin: bases and quality characters
+ * [from, from + n) of one record as the aligned twin has them — flag 0x10: base j = the complement of stored base
+ * l_seq-1-j (the 4-bit code bit-reversed), quality j = qual[l_seq-1-j] + 33, the slice in twin coordinates; else the
+ * stored order.  -1: a quality without a FASTQ character in the slice, or a slice outside the record. */
 typedef struct
 {
   uint64_t off, name_off, seq_off, qual_off, end; /* block_size field, name, 4-bit bases, qualities, the next record */
@@ -324,6 +332,8 @@ typedef struct
 int gr_bam_header(const unsigned char* buf, uint64_t n, uint64_t* header_bytes);
 int gr_bam_walk(const unsigned char* buf, uint64_t n, int final_chunk, gr_bam_record* recs, uint64_t cap, uint64_t* n_records, uint64_t* consumed, uint64_t* bad_offset, const char** why);
 int gr_bam_decode(const unsigned char* buf, const gr_bam_record* rec, char* seq_out, char* qual_out);
+int gr_bam_walk_ex(const unsigned char* buf, uint64_t n, int final_chunk, uint32_t accept, gr_bam_record* recs, uint64_t cap, uint64_t* n_records, uint64_t* consumed, uint64_t* bad_offset, const char** why, uint64_t* skipped);
+int gr_bam_decode_twin(const unsigned char* buf, const gr_bam_record* rec, uint64_t from, uint64_t n, char* seq_out, char* qual_out);
 
 /* ---- optional engine entry points that came after grp_engine_vt was frozen at 48 members: a second table, every member
  * optional (NULL, or a struct_size that ends in front of it: the host takes the path it took without it) */
@@ -344,6 +354,10 @@ typedef struct
    * gzip_inflate above and formats them itself */
   int (*records_fetch)(void* ctx, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags,
                        char* out, uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record);
+  /* grp_bam_parse_ex: with it (and GRP_BAM_ALIGNED=on), the records of an aligned BAM input are parsed and packed on the
+   * device as the reads of its aligned twin; without it such a run's BAM files take the host reader, as BAM files do on an
+   * engine without bam_parse */
+  int (*bam_parse_ex)(void* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, uint32_t accept, void** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset, uint64_t* n_skipped);
 } grp_engine_ext;
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */

@@ -34,12 +34,16 @@ typedef struct
   uint32_t id_len;    /* up to the first whitespace of the header */
   uint32_t seq_len;   /* trailing CR / blanks trimmed */
   uint32_t qual_len;
-  uint32_t flags;     /* GRP_FQ_NON_ACGT: find_first_not_of("ACGTacgt") != npos (goldrush_path.cpp:293) */
+  uint32_t flags;     /* GRP_FQ_NON_ACGT: find_first_not_of("ACGTacgt") != npos (goldrush_path.cpp:293); GRP_FQ_REVERSED */
   double phred_sum;   /* sum_{i<qual_len} 10^(-(q_i-33)/10), left to right */
   double phred_first; /* the same sum after i = qual_len/2 - 1 (0 when never reached) */
 } grp_fastq_record;
 
 #define GRP_FQ_NON_ACGT 1u
+/* grp_bam_parse_ex with flag 0x10 accepted, a reverse-strand record: the read is the reverse complement of what is stored.
+ * seq_off / qual_off still name the stored bytes; phred_sum / phred_first are those of the quality line read backwards;
+ * grp_fastq_pack packs the reverse complement. */
+#define GRP_FQ_REVERSED 2u
 
 /*
  * Upload and parse `n_bytes` of FASTQ text (host memory; pinned memory — grp_fastq_pin — is faster).
@@ -167,6 +171,24 @@ int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
  *    phred_sum / phred_first are the same left-to-right double sums, bit-identical to those of the twin's quality line.
  */
 int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);
+/*
+ * The same for an ALIGNED BAM file, read as the FASTQ that `samtools fastq -n` writes for it with its default filters
+ * (the aligned twin; written down from the SAM specification and samtools' documented behaviour, not pinned against
+ * samtools' output).  `accept` is a subset of 0x910 (any other bit: GRP_ERR_INVALID); grp_bam_parse is the call with
+ * accept 0.  A record with a flag bit of 0x910 that is not in `accept` is refused as above.
+ *  - An accepted 0x100 / 0x800 (secondary, supplementary): the record is no read of the twin.  Its structural fields are
+ *    checked like any record's (the chain runs through it), it is consumed and counted in *n_skipped, its bases and
+ *    qualities are not looked at (0xFF qualities are fine) and it has no entry in the table.  A chunk may so consume bytes
+ *    and return no record.
+ *  - An accepted 0x10, and neither of the above: the entry has GRP_FQ_REVERSED.  The read is the complement of stored base
+ *    l_seq-1-j at base j (the complement of a 4-bit code is its bit reversal) with quality qual[l_seq-1-j] + 33.
+ *    seq_off / qual_off name the stored bytes; GRP_FQ_NON_ACGT does not depend on the order; phred_sum is the
+ *    right-to-left sum over the stored bytes and phred_first that sum after the stored bytes l_seq-1 ... l_seq - l_seq/2,
+ *    the same additions in the same order as the left-to-right sums of the twin's line: bit-identical to them.
+ *    grp_fastq_pack packs such a record as the twin's read.
+ *  - Every other record, flag 0x4 or paired-end flags included, is read as by grp_bam_parse.
+ */
+int grp_bam_parse_ex(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, uint32_t accept, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset, uint64_t* n_skipped);
 
 /*
  * ---- records of a compressed input, fetched and formatted on the device ----------------------------------------------
@@ -192,9 +214,14 @@ struct grp_fetch_record
   uint32_t n_seq;     /* ... and how many */
   uint32_t qual_from; /* first quality written, counted from qual_off ... */
   uint32_t n_qual;    /* ... and how many (ignored for the output without GRP_FETCH_FASTQ; the sum covers them all the same) */
-  uint32_t flags;     /* GRP_FETCH_REC_TRIMMED: the id gets "_trimmed", else "_untrimmed" */
+  uint32_t flags;     /* GRP_FETCH_REC_TRIMMED: the id gets "_trimmed", else "_untrimmed"; GRP_FETCH_REC_REVERSED */
 }; /* (the typedef is in grpath.h) */
 #define GRP_FETCH_REC_TRIMMED 1u
+/* With GRP_FETCH_BAM only (without it the flag is refused like any unknown one): a reverse-strand record of an aligned BAM
+ * file.  seq_from / n_seq and qual_from / n_qual name the STORED range (the caller computes l_seq - from - n of the twin's
+ * slice); it is written last element first, the bases complemented, the qualities + 33, and the sum is that of the
+ * written quality characters left to right: the right-to-left chain over the stored bytes. */
+#define GRP_FETCH_REC_REVERSED 2u
 /* unit_kind: what `units` points at */
 #define GRP_FETCH_UNITS_BGZF 0 /* grp_bgzf_block[]; dict is not looked at */
 #define GRP_FETCH_UNITS_GZIP 1 /* grp_gzip_segment[] with their histories in dict */
@@ -209,7 +236,8 @@ struct grp_fetch_record
  * (computed without GRP_FETCH_FASTQ too).
  * Synchronous, on the side stream, with the threading rules of grp_bgzf_inflate.  Both tables are checked before anything
  * is launched: the units as grp_bgzf_inflate / grp_gzip_inflate check theirs (GRP_ERR_INVALID, *bad_unit = the entry); of a
- * record the id, the bases' and the qualities' ranges inside the units' text, no flag but GRP_FETCH_REC_TRIMMED, its output
+ * record the id, the bases' and the qualities' ranges inside the units' text, no flag but GRP_FETCH_REC_TRIMMED (and, with
+ * GRP_FETCH_BAM, GRP_FETCH_REC_REVERSED), its output
  * range inside out_cap and disjoint from every other record's (GRP_ERR_INVALID, *bad_record = the entry; of two
  * overlapping records the one that begins later).  A unit that is not a valid stream with its CRC32 is refused as by
  * grp_bgzf_inflate (*bad_unit); `out` and `sums` are then untouched.  The call relies on no padding behind the text or
