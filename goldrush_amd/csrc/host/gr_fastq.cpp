@@ -116,26 +116,44 @@ input_format(const unsigned char* head, size_t n)
   return n >= 1 && head[0] == '@' ? 1 : 0;
 }
 
-// *err: errno of a read that failed (0: none; a short count is then the end of the file)
-static size_t
-pread_all(int fd, char* dst, size_t n, uint64_t off, int* err)
+size_t
+pread_full(int fd, void* dst, size_t want, uint64_t off, int* err)
 {
-  size_t got = 0;
-  while (got < n) {
-    const ssize_t r = pread(fd, dst + got, n - got, (off_t)(off + got));
+  *err = 0;
+  size_t k = 0;
+  while (k < want) {
+    const ssize_t r = pread(fd, static_cast<char*>(dst) + k, want - k, (off_t)(off + k));
     if (r < 0 && errno == EINTR) {
       continue;
     }
-    if (r < 0) {
-      *err = errno;
+    if (r <= 0) {
+      *err = r < 0 ? errno : 0;
       break;
     }
-    if (r == 0) {
-      break;
-    }
-    got += (size_t)r;
+    k += (size_t)r;
   }
-  return got;
+  return k;
+}
+
+FileProbe
+probe_file(const std::string& path)
+{
+  FileProbe p;
+  const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  p.opened = fd >= 0;
+  p.err = p.opened ? 0 : errno;
+  struct stat st;
+  if (p.opened && fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
+    p.regular = true;
+    p.size = (uint64_t)st.st_size;
+    unsigned char head[4];
+    const size_t k = pread_full(fd, head, sizeof(head), 0, &p.err);
+    p.magic = k < 2 ? FileProbe::NONE : (head[0] == 0x1f && head[1] == 0x8b) ? FileProbe::GZIP : input_format(head, k) == 2 ? FileProbe::BAM : FileProbe::OTHER;
+  }
+  if (p.opened) {
+    ::close(fd);
+  }
+  return p;
 }
 
 size_t
@@ -152,7 +170,7 @@ InputFile::read(char* dst, size_t n)
     size_t got = 0;
     int err = 0;
     if (threads < 2) {
-      got = pread_all(fd_, dst, n, off_, &err);
+      got = pread_full(fd_, dst, n, off_, &err);
     } else {
       // slice i covers [i * per, (i + 1) * per); the data ends in the first short slice
       const size_t per = (n + threads - 1) / threads;
@@ -160,9 +178,9 @@ InputFile::read(char* dst, size_t n)
       std::vector<int> errs(threads, 0);
       std::vector<std::thread> pool;
       for (size_t i = 1; i < threads; ++i) {
-        pool.emplace_back([&, i] { part[i] = pread_all(fd_, dst + i * per, std::min(per, n - i * per), off_ + i * per, &errs[i]); });
+        pool.emplace_back([&, i] { part[i] = pread_full(fd_, dst + i * per, std::min(per, n - i * per), off_ + i * per, &errs[i]); });
       }
-      part[0] = pread_all(fd_, dst, per, off_, &errs[0]);
+      part[0] = pread_full(fd_, dst, per, off_, &errs[0]);
       for (auto& t : pool) {
         t.join();
       }

@@ -25,6 +25,18 @@ void clear_input_failure();
 void note_bam_failure(const std::string& path, uint64_t off, const char* why);
 // what the first four bytes of the data say: 1 FASTQ ('@'), 2 BAM ("BAM\1"), 0 neither
 int input_format(const unsigned char* head, size_t n);
+// `want` bytes at `off`; fewer: the file ends there (*err 0) or the read failed (*err: errno; no descriptor: EBADF)
+size_t pread_full(int fd, void* dst, size_t want, uint64_t off, int* err);
+// One look at an input file: can it be opened (else err: the errno), is it a regular file, its size and what it begins
+// with.  Only a regular file is read from — the bytes of a pipe are the input.
+struct FileProbe
+{
+  bool opened = false, regular = false;
+  int err = 0;
+  uint64_t size = 0;
+  enum Magic { NONE, GZIP, BAM, OTHER } magic = NONE; // fewer than two bytes / 1f 8b / "BAM\1" (not compressed) / anything else
+};
+FileProbe probe_file(const std::string& path);
 
 class InputFile
 {

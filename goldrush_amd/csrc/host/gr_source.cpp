@@ -28,6 +28,31 @@ now_s()
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+void
+PathRun::note_bam_aligned(size_t file, uint64_t skipped, uint64_t reversed)
+{
+  if (bam_aligned.size() < files.size()) {
+    bam_aligned.resize(files.size());
+  }
+  if (!bam_aligned[file].counted) {
+    bam_aligned[file].counted = true;
+    bam_aligned[file].skipped = skipped;
+    bam_aligned[file].reversed = reversed;
+  }
+}
+
+void
+PathRun::say_bam_aligned()
+{
+  for (size_t f = 0; f < bam_aligned.size(); ++f) {
+    BamAligned& a = bam_aligned[f];
+    if (a.counted && !a.said && (a.skipped || a.reversed)) {
+      std::cerr << "GRP_BAM_ALIGNED: " << files[f] << ": " << a.skipped << " secondary or supplementary records skipped, " << a.reversed << " reverse-strand records read as their reverse complement" << std::endl;
+    }
+    a.said = a.said || a.counted;
+  }
+}
+
 namespace {
 
 // records / bases per host batch (one grp_reads upload each).  GRP_BATCH_RECORDS
@@ -191,26 +216,6 @@ public:
   virtual int peek() { return -2; }
   virtual bool ok() const { return true; } // the file could be opened
 };
-
-// `want` bytes at `off`; fewer: the file ends there (*err 0) or the read failed (*err: errno)
-size_t
-pread_full(int fd, unsigned char* dst, size_t want, uint64_t off, int* err)
-{
-  *err = 0;
-  size_t k = 0;
-  while (k < want) {
-    const ssize_t r = pread(fd, dst + k, want - k, (off_t)(off + k));
-    if (r < 0 && errno == EINTR) {
-      continue;
-    }
-    if (r <= 0) {
-      *err = r < 0 ? errno : 0;
-      break;
-    }
-    k += (size_t)r;
-  }
-  return k;
-}
 
 // Text: InputFile (parallel pread of a plain file, zlib for gzip data), or GzIndexReader — zlib as before, on the reader
 // thread — in the first pass over a plain gzip file, which leaves the index of its restart points in the run when it
@@ -563,21 +568,23 @@ plan_feed(PathRun& run, size_t file, size_t chunk)
   const std::string& path = run.files[file];
   FilePlan pl;
   pl.want = Feed::Sizes{ chunk, 0, 0 };
-  const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
-  if (fd < 0) {
+  const FileProbe p = probe_file(path);
+  if (!p.opened) {
     return pl;
   }
-  struct stat st;
-  const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-  unsigned char magic[2] = { 0, 0 };
-  const bool gz = regular && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+  const bool regular = p.regular, gz = p.magic == FileProbe::GZIP;
   const char* e = getenv("GRP_BGZF");
-  if (run.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
-    // is the first member a complete BGZF member?  (a member is at most 64 KiB; a pipe cannot be pread: zlib)
+  if (gz && run.ext.bgzf_inflate && !(e && !strcmp(e, "off"))) {
+    // is the first member a complete BGZF member?  (a member is at most 64 KiB)
     std::vector<unsigned char> head(BGZF_MAX_MEMBER);
-    const ssize_t k = pread(fd, head.data(), head.size(), 0);
+    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    int err = 0;
+    const size_t k = pread_full(fd, head.data(), head.size(), 0, &err);
+    if (fd >= 0) {
+      ::close(fd);
+    }
     grp_bgzf_block b;
-    if (k > 0 && bgzf_scan(head.data(), (size_t)k, &b, 1, nullptr, nullptr) == 1) {
+    if (k > 0 && bgzf_scan(head.data(), k, &b, 1, nullptr, nullptr) == 1) {
       pl.kind = FilePlan::BGZF;
       pl.want = BgzfFeed::want(chunk);
     }
@@ -595,9 +602,8 @@ plan_feed(PathRun& run, size_t file, size_t chunk)
   }
   if (pl.kind == FilePlan::TEXT && regular && !gz && !getenv("GRP_ZLIB_READER")) {
     pl.plain = true;
-    pl.plain_size = (uint64_t)st.st_size;
+    pl.plain_size = p.size;
   }
-  ::close(fd);
   return pl;
 }
 
@@ -1126,14 +1132,11 @@ std::string
 check_inputs(const PathRun& run)
 {
   for (const std::string& path : run.files) {
-    struct stat st;
-    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
-    if (fd < 0) {
-      return path + ": cannot be opened: " + strerror(errno);
+    const FileProbe p = probe_file(path);
+    if (!p.opened) {
+      return path + ": cannot be opened: " + strerror(p.err);
     }
-    const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-    ::close(fd);
-    if (regular && st.st_size != 0 && probe_format(path) <= 0) {
+    if (p.regular && p.size != 0 && probe_format(path) <= 0) {
       return path + ": neither FASTQ nor BAM";
     }
   }

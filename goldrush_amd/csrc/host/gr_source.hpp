@@ -1,4 +1,4 @@
-// The record sources of goldrush-path (gr_path.cpp): a pass over the input hands out batches of consecutive FASTQ
+// The record sources of goldrush-path (gr_passes.cpp): a pass over the input hands out batches of consecutive FASTQ
 // records, their Phred statistics and the selected ones as packed reads on the device.  HostSource reads and packs on
 // the host (engines without the ingest entry points); GpuSource hands raw text chunks to the engine (grpath_ingest.h),
 // from plain text, gzip through zlib, BGZF members or the segments of an indexed gzip file (gr_source.cpp).
@@ -61,28 +61,9 @@ struct PathRun
   };
   std::vector<BamAligned> bam_aligned;
   // a source, at the end of a file it has read from its first byte to its last
-  void note_bam_aligned(size_t file, uint64_t skipped, uint64_t reversed)
-  {
-    if (bam_aligned.size() < files.size()) {
-      bam_aligned.resize(files.size());
-    }
-    if (!bam_aligned[file].counted) {
-      bam_aligned[file].counted = true;
-      bam_aligned[file].skipped = skipped;
-      bam_aligned[file].reversed = reversed;
-    }
-  }
+  void note_bam_aligned(size_t file, uint64_t skipped, uint64_t reversed);
   // behind a pass: one line per BAM file that held such records (ranks other than 0 are silent)
-  void say_bam_aligned()
-  {
-    for (size_t f = 0; f < bam_aligned.size(); ++f) {
-      BamAligned& a = bam_aligned[f];
-      if (a.counted && !a.said && (a.skipped || a.reversed)) {
-        std::cerr << "GRP_BAM_ALIGNED: " << files[f] << ": " << a.skipped << " secondary or supplementary records skipped, " << a.reversed << " reverse-strand records read as their reverse complement" << std::endl;
-      }
-      a.said = a.said || a.counted;
-    }
-  }
+  void say_bam_aligned();
 
   int fail_engine(const char* what)
   {

@@ -1,11 +1,12 @@
-// Random access into a compressed input by DECOMPRESSED offset (gr_path.cpp: the reads of a BGZF / gzip / BAM input kept on
+// Random access into a compressed input by DECOMPRESSED offset (gr_writer.cpp: the reads of a BGZF / gzip / BAM input kept on
 // the device between the passes, whose written records are fetched through their inflatable units).  A file's units are
 // the members of a BGZF file (BgzfMap, written down by the pass that walks them to the file's end: BgzfFeed) or the
 // segments of a plain gzip file's index (GzIndex::segs); either way unit i holds the text [text_off[i], text_off[i + 1]) of
-// the file's decompressed stream.  Header-only and pure (no I/O): tools/dev/units_host_check.cpp drives it under the
-// sanitizers.
+// the file's decompressed stream.  Below them: what is written of a stored record, and its entry in a fetch call.
+// Header-only and pure (no I/O): tools/dev/units_host_check.cpp drives it under the sanitizers.
 #pragma once
 #include "../../../include/grpath_ingest.h"
+#include "gr_tiles.hpp"
 
 #include <algorithm>
 #include <cstddef>
@@ -114,6 +115,54 @@ plan_fetch(const std::vector<uint64_t>& text_off, const FetchItem* items, size_t
     ++pl.n_recs;
   }
   return pl.n_recs != 0;
+}
+
+// ---- from a stored record to what is written of it ----------------------------------------------------------------------
+// A read kept on the device (gr_resident.hpp), as the fill pass wrote it down: where its record lies in its file's text
+struct RecLoc
+{
+  uint32_t file;    // which of the run's files
+  uint64_t off;     // offset of the record's id in that file
+  uint32_t id_len;
+  uint32_t seq_rel; // seq / qual relative to `off`
+  uint32_t seq_len;
+  uint64_t qual_rel;
+  uint32_t qual_len;
+  uint8_t reversed; // a reverse-strand record of an aligned BAM file: written backwards (seq_rel / qual_rel: the stored bytes)
+};
+
+// The slice of a committed read that is written (goldrush_path.cpp:996-1002, 1055-1070): bases [off, off + n_seq), qualities
+// [qoff, qoff + n_qual); a read inserted whole is written whole
+struct WrittenSlice
+{
+  size_t off, n_seq, qoff, n_qual;
+  bool trimmed;
+};
+
+inline WrittenSlice
+written_slice(size_t tile, size_t seq_len, size_t qual_len, const grp_read_decision& d)
+{
+  WrittenSlice w{ 0, seq_len, 0, qual_len, d.kind == DEC_INSERT_TRIMMED };
+  if (w.trimmed) {
+    w.off = (size_t)d.trim_start * tile;
+    const size_t end_pos = (d.trim_end == d.num_tiles - 1) ? SIZE_MAX : (size_t)(d.trim_end - d.trim_start + 1) * tile;
+    w.n_seq = std::min(end_pos, seq_len - w.off);
+    w.n_qual = (w.off <= qual_len) ? std::min(end_pos, qual_len - w.off) : 0;
+  }
+  w.qoff = std::min(w.off, qual_len);
+  return w;
+}
+
+// The entry of grp_records_fetch (grpath_ingest.h) for a record whose id lies at `text_off` of the fetched text and whose
+// bytes go to out_off; *size: how many those are.  A reversed record: the written slice counts in the twin's coordinates,
+// the fetch takes the stored range and writes it backwards.
+inline grp_fetch_record
+fetch_record_of(const RecLoc& l, const WrittenSlice& w, uint64_t text_off, uint64_t out_off, bool fastq, uint64_t* size)
+{
+  const size_t seq_from = l.reversed ? l.seq_len - w.off - w.n_seq : w.off, qual_from = l.reversed ? l.qual_len - w.qoff - w.n_qual : w.qoff;
+  *size = 1 + (uint64_t)l.id_len + (w.trimmed ? 9 : 11) + w.n_seq + 1 + (fastq ? 3 + (uint64_t)w.n_qual : 0);
+  return grp_fetch_record{ text_off, text_off + l.seq_rel, text_off + l.qual_rel, out_off, l.id_len, (uint32_t)seq_from, (uint32_t)w.n_seq, (uint32_t)qual_from, (uint32_t)w.n_qual,
+                           (w.trimmed ? GRP_FETCH_REC_TRIMMED : 0u) | (l.reversed ? GRP_FETCH_REC_REVERSED : 0u) };
 }
 
 } // namespace gr

@@ -1,6 +1,6 @@
 """GPU: grp_records_fetch (csrc/grp_inflate.inc, k_emit_records) at the C ABI — records of a compressed input inflated,
 cut and formatted on the device.  The expectation is a Python model of what the host program's commit_sink writes for an
-inserted read (csrc/host/gr_path.cpp) and the host library's gr_sum_phred of the quality characters it writes: bytes are
+inserted read (csrc/host/gr_writer.cpp) and the host library's gr_sum_phred of the quality characters it writes: bytes are
 compared as bytes, sums by their 64 bits.  Every refusal here is one of the table checks or a unit with a wrong CRC32:
 both are turned down before the emit kernel is launched, and the caller's buffer is untouched."""
 import struct
@@ -37,7 +37,7 @@ def hl(native):
     return h
 
 
-# ---- the model: commit_sink (gr_path.cpp) --------------------------------------------------------------------------------
+# ---- the model: commit_sink (gr_writer.cpp) ------------------------------------------------------------------------------
 def slice_of(seq_len, qual_len, trim, tile=1):
     """(off, n_seq, qoff, n_qual) of a committed read; trim = None (inserted whole) or (trim_start, trim_end, num_tiles)"""
     off, n_seq, n_qual = 0, seq_len, qual_len

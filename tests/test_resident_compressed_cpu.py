@@ -1,5 +1,5 @@
 """CPU: GRP_RESIDENT=all — the reads of BGZF, plain gzip and BAM inputs kept between the passes, the written records fetched
-through their inflatable units (csrc/host/gr_path.cpp: Deferred; gr_units.hpp).  The product's whole host program runs over
+through their inflatable units (csrc/host/gr_writer.cpp: Deferred; gr_units.hpp).  The product's whole host program runs over
 the oracle engine (tests/resident_runner.py), once with zlib stand-ins for the two inflate entry points only — the host's own
 fetch — and once with a Python restatement of grp_records_fetch.  Every run's files and verbose counters, "Average Phred"
 included, are those of the run on the FASTQ twin and of the same input with GRP_RESIDENT=off."""

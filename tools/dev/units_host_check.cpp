@@ -1,10 +1,14 @@
 // Developer check of csrc/host/gr_units.hpp under the sanitizers, without a device and outside Python:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include tools/dev/units_host_check.cpp -o /tmp/units_host_check && /tmp/units_host_check
 // Random files cut into units — empty ones in the middle, at the front and at the end — and random records in them:
-// locate_units against a linear search, and the walk gr_path.cpp's flush makes over its list of pending records (runs of
+// locate_units against a linear search, and the walk gr_writer.cpp's flush makes over its list of pending records (runs of
 // records of one file; records of plain files in between are not planned; a compressed file's run goes through plan_fetch
 // call after call, under small caps) against the bytes: every record's text must be found at its offset in the
 // concatenated text of the units of its call, every unit at most once per call and in file order.
+// Then the mapping from a stored record and its decision to what is written of it (written_slice, fetch_record_of): every
+// field and the byte count against values written down by hand from include/grpath_ingest.h (grp_fetch_record and the size
+// of a record's bytes) — forward and reversed, whole and trimmed, a trim that ends at the last tile, fewer qualities than
+// bases and none at the slice, records of no base and of one, FASTA and FASTQ.
 #include "../../goldrush_amd/csrc/host/gr_units.hpp"
 
 #include <cstdio>
@@ -21,6 +25,61 @@ using namespace gr;
       std::exit(1);                                                                                                    \
     }                                                                                                                  \
   } while (0)
+
+// one case of the mapping: the record at `text_off` of the fetched text, its bytes at out_off 70; `want` in the order of the
+// struct's fields from id_len on (out_off and the three text offsets follow from the arguments), and the byte counts
+struct SliceCase
+{
+  uint32_t seq_len, qual_len;
+  uint8_t reversed;
+  uint32_t kind, trim_start, trim_end, num_tiles;
+  uint32_t seq_from, n_seq, qual_from, n_qual, flags;
+  uint64_t fasta_bytes, fastq_bytes;
+};
+
+static void
+check_slices()
+{
+  // tiles of 10 bases; a record of 47 bases has 4 of them.  id "read1" (5 bytes): '@' id "_untrimmed\n" is 1 + 5 + 11 bytes,
+  // "_trimmed\n" 9; then the bases and '\n'; FASTQ: "+\n", the qualities and '\n' more
+  const SliceCase cases[] = {
+    // forward: whole; tiles 1-2 of 4: bases [10, 30); tiles 2-3, the last tile: to the end, bases [20, 47)
+    { 47, 47, 0, 2, 0, 0, 4, /**/ 0, 47, 0, 47, 0, /**/ 65, 115 },
+    { 47, 47, 0, 4, 1, 2, 4, /**/ 10, 20, 10, 20, 1, /**/ 36, 59 },
+    { 47, 47, 0, 4, 2, 3, 4, /**/ 20, 27, 20, 27, 1, /**/ 43, 73 },
+    // reversed: the same slices of the twin are the stored ranges [0, 47), [17, 37), [0, 27), written backwards
+    { 47, 47, 1, 2, 0, 0, 4, /**/ 0, 47, 0, 47, 2, /**/ 65, 115 },
+    { 47, 47, 1, 4, 1, 2, 4, /**/ 17, 20, 17, 20, 3, /**/ 36, 59 },
+    { 47, 47, 1, 4, 2, 3, 4, /**/ 0, 27, 0, 27, 3, /**/ 43, 73 },
+    // 25 qualities for 47 bases: whole — all 25; tiles 1-2 — qualities [10, 25), reversed the stored [0, 15)
+    { 47, 25, 0, 2, 0, 0, 4, /**/ 0, 47, 0, 25, 0, /**/ 65, 93 },
+    { 47, 25, 0, 4, 1, 2, 4, /**/ 10, 20, 10, 15, 1, /**/ 36, 54 },
+    { 47, 25, 1, 4, 1, 2, 4, /**/ 17, 20, 0, 15, 3, /**/ 36, 54 },
+    // 5 qualities, the slice begins behind them: none, from the end of the qualities (reversed: the stored front)
+    { 47, 5, 0, 4, 1, 2, 4, /**/ 10, 20, 5, 0, 1, /**/ 36, 39 },
+    { 47, 5, 1, 4, 1, 2, 4, /**/ 17, 20, 0, 0, 3, /**/ 36, 39 },
+    { 47, 5, 0, 4, 2, 3, 4, /**/ 20, 27, 5, 0, 1, /**/ 43, 46 },
+    // no base; one base
+    { 0, 0, 0, 2, 0, 0, 0, /**/ 0, 0, 0, 0, 0, /**/ 18, 21 },
+    { 0, 0, 1, 2, 0, 0, 0, /**/ 0, 0, 0, 0, 2, /**/ 18, 21 },
+    { 1, 1, 0, 2, 0, 0, 0, /**/ 0, 1, 0, 1, 0, /**/ 19, 23 },
+    { 1, 1, 1, 2, 0, 0, 0, /**/ 0, 1, 0, 1, 2, /**/ 19, 23 },
+  };
+  for (const SliceCase& c : cases) {
+    const RecLoc l{ 3, 1000, 5, 6, c.seq_len, 60, c.qual_len, c.reversed };
+    const grp_read_decision d{ c.kind, c.num_tiles, 0, c.trim_start, c.trim_end, 0, 0, 0 };
+    const WrittenSlice w = written_slice(10, l.seq_len, l.qual_len, d);
+    for (int fastq = 0; fastq < 2; ++fastq) {
+      uint64_t size = 0;
+      const grp_fetch_record r = fetch_record_of(l, w, 300, 70, fastq != 0, &size);
+      CHECK(r.id_off == 300 && r.seq_off == 306 && r.qual_off == 360 && r.out_off == 70 && r.id_len == 5);
+      CHECK(r.seq_from == c.seq_from && r.n_seq == c.n_seq && r.qual_from == c.qual_from && r.n_qual == c.n_qual && r.flags == c.flags);
+      CHECK(size == (fastq ? c.fastq_bytes : c.fasta_bytes));
+      // the stored ranges lie inside the record
+      CHECK((uint64_t)r.seq_from + r.n_seq <= c.seq_len && (uint64_t)r.qual_from + r.n_qual <= c.qual_len);
+    }
+  }
+}
 
 struct File
 {
@@ -161,6 +220,7 @@ main()
     }
   }
   CHECK(n_located > 10000 && n_calls > 1000 && n_straddling > 1000 && n_refused > 100);
+  check_slices();
   std::printf("units_host_check ok: %zu ranges located, %zu refused, %zu fetch calls planned, %zu records in two or more units\n", n_located, n_refused, n_calls, n_straddling);
   return 0;
 }
