@@ -2,9 +2,11 @@
 // Measurement support only: lets bench.py build BASELINE-sized inputs
 // (1 M reads x 25 kb = 25 Gbases) directly in HBM in about a second.
 #include "../../include/grpath_synth.h"
+#include "grp_buffers.h"
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <string>
 
@@ -167,6 +169,46 @@ fail(const char* what, hipError_t e)
   return -3;
 }
 
+int
+refuse(const char* what)
+{
+  g_err = std::string("grp_synth_reads: ") + what;
+  return -1;
+}
+
+constexpr float SC = 1048576.0f; // 2^20: the per-base draws of k_synth are 20-bit fields
+
+// the accepted ranges of grpath_synth.h; plain host arithmetic, no HIP call.  p_del is bounded by its threshold: at
+// 2^20 every source base is deleted and a read of k_synth never completes.
+int
+check_params(const grp_synth_params& p)
+{
+  if (p.genome_len == 0 || p.genome_len > (1ULL << 63)) {
+    return refuse("genome_len must lie in 1 .. 2^63");
+  }
+  if (!std::isfinite(p.p_sub) || !std::isfinite(p.p_ins) || !std::isfinite(p.p_del) || p.p_sub < 0.0f || p.p_ins < 0.0f || p.p_del < 0.0f) {
+    return refuse("p_sub, p_ins and p_del must be finite and not negative");
+  }
+  if (p.p_sub > 1.0f || p.p_ins > 1.0f) {
+    return refuse("p_sub and p_ins must not exceed 1");
+  }
+  if (!(p.p_del * SC < SC) || (uint32_t)(p.p_del * SC) >= (1u << 20)) {
+    return refuse("p_del must stay below 1 (a read of only deleted bases never completes)");
+  }
+  if (!std::isfinite(p.repeat_frac) || p.repeat_frac < 0.0f) {
+    return refuse("repeat_frac must be finite and not negative");
+  }
+  return 0;
+}
+
+template<typename T>
+hipError_t
+upload(DevBuf<T>& d, const T* host, size_t n)
+{
+  const hipError_t e = d.reset(n);
+  return e != hipSuccess ? e : hipMemcpy(d.p, host, n * sizeof(T), hipMemcpyHostToDevice);
+}
+
 } // namespace
 
 extern "C" {
@@ -187,38 +229,36 @@ grp_synth_reads(const grp_synth_params* p,
                 void* d_out,
                 void* stream_v)
 {
-  if (!p || !start || !len || !strand || !word_off || !d_out || p->genome_len == 0) {
-    g_err = "grp_synth_reads: bad argument";
-    return -1;
+  // every refusal comes before the first HIP call: a refused call touches neither the device nor d_out
+  if (!p || !start || !len || !strand || !word_off || !d_out) {
+    return refuse("bad argument");
+  }
+  if (const int rc = check_params(*p)) {
+    return rc;
   }
   if (n == 0) {
     return 0;
   }
   hipStream_t stream = (hipStream_t)stream_v;
-  uint64_t *d_start = nullptr, *d_off = nullptr;
-  uint32_t* d_len = nullptr;
-  uint8_t* d_strand = nullptr;
+  // owners (grp_buffers.h): every return below frees what was allocated
+  DevBuf<uint64_t> d_start, d_off;
+  DevBuf<uint32_t> d_len;
+  DevBuf<uint8_t> d_strand;
   hipError_t e;
-  if ((e = hipMalloc(&d_start, (size_t)n * 8)) != hipSuccess) return fail("hipMalloc", e);
-  if ((e = hipMalloc(&d_off, ((size_t)n + 1) * 8)) != hipSuccess) return fail("hipMalloc", e);
-  if ((e = hipMalloc(&d_len, (size_t)n * 4)) != hipSuccess) return fail("hipMalloc", e);
-  if ((e = hipMalloc(&d_strand, (size_t)n)) != hipSuccess) return fail("hipMalloc", e);
-  if ((e = hipMemcpy(d_start, start, (size_t)n * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy", e);
-  if ((e = hipMemcpy(d_off, word_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy", e);
-  if ((e = hipMemcpy(d_len, len, (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy", e);
-  if ((e = hipMemcpy(d_strand, strand, (size_t)n, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy", e);
-  const float sc = 1048576.0f; // 2^20
+  if ((e = upload(d_start, start, (size_t)n)) != hipSuccess) return fail("upload of start", e);
+  if ((e = upload(d_off, word_off, (size_t)n + 1)) != hipSuccess) return fail("upload of word_off", e);
+  if ((e = upload(d_len, len, (size_t)n)) != hipSuccess) return fail("upload of len", e);
+  if ((e = upload(d_strand, strand, (size_t)n)) != hipSuccess) return fail("upload of strand", e);
   // a grid holds fewer than 2^32 work-items: slices of 2^22 reads
   for (uint32_t r0 = 0; r0 < n; r0 += (1u << 22)) {
     const uint32_t nr = n - r0 < (1u << 22) ? n - r0 : (1u << 22);
-    k_synth<<<dim3(nr), dim3(T), 0, stream>>>(*p, d_start, d_len, d_strand, d_off, static_cast<uint32_t*>(d_out), (uint32_t)(p->p_sub * sc), (uint32_t)(p->p_ins * sc), (uint32_t)(p->p_del * sc), r0);
-    if ((e = hipGetLastError()) != hipSuccess) return fail("k_synth launch", e);
+    k_synth<<<dim3(nr), dim3(T), 0, stream>>>(*p, d_start, d_len, d_strand, d_off, static_cast<uint32_t*>(d_out), (uint32_t)(p->p_sub * SC), (uint32_t)(p->p_ins * SC), (uint32_t)(p->p_del * SC), r0);
+    if ((e = hipGetLastError()) != hipSuccess) {
+      (void)hipStreamSynchronize(stream); // the slices already launched still read the arrays freed on return
+      return fail("k_synth launch", e);
+    }
   }
   if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail("k_synth", e);
-  (void)hipFree(d_start);
-  (void)hipFree(d_off);
-  (void)hipFree(d_len);
-  (void)hipFree(d_strand);
   return 0;
 }
 

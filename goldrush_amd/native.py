@@ -899,6 +899,7 @@ def synth_reads_range(plan, lo: int, hi: int, genome_len: int, genome_seed: int 
     p = grp_synth_params(genome_len, genome_seed, error_seed, p_sub, p_ins, p_del, repeat_frac)
     rc = lib.grp_synth_reads(C.byref(p), _ptr(st), _ptr(ln), _ptr(sd), _ptr(wo), n, C.c_void_p(d), C.c_void_p(stream))
     if rc != 0:
+        lib.grp_synth_free(C.c_void_p(d))
         raise GrpError(rc, lib.grp_synth_last_error().decode())
     return DeviceReads(d, wo, ln)
 
@@ -913,5 +914,6 @@ def synth_reads(n_reads: int, genome_len: int, genome_seed: int = 1, error_seed:
     p = grp_synth_params(genome_len, genome_seed, error_seed, p_sub, p_ins, p_del, repeat_frac)
     rc = lib.grp_synth_reads(C.byref(p), _ptr(start), _ptr(lens), _ptr(strand), _ptr(word_off), n_reads, C.c_void_p(d), C.c_void_p(stream))
     if rc != 0:
+        lib.grp_synth_free(C.c_void_p(d))
         raise GrpError(rc, lib.grp_synth_last_error().decode())
     return DeviceReads(d, word_off, lens)

@@ -11,7 +11,32 @@
  * base is deleted with probability p_del, otherwise emitted (substituted by a
  * different base with probability p_sub) and followed by one random inserted
  * base with probability p_ins.  Exactly len[r] bases are produced per read and
- * written 2-bit packed (grpath.h encoding) at word_off[r].
+ * written 2-bit packed (grpath.h encoding) at word_off[r]: (len[r] + 15) / 16
+ * words, the bits behind the last base zero, and no other word of the output.
+ * On the other strand the source is walked downwards from start[r] (which is
+ * its first base, complemented), wrapping below 0.  A read of more bases than
+ * the genome walks round it again.  An insertion that the end of the read leaves
+ * no room for is dropped.
+ *
+ * The errors of a read are a function of error_seed, of the read's index r
+ * INSIDE THE CALL and of the source base's index inside the read, and of
+ * nothing else: the same plan cut into other batches gives other reads, and read
+ * j of every batch of a run has the same error pattern (the same source bases
+ * deleted, substituted, followed by an insertion) as read j of every other batch.
+ * Genome, start, length and strand do not enter it.
+ *
+ * Accepted ranges (anything else is refused with -1 before the device is
+ * touched; grp_synth_last_error says why):
+ *   genome_len     1 .. 2^63
+ *   p_sub, p_ins   finite, 0 .. 1.  A probability acts as the 20-bit threshold
+ *                  (uint32)(p * 2^20): below 2^-20 it is 0, and 1 is "always".
+ *   p_del          finite, >= 0 and (uint32)(p_del * 2^20) < 2^20, i.e. below 1:
+ *                  a read of deleted bases alone would never be complete.  The
+ *                  cost of a read grows as 1 / (1 - p_del).
+ *   repeat_frac    finite, >= 0; 1.5 * repeat_frac is clamped to 1, so from 2/3
+ *                  on every slot is a repeat copy.
+ * tests/synth_model.py restates the model on the host; the kernel is held to it
+ * bit for bit (tests/test_gpu_synth.py).
  */
 #ifndef GRPATH_SYNTH_H
 #define GRPATH_SYNTH_H
@@ -40,8 +65,12 @@ typedef struct
 /*
  * d_packed_out: device memory of word_off[n_reads] 32-bit words (caller
  * allocates; e.g. a torch tensor or grp_synth_alloc).  start / len / strand /
- * word_off are HOST arrays.  `stream` is a hipStream_t (NULL = default stream);
- * the call returns after the kernel has completed.  Returns 0 on success.
+ * word_off are HOST arrays (word_off of n_reads + 1 entries; read r is written
+ * at word_off[r], wherever the caller put it).  `stream` is a hipStream_t (NULL
+ * = default stream); the call returns after the kernel has completed.  Returns 0
+ * on success, -1 for an argument outside the accepted ranges (nothing was
+ * written), -3 for a HIP error; the device arrays of the call are released on
+ * every return.
  */
 int grp_synth_reads(const grp_synth_params* p,
                     const uint64_t* start,
