@@ -68,6 +68,21 @@ def test_bgzf_input_gives_the_plain_files_outputs(cli, inputs, plain, tmp_path_f
         assert max(n) == n_members and all(x <= n_members for x in n), n
 
 
+def test_a_file_written_by_libdeflate_gives_the_plain_files_outputs(cli, tmp_path_factory):
+    """tests/golden/tiny_libdeflate.fq.gz: tiny.fq as bgzip writes it (htslib's encoder is libdeflate, not zlib)"""
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    fq, gz = os.path.join(gold, "tiny.fq"), os.path.join(gold, "tiny_libdeflate.fq.gz")
+    n_members = len(B.walk_members(open(gz, "rb").read())[0])
+    ro, fo = _run(cli, tmp_path_factory, SILVER, fq)
+    rp, fp = _run(cli, tmp_path_factory, SILVER, gz)
+    assert ro.returncode == rp.returncode == 0, rp.stderr[-2000:]
+    assert fp == fo and fo
+    assert _log(rp, gz) == _log(ro, fq)
+    assert set(_traced(ro)) == {0}
+    n = _traced(rp)
+    assert max(n) == n_members == 4 and all(0 < x <= n_members for x in n), n
+
+
 def test_switch_selects_the_zlib_path(cli, inputs, plain, tmp_path_factory):
     rp, files = _run(cli, tmp_path_factory, SILVER, inputs[0]["bgzf"], GRP_BGZF="off")
     assert rp.returncode == 0, rp.stderr[-2000:]

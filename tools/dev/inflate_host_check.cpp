@@ -11,6 +11,13 @@
 // zlib on its own (inflatePrime + inflateSetDictionary) and by the decoder, at two alignments of the output, with buffers
 // that end where the engine's end; then damaged forms of it (flipped bits, text_len +- 1, n_bits off, a shorter history,
 // the other flag) must be refused, fail the CRC32 or give the same text — and touch nothing outside their buffers.
+// The generated corpus (tests/deflate_gen.py: random codes up to 15 bits, the match sweep, the threshold members, the
+// hand-made segments) and the libdeflate fixtures, good and refused — what tests/test_gpu_inflate_generated.py gives the device;
+// tests/test_deflate_gen_cpu.py runs the same three commands on a build without the sanitizers:
+//   python tools/dev/inflate_host_cases.py --generated /tmp/inflate_gen
+//   /tmp/inflate_host_check /tmp/inflate_gen/members.bin
+//   /tmp/inflate_host_check --segments /tmp/inflate_gen/segments.bin
+//   /tmp/inflate_host_check --gzip /tmp/inflate_gen/gzip/*.gz
 #define GRP_INFLATE_HOST
 #include <cstdint>
 #include <cstdio>
@@ -26,6 +33,12 @@
 // file: u32 n; per case: u32 comp_len, u32 text_len, u32 expect_ok, u32 crc, u32 pre (bytes in front of payload), payload(pre+comp_len), text
 static InfLds g_s;
 static CrcLds g_cs;
+
+// a case file that ends early is an error, not a case
+static void must_read(void* to, size_t size, size_t n, FILE* f)
+{
+  if (fread(to, size, n, f) != n) { printf("the case file ends early\n"); exit(2); }
+}
 
 // the segment by zlib alone: the bits from comp_bit on with the history as the dictionary
 static bool zlib_segment(const uint8_t* file, size_t n_file, const gr::GzSegment& g, const uint8_t* dict, std::vector<char>& out)
@@ -133,25 +146,65 @@ static int gzip_main(int argc, char** argv)
   return bad != 0;
 }
 
+// hand-made segments (inflate_host_cases.py: write_segments): each with its own file and a history at a given alignment
+static int segments_main(const char* path)
+{
+  FILE* f = fopen(path, "rb");
+  if (!f) { printf("%s: cannot open\n", path); return 2; }
+  uint32_t n = 0; must_read(&n, 4, 1, f);
+  uint32_t tabs[1056]; crc_tables(tabs);
+  int bad = 0;
+  for (uint32_t c = 0; c < n; ++c) {
+    uint64_t q[2]; uint32_t h[7]; must_read(q, 8, 2, f); must_read(h, 4, 7, f);
+    const uint32_t dict_len = h[0], text_len = h[1], crc = h[2], flags = h[3], ok = h[4], file_len = h[5], pre = h[6];
+    // the engine's buffers: the bytes, 8 bytes of zero padding, nothing behind
+    std::vector<uint32_t> compw((file_len + 8 + 3) / 4, 0), dictw((pre + dict_len + 8 + 3) / 4, 0);
+    uint8_t* comp = (uint8_t*)compw.data(); uint8_t* dict = (uint8_t*)dictw.data();
+    must_read(comp, 1, file_len, f); must_read(dict, 1, pre + dict_len, f);
+    std::vector<char> text(text_len + 1), outw((size_t)text_len + 3 + 1);
+    must_read(text.data(), 1, text_len, f);
+    const grp_gzip_segment e{ q[0], q[1], pre, dict_len, text_len, crc, flags };
+    for (int mis = 0; mis < 2; ++mis) {
+      char* out = outw.data() + (mis ? 3 : 0);
+      memset(outw.data(), 0x55, outw.size());
+      memset(&g_s, 0xAA, sizeof g_s);
+      const uint32_t st = inf_entry(g_s, comp, dict, e, out);
+      if ((uint8_t)out[text_len] != 0x55) { printf("segment %u: wrote behind the text\n", c); ++bad; }
+      if (ok) {
+        if (st != 0 || memcmp(out, text.data(), text_len) != 0) { printf("segment %u mis %d: status %u (%s) or text differs\n", c, mis, st, INF_STATUS_TEXT[st]); ++bad; continue; }
+        if (crc_member(g_cs, tabs, out, text_len) != crc) { printf("segment %u: crc differs\n", c); ++bad; }
+      } else if (st == 0) { printf("segment %u: accepted a bad segment\n", c); ++bad; }
+      else if (mis == 0) { printf("segment %u refused: %s\n", c, INF_STATUS_TEXT[st]); }
+    }
+  }
+  fclose(f);
+  printf("%u segments, %d bad\n", n, bad);
+  return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
   if (argc >= 3 && !strcmp(argv[1], "--gzip")) {
     return gzip_main(argc, argv);
   }
+  if (argc >= 3 && !strcmp(argv[1], "--segments")) {
+    return segments_main(argv[2]);
+  }
   FILE* f = fopen(argv[1], "rb");
-  uint32_t n; fread(&n, 4, 1, f);
+  if (!f) { printf("%s: cannot open\n", argv[1]); return 2; }
+  uint32_t n; must_read(&n, 4, 1, f);
   static InfLds s; static CrcLds cs;
   uint32_t tabs[1056]; crc_tables(tabs);
   int bad = 0;
   for (uint32_t c = 0; c < n; ++c) {
-    uint32_t h[5]; fread(h, 4, 5, f);
+    uint32_t h[5]; must_read(h, 4, 5, f);
     const uint32_t comp_len = h[0], text_len = h[1], ok = h[2], crc = h[3], pre = h[4];
     // words must be readable up to the aligned end: pad
     std::vector<uint32_t> compw((pre + comp_len + 3) / 4 + 1);
     uint8_t* comp = (uint8_t*)compw.data();
-    fread(comp, 1, pre + comp_len, f);
+    must_read(comp, 1, pre + comp_len, f);
     std::vector<char> text(text_len + 1), outw(text_len + 8 + 3);
-    fread(text.data(), 1, text_len, f);
+    must_read(text.data(), 1, text_len, f);
     memset(&s, 0xAA, sizeof s);
     for (int mis = 0; mis < 2; ++mis) {
       char* out = outw.data() + (mis ? 3 : 0);
