@@ -22,6 +22,7 @@
 #include "host/gr_tile_geom.hpp"
 #include "host/gr_tiles_core.hpp"
 #include "host/gr_bam.hpp"
+#include "host/gr_gather_word.hpp"
 
 #include "../../include/grpath.h"
 #include "../../include/grpath_ingest.h"
@@ -341,6 +342,13 @@ struct grp_ctx : CtxStreams
   mutable std::string err;
 };
 
+// a source batch of grp_reads_gather as its kernel sees it (grp_gather.inc)
+struct GatherSrc
+{
+  const uint32_t* packed;
+  const uint64_t* word_off;
+};
+
 struct grp_reads
 {
   grp_ctx* ctx = nullptr;
@@ -363,6 +371,9 @@ struct grp_reads
   DevBuf<uint8_t> d_slab;
   std::vector<uint64_t> h_word_off, h_seq_off;
   std::vector<uint32_t> h_tile_read, h_chunk_read;
+  // grp_reads_gather: the slices and the sources' addresses, likewise
+  std::vector<grp_read_slice> h_slices;
+  std::vector<GatherSrc> h_srcs;
   DevReads dev{};
 };
 
@@ -3264,6 +3275,7 @@ grp_dev_hooks(void)
 #include "grp_verify.inc"
 #include "grp_ingest.inc"
 #include "grp_inflate.inc"
+#include "grp_gather.inc"
 #include "grp_ntcard.inc"
 #include "grp_comm.inc"
 #ifdef GRP_DEV_HOOKS // priced-and-rejected prototypes, measurement only (make DEV=1; include/grpath_dev.h)

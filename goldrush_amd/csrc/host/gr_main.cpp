@@ -114,5 +114,9 @@ main(int argc, char** argv)
   ext.bam_parse_ex = [](void* c, const char* bytes, uint64_t n, int fin, uint32_t accept, void** out, uint64_t* nrec, uint64_t* used, uint64_t* bad, uint64_t* skipped) {
     return grp_bam_parse_ex(static_cast<grp_ctx*>(c), bytes, n, fin, accept, reinterpret_cast<grp_fastq**>(out), nrec, used, bad, skipped);
   };
+  ext.reads_gather = [](void* c, const void* const* srcs, uint32_t n_srcs, const grp_read_slice* slices, uint32_t n_slices, void** out) {
+    return grp_reads_gather(static_cast<grp_ctx*>(c), reinterpret_cast<const grp_reads* const*>(srcs), n_srcs, slices, n_slices, reinterpret_cast<grp_reads**>(out));
+  };
+  ext.rewind = [](void* c) { return grp_rewind(static_cast<grp_ctx*>(c)); };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

@@ -51,7 +51,8 @@ process_options(Opts& o, int argc, char** argv)
 {
   const struct option longopts[] = { { "debug", no_argument, &o.debug, 1 },       { "verbose", no_argument, &o.verbose, 1 },
                                      { "silver_path", no_argument, &o.silver_path, 1 }, { "help", no_argument, &o.help, 1 },
-                                     { "ntcard", no_argument, &o.ntcard, 1 },     { nullptr, 0, nullptr, 0 } };
+                                     { "ntcard", no_argument, &o.ntcard, 1 },     { "golden_path", required_argument, nullptr, 1000 },
+                                     { nullptr, 0, nullptr, 0 } };
   optind = 0; // allow repeated parsing inside one process
   int c, idx = 0;
   while ((c = getopt_long(argc, argv, "a:b:d:f:g:h:i:j:k:m:M:o:r:s:t:u:w:x:p:P:H:", longopts, &idx)) != -1) {
@@ -81,6 +82,10 @@ process_options(Opts& o, int argc, char** argv)
       case 'u': o.unassigned_min = strtoul(optarg, nullptr, 10); break;
       case 'w': o.weight = strtoul(optarg, nullptr, 10); break;
       case 'x': o.threshold = strtoul(optarg, nullptr, 10); break;
+      case 1000: // --golden_path PREFIX (what it needs beside it is checked where the ranks are known: gr_path.cpp)
+        o.golden_path = 1;
+        o.golden_prefix = optarg;
+        break;
       default: return EXIT_FAILURE;
     }
   }

@@ -33,6 +33,10 @@ struct Opts
   std::string seed_preset;    // -s
   std::string filter_file;    // -f
   int help = 0, ntcard = 0, silver_path = 0, verbose = 0, debug = 0;
+  // --golden_path PREFIX (not the reference's): behind the silver paths, the golden path of the same command — the second
+  // goldrush-path process of the GoldRush pipeline, which reads the silver files with -m 0 and writes PREFIX.fa (gr_path.cpp)
+  int golden_path = 0;
+  std::string golden_prefix;
 };
 
 void print_usage(const std::string& progname);

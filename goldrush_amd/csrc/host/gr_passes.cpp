@@ -1,6 +1,7 @@
 // The passes over the input (gr_passes.hpp): goldrush_path.cpp:1109-1112, 79-107, 235-339, 1210-1256.
 #include "gr_passes.hpp"
 #include "gr_fastq.hpp"
+#include "gr_golden.hpp"
 #include "gr_params.hpp"
 
 #include <cmath>
@@ -172,11 +173,6 @@ calc_min_phred_threshold(PathRun& run)
 
 namespace {
 
-struct FillCounts
-{
-  size_t num_reads = 0, num_passed_reads = 0, by_phred = 0, by_delta = 0, by_length = 0, by_bases = 0;
-};
-
 // The read filters of the fill pass over one batch (goldrush_path.cpp:261-301): the records that pass go to `sel`, and, the
 // reads staying on the device, what the classification pass needs of them to `keep`.  Returns the records behind the last
 // selected one.
@@ -232,6 +228,34 @@ filter_batch(PathRun& run, Resident& res, const Batch& b, FillCounts& n, std::ve
 }
 
 } // namespace
+
+// behind the fill pass's loop: its --verbose counts; 1 (said): no read passed; -2: none passed because the input could not
+// be read (the caller reports that); -1: go on
+int
+say_fill_counts(const PathRun& run, const FillCounts& n)
+{
+  const Opts& opt = run.opt;
+  if (opt.verbose) {
+    std::cerr << "num_passed_reads: " << n.num_passed_reads << "\n"
+              << "num_reads: " << n.num_reads << "\n"
+              << "num_reads - num_passed_reads: " << n.num_reads - n.num_passed_reads << "\n"
+              << "num_reads - num_passed_reads / num_reads: " << floor((double)(n.num_reads - n.num_passed_reads) / n.num_reads) << "\n"
+              << "num_reads_skipped_by_phred: " << n.by_phred << "\n"
+              << "num_reads_skipped_by_delta: " << n.by_delta << "\n"
+              << "num_reads_skipped_by_length: " << n.by_length << "\n"
+              << "num_reads_skipped_by_invalid_bases: " << n.by_bases << "\n"
+              << "Total reads skipped: " << n.by_phred + n.by_delta + n.by_length + n.by_bases << std::endl;
+  }
+  if (n.num_passed_reads == 0) {
+    if (input_failed()) {
+      return -2; // (not an input without usable reads: one that could not be read — the caller reports that)
+    }
+    std::cerr << "Error: no reads passed the Phred score and min length requirements\n"
+              << "Try again with a lower Phred threshold or lower min length" << std::endl;
+    return 1;
+  }
+  return -1;
+}
 
 // goldrush_path.cpp:235-339
 int
@@ -314,24 +338,9 @@ fill_bit_vector(PathRun& run, Resident& res)
   if (prev) {
     run.vt.reads_free(prev);
   }
-  if (opt.verbose) {
-    std::cerr << "num_passed_reads: " << n.num_passed_reads << "\n"
-              << "num_reads: " << n.num_reads << "\n"
-              << "num_reads - num_passed_reads: " << n.num_reads - n.num_passed_reads << "\n"
-              << "num_reads - num_passed_reads / num_reads: " << floor((double)(n.num_reads - n.num_passed_reads) / n.num_reads) << "\n"
-              << "num_reads_skipped_by_phred: " << n.by_phred << "\n"
-              << "num_reads_skipped_by_delta: " << n.by_delta << "\n"
-              << "num_reads_skipped_by_length: " << n.by_length << "\n"
-              << "num_reads_skipped_by_invalid_bases: " << n.by_bases << "\n"
-              << "Total reads skipped: " << n.by_phred + n.by_delta + n.by_length + n.by_bases << std::endl;
-  }
-  if (n.num_passed_reads == 0) {
-    if (input_failed()) {
-      return -1; // (not an input without usable reads: one that could not be read — the caller reports that)
-    }
-    std::cerr << "Error: no reads passed the Phred score and min length requirements\n"
-              << "Try again with a lower Phred threshold or lower min length" << std::endl;
-    return 1;
+  const int counted = say_fill_counts(run, n);
+  if (counted != -1) {
+    return counted == -2 ? -1 : counted;
   }
   const double ts0 = trace ? now_s() : 0.0;
   if (run.vt.sync(run.ctx) != GRP_OK) {
@@ -426,6 +435,9 @@ classify_resident(PathRun& run, Resident& res, Classifier& cls, SinkState& sink)
       rc = cls.run(rb.reads, rb.lens.data(), idx[a], (uint32_t)(e - a), sb.data(), e == idx.size() ? trailing : 0u, finished);
       a = e;
     }
+    if (sink.golden) {
+      sink.golden->cut(run, rb.reads); // (the settle point: no window is parked, every commit of the batch is written)
+    }
     run.vt.reads_free(rb.reads);
     rb.reads = nullptr;
     if (rc != GRP_OK) {
@@ -485,6 +497,9 @@ classify_source(PathRun& run, Classifier& cls, SinkState& sink)
     const int rc = cls.run(h, lens.data(), 0, (uint32_t)sel.size(), skipped_before.data(), skipped, finished);
     if (opt.debug && rc == GRP_OK && !finished) {
       debug_skipped(sink, sink.skipped_done, skipped_recs.size()); // the records behind the batch's last classified read
+    }
+    if (sink.golden) {
+      sink.golden->cut(run, h);
     }
     run.vt.reads_free(h);
     if (rc != GRP_OK) {

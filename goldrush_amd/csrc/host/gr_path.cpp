@@ -4,9 +4,11 @@
 //
 // Same flags, same stderr messages, same output files (<prefix>_<n>.fq in
 // --silver_path mode, <prefix>.fa otherwise), same exit codes.
-// Here: options, ranks, the engine, the banner and the passes in order (gr_passes.hpp, over gr_resident.hpp and gr_writer.hpp).
+// Here: options, ranks, the engine, the banner and the passes in order (gr_passes.hpp, over gr_resident.hpp and gr_writer.hpp);
+// and, not the reference's, --golden_path: that flow twice in one process, the golden path behind the silver paths (gr_golden.hpp).
 #include "../../../include/grpath_host.h"
 #include "gr_fastq.hpp"
+#include "gr_golden.hpp"
 #include "gr_opts.hpp"
 #include "gr_params.hpp"
 #include "gr_passes.hpp"
@@ -15,6 +17,7 @@
 #include <cstddef>
 #include <cstring>
 #include <iomanip>
+#include <sys/stat.h>
 #include <unistd.h>
 #if defined(_OPENMP)
 #include <omp.h>
@@ -56,13 +59,22 @@ struct RunGuard // the engine, and what a resident run holds of it and of the fi
 {
   PathRun& run;
   Resident& res;
+  GoldenCarry *collect, *from; // --golden_path: the stage fills one, or is built from one (gr_golden.hpp)
   ~RunGuard()
   {
     res.drop(run);
     res.close_files();
-    if (run.ctx) {
+    for (GoldenCarry* g : { collect, from }) {
+      if (g && !(g == collect && g->on && g->done)) {
+        g->free_parts(run);
+      }
+    }
+    if (run.ctx && collect && collect->on && collect->done) {
+      collect->ctx = run.ctx; // the first stage ended well: its engine goes to the second, with the parts
+    } else if (run.ctx) {
       run.vt.destroy(run.ctx);
     }
+    run.ctx = nullptr;
   }
 };
 
@@ -105,6 +117,17 @@ read_options(PathRun& run, int argc, char** argv, Quiet& quiet)
   const int ec = process_options(run.opt, argc, argv);
   if (ec >= 0) {
     return ec;
+  }
+  if (run.opt.golden_path) {
+    // --golden_path: refused here, in front of the first pass, where it cannot run
+    const char* why = !run.opt.silver_path            ? "it needs --silver_path: the golden path is built from the silver paths of the same command"
+                      : run.opt.golden_prefix.empty() ? "the prefix of the golden path's file is empty"
+                      : run.world > 1                 ? "several ranks are out of scope of the option: it runs on one rank (GRP_WORLD=1)"
+                                                      : nullptr;
+    if (why) {
+      std::cerr << "goldrush-path: --golden_path: " << why << std::endl;
+      return 1;
+    }
   }
   // every -i is an input, a ".fofn" list stands for the files it names (gr_opts.hpp); no -i at all: the reference's empty name
   std::string bad_list;
@@ -179,6 +202,9 @@ say_banner(PathRun& run, uint64_t filter_size)
     }
   }
   run.out.open(run.rank != 0 ? std::string("/dev/null") : opt.silver_path ? opt.prefix_file + "_1.fq" : opt.prefix_file + ".fa");
+  if (run.rank == 0) {
+    run.out_files.push_back(opt.silver_path ? opt.prefix_file + "_1.fq" : opt.prefix_file + ".fa");
+  }
   const double s_time = now_s();
   std::cerr << "allocating bit vector" << std::endl;
   std::cerr << "m_filterSize: " << filter_size << std::endl;
@@ -213,38 +239,17 @@ classifier_params(const PathRun& run)
   return cp;
 }
 
-} // namespace
-} // namespace gr
-
-extern "C" int
-gr_path_main(int argc, char** argv, const grp_engine_vt* vt)
+// One run of the program behind its options: `run` holds the engine's tables, the ranks, the options and the files to
+// read; everything else — the engine, the reads kept on the device, the classifier, the sink — lives and dies in here.
+// The exit code: 0 also where the reference does exit(0) inside silver_path_check.
+// --golden_path: `collect`, the first stage, remembers what it writes; `from`, the second stage on the device route, is built
+// from what the first remembered — its engine rewound, its Phred median and its fill from the kept records.
+int
+run_stage(PathRun& run, void* shm_h, GoldenCarry* collect = nullptr, GoldenCarry* from = nullptr)
 {
-  return gr_path_main_ext(argc, argv, vt, nullptr);
-}
-
-extern "C" int
-gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engine_ext* ext)
-{
-  using namespace gr;
-  PathRun run;
   Resident res;
-  take_engine(run, vt, ext);
   Opts& opt = run.opt;
-  Quiet quiet;
-  int ec = read_options(run, argc, argv, quiet);
-  if (ec >= 0) {
-    return ec;
-  }
-  ShmGuard shm;
-  if (run.world > 1) {
-    const char* key = getenv("GRP_SHM_KEY");
-    std::string k = key && *key ? key : std::string("path_") + (getenv("MASTER_PORT") ? getenv("MASTER_PORT") : "0") + "_" + std::to_string((unsigned long)getppid());
-    shm.h = gr_shm_allgather_open(run.world, run.rank, k.c_str(), 120.0);
-    if (!shm.h) {
-      std::cerr << "goldrush-path: cannot set up the exchange between the " << run.world << " ranks (/dev/shm/grp_" << k << ")" << std::endl;
-      return 1;
-    }
-  }
+  int ec = -1;
 #if defined(_OPENMP)
   // the reference uses -j for its OpenMP regions; here it only drives the host
   // side (parsing, Phred, packing, decisions) and is capped at the machine size
@@ -263,10 +268,20 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   // pass already uses the GPU ingest); the reference's messages keep their order.
   // With --ntcard the filter size is only known after the ntcard pass.
   uint64_t filter_size = use_ntcard ? 0 : calc_optimal_size(opt.hash_universe, 1, opt.occupancy);
-  if (!create_engine(run, filter_size)) {
+  if (from) {
+    // the first stage's engine, returned to its fill state: its tables go, this stage's take their place
+    run.ctx = from->ctx;
+    from->ctx = nullptr;
+  } else if (!create_engine(run, filter_size)) {
     return 1;
   }
-  RunGuard guard{ run, res };
+  RunGuard guard{ run, res, collect, from };
+  if (from && (filter_size != from->filter_size || run.ext.rewind(run.ctx) != GRP_OK)) {
+    return run.fail_engine("returning the engine to its fill state");
+  }
+  if (collect) {
+    collect->filter_size = filter_size;
+  }
   if (run.files.size() > 1) {
     // several inputs: each is looked at before the first pass — a run does not get an hour into the fill before it finds
     // that its last file is missing
@@ -294,7 +309,7 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     // size (:1183-1184) — the engine allocates them beside the fill instead of between the passes (a hint: ignored where wrong)
     (void)run.vt.occupancy_hint(run.ctx, opt.occupancy);
   }
-  if (run.world > 1 && shm.h && gr_ranks_share_device(shm.h, run.world, run.device) == 1) {
+  if (run.world > 1 && shm_h && gr_ranks_share_device(shm_h, run.world, run.device) == 1) {
     // ranks on one device (a test box): their windows' launches must all fit it at once — the in-launch inserts of
     // the ranks' windows wait grid-wide (read at the engine's first streaming launch; an explicit setting stands)
     setenv("GRP_STREAM_WGS_PER_CU", "1", 0);
@@ -303,18 +318,20 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
     // A sharded fill needs a way to merge: RCCL inside the engine (one GPU per rank), else the
     // host-staged form (ranks sharing a device, engines without RCCL).  Every decision below is
     // taken by ALL ranks alike (flags all-gathered through /dev/shm).
-    run.shm = shm.h;
-    const int plan = gr_fill_merge_plan(&run.vt, run.ctx, shm.h, run.world, run.rank, run.device);
+    run.shm = shm_h;
+    const int plan = gr_fill_merge_plan(&run.vt, run.ctx, shm_h, run.world, run.rank, run.device);
     run.merge_rccl = plan == GR_MERGE_RCCL;
     run.shard_fill = plan != GR_MERGE_NONE;
   }
-  ec = after_pass(run, calc_min_phred_threshold(run));
+  ec = after_pass(run, from ? golden_phred_threshold(run, *from) : calc_min_phred_threshold(run));
   if (ec >= 0) {
     return ec;
   }
   say_banner(run, filter_size);
-  res.decide(run);
-  ec = after_pass(run, fill_bit_vector(run, res));
+  if (!from) {
+    res.decide(run);
+  }
+  ec = after_pass(run, from ? golden_fill(run, res, *from) : fill_bit_vector(run, res));
   if (ec >= 0) {
     return ec;
   }
@@ -341,15 +358,19 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   Classifier cls(classifier_params(run), run.vt, run.ctx);
   SinkState sink;
   sink.run = &run;
+  sink.golden = collect;
   cls.set_callbacks(commit_sink, rollover_sink, nullptr, &sink);
   if (run.world > 1) {
-    cls.set_allgather(gr_shm_allgather, shm.h);
+    cls.set_allgather(gr_shm_allgather, shm_h);
   }
   if (opt.debug) {
     cls.set_debug(debug_sink);
   }
   ec = res.on ? classify_resident(run, res, cls, sink) : classify_source(run, cls, sink);
   if (ec >= 0) {
+    if (collect) {
+      collect->done = ec == 0;
+    }
     return ec;
   }
   if (input_error()) {
@@ -366,5 +387,131 @@ gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engin
   }
   std::cerr << "assigned" << std::endl;
   std::cerr << "in " << std::setprecision(4) << std::fixed << now_s() - s_time << "\n";
+  if (collect) {
+    collect->done = true;
+  }
   return 0;
+}
+
+// --golden_path: the silver files stage A wrote that hold something, in the order `cat PREFIX_*.fq` puts them — their names
+// compared byte by byte (_1, _10, _11, _2, ... once there are ten).  An empty file adds nothing to the concatenation and is
+// left out; where every file is empty the first one stands for the empty concatenation.
+std::vector<std::string>
+silver_files(const PathRun& a)
+{
+  std::vector<std::string> all = a.out_files, files;
+  std::sort(all.begin(), all.end());
+  for (const std::string& f : all) {
+    struct stat st;
+    if (stat(f.c_str(), &st) == 0 && st.st_size > 0) {
+      files.push_back(f);
+    }
+  }
+  if (files.empty() && !all.empty()) {
+    files.push_back(all.front());
+  }
+  return files;
+}
+
+// --golden_path, stage B: the run `goldrush-path <the options of stage A without --silver_path, -M, -r, -f, -i, -p> -m 0
+// -p PREFIX -i F1 -i F2 ...` would be, in this process.  Nothing of stage A is left but the engine's function tables, the
+// switches read from the environment, the names of its files and — on the device route — what `carry` holds: a new PathRun,
+// its own reads, and std::cerr as a new process finds it (the reference leaves `fixed` and a precision of 4 on it behind
+// its first timing line).  Its engine is A's, rewound, on the device route and one of its own where the files are read back.
+int
+golden_stage(const PathRun& a, const Opts& parsed, GoldenCarry& carry)
+{
+  PathRun b;
+  b.vt = a.vt;
+  b.ext = a.ext;
+  b.bam_accept = a.bam_accept;
+  b.opt = parsed;
+  const Opts dflt;
+  b.opt.golden_path = 0;
+  b.opt.golden_prefix.clear();
+  b.opt.silver_path = 0;
+  b.opt.max_paths = dflt.max_paths;
+  b.opt.ratio = dflt.ratio;
+  b.opt.filter_file.clear();
+  b.opt.min_length = 0;
+  b.opt.prefix_file = parsed.golden_prefix;
+  b.files = silver_files(a);
+  b.opt.inputs = b.files;
+  b.opt.input = b.files.empty() ? std::string() : b.files.back();
+  if (b.files.empty()) {
+    b.files.push_back(b.opt.input);
+  }
+  b.bam_aligned.resize(b.files.size());
+  clear_input_failure();
+  std::cerr.unsetf(std::ios::floatfield);
+  std::cerr.precision(6);
+  if (carry.on && carry.recs.empty()) {
+    carry.give_up(a, "the first stage wrote no record");
+  }
+  if (!carry.on && carry.ctx) {
+    a.vt.destroy(carry.ctx);
+    carry.ctx = nullptr;
+  }
+  const bool device = carry.on && carry.ctx;
+  uint64_t n_records = carry.n_written, n_parts = carry.parts.size(), bytes_read = 0;
+  if (device) {
+    golden_order(carry, a.out_files, b.files);
+  } else {
+    std::cerr << "--golden_path: the silver reads are read back from their files: " << carry.why << std::endl;
+    for (const std::string& f : b.files) {
+      struct stat st;
+      bytes_read += stat(f.c_str(), &st) == 0 ? (uint64_t)st.st_size : 0;
+    }
+  }
+  const int ec = run_stage(b, nullptr, nullptr, device ? &carry : nullptr);
+  if (getenv("GRP_TRACE_INGEST")) {
+    std::cerr << "GRP_TRACE_INGEST golden: route=" << (device ? "device" : "files") << " records=" << n_records << " parts=" << n_parts << " batches=" << carry.n_batches << " bytes_read=" << bytes_read << std::endl;
+  }
+  return ec;
+}
+
+} // namespace
+} // namespace gr
+
+extern "C" int
+gr_path_main(int argc, char** argv, const grp_engine_vt* vt)
+{
+  return gr_path_main_ext(argc, argv, vt, nullptr);
+}
+
+extern "C" int
+gr_path_main_ext(int argc, char** argv, const grp_engine_vt* vt, const grp_engine_ext* ext)
+{
+  using namespace gr;
+  PathRun run;
+  take_engine(run, vt, ext);
+  Quiet quiet;
+  int ec = read_options(run, argc, argv, quiet);
+  if (ec >= 0) {
+    return ec;
+  }
+  ShmGuard shm;
+  if (run.world > 1) {
+    const char* key = getenv("GRP_SHM_KEY");
+    std::string k = key && *key ? key : std::string("path_") + (getenv("MASTER_PORT") ? getenv("MASTER_PORT") : "0") + "_" + std::to_string((unsigned long)getppid());
+    shm.h = gr_shm_allgather_open(run.world, run.rank, k.c_str(), 120.0);
+    if (!shm.h) {
+      std::cerr << "goldrush-path: cannot set up the exchange between the " << run.world << " ranks (/dev/shm/grp_" << k << ")" << std::endl;
+      return 1;
+    }
+  }
+  if (!run.opt.golden_path) {
+    return run_stage(run, shm.h);
+  }
+  // --golden_path: stage A is the command as written; behind it — where it ends at the end of its input or where the
+  // reference does exit(0), not behind an error — stage B reads the silver files A has written and closed
+  const Opts parsed = run.opt; // (a stage completes its own copy: the hash universe, the Phred threshold)
+  GoldenCarry carry;
+  carry.decide(run);
+  ec = run_stage(run, shm.h, &carry);
+  if (ec != 0) {
+    return ec;
+  }
+  run.out.close();
+  return golden_stage(run, parsed, carry);
 }

@@ -35,6 +35,7 @@ struct PathRun
   std::vector<std::string> seeds;
   std::unordered_set<std::string> filter_out_reads;
   std::ofstream out;
+  std::vector<std::string> out_files; // every file `out` was opened on, in order (rank 0): what a --golden_path run reads back
   uint32_t world = 1, rank = 0; // ranks sharing the classification windows (one process per GPU)
   // several ranks: every rank hashes the reads of its share of the batches into its bit vector, the
   // vectors are OR-merged before the rank build (round 3: the CLI's fill is no longer replicated)

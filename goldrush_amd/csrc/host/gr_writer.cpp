@@ -1,6 +1,7 @@
 // The classification sinks (gr_writer.hpp).
 #include "gr_writer.hpp"
 #include "gr_fastq.hpp"
+#include "gr_golden.hpp"
 #include "gr_params.hpp"
 
 namespace gr {
@@ -17,6 +18,9 @@ write_record(SinkState& st, const Batch& b, const Rec& r, const grp_read_decisio
   const char* seq = b.seq_text(r, w.off, n_seq, st.bam_seq);
   const char* qual = b.qual_text(r, w.qoff, n_qual, st.bam_qual);
   std::ofstream& o = run.out;
+  if (st.golden && run.rank == 0) {
+    st.golden->note_written(run, (uint64_t)(std::streamoff)o.tellp() + 1, b.text + r.id_off, r.id_len, w.trimmed, n_seq, qual, n_qual);
+  }
   o.put(run.opt.silver_path ? '@' : '>');
   o.write(b.text + r.id_off, (std::streamsize)r.id_len);
   o << (w.trimmed ? "_trimmed\n" : "_untrimmed\n");
@@ -165,6 +169,15 @@ Deferred::fetch_some(SinkState& st, size_t& i, size_t e)
                               (fastq ? GRP_FETCH_FASTQ : 0u) | (bam ? GRP_FETCH_BAM : 0u), out.data(), out.size(), got_sums.data(), &bad_unit, &bad_rec) != GRP_OK) {
       return engine_says("the written records could not be fetched");
     }
+    if (st.golden) {
+      // the formatted records are in hand: "@<id>_[un]trimmed\n<bases>\n+\n<qualities>\n"
+      const uint64_t at = (uint64_t)(std::streamoff)run.out.tellp();
+      for (const grp_fetch_record& fr : recs) {
+        const bool trimmed = (fr.flags & GRP_FETCH_REC_TRIMMED) != 0;
+        const char* id = out.data() + fr.out_off + 1;
+        st.golden->note_written(run, at + fr.out_off + 1, id, fr.id_len, trimmed, fr.n_seq, id + fr.id_len + (trimmed ? 9 : 11) + fr.n_seq + 3, fr.n_qual);
+      }
+    }
     run.out.write(out.data(), (std::streamsize)out.size());
     sums.insert(sums.end(), got_sums.begin(), got_sums.end());
     n_out_bytes += out.size();
@@ -227,6 +240,9 @@ commit_sink(void* user, const gr_commit* c)
   if ((c->dec.kind != DEC_INSERT_WHOLE && c->dec.kind != DEC_INSERT_TRIMMED) || input_failed()) {
     return 0.0;
   }
+  if (st.golden && st.run->rank == 0) {
+    st.golden->note_commit(*st.run, c->read, st.resident ? st.resident->loc[c->read].seq_len : (uint32_t)st.batch->rec[(*st.sel)[c->read]].seq_len, c->dec);
+  }
   if (st.resident && st.deferred) {
     // (ranks other than 0 write nothing and print nothing: nothing to fetch)
     if (st.run->rank == 0) {
@@ -252,6 +268,9 @@ rollover_sink(void* user, uint64_t new_path)
   }
   run.out.close();
   run.out.open(run.rank == 0 ? run.opt.prefix_file + "_" + std::to_string(new_path) + ".fq" : std::string("/dev/null"));
+  if (run.rank == 0) {
+    run.out_files.push_back(run.opt.prefix_file + "_" + std::to_string(new_path) + ".fq");
+  }
 }
 
 void

@@ -8,6 +8,7 @@
 namespace gr {
 
 struct Deferred;
+struct GoldenCarry; // (gr_golden.hpp)
 
 // what the classifier's callbacks get as their user pointer
 struct SinkState
@@ -19,6 +20,7 @@ struct SinkState
   const ResidentBatch* resident = nullptr;
   Resident* res = nullptr;
   Deferred* deferred = nullptr; // the resident run has compressed inputs: the commits are written in batches
+  GoldenCarry* golden = nullptr; // --golden_path, the first stage: what is written is remembered for the second
   std::vector<char> text;
   std::string upper;
   std::string bam_seq, bam_qual; // a BAM record's written slice as text

@@ -117,9 +117,15 @@ RECORDS_FETCH_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, _vp, C.c_uint64, _vp, C.c_
                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 
 
+READS_GATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(_vp))
+
+
+REWIND_FN = C.CFUNCTYPE(C.c_int, _vp)
+
+
 class grp_engine_ext(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN), ("records_fetch", RECORDS_FETCH_FN),
-                ("bam_parse_ex", BAM_PARSE_EX_FN)]
+                ("bam_parse_ex", BAM_PARSE_EX_FN), ("reads_gather", READS_GATHER_FN), ("rewind", REWIND_FN)]
 
 
 class gr_bam_record(C.Structure):
@@ -392,6 +398,8 @@ def hip_engine_ext() -> grp_engine_ext:
     ext.bam_parse = C.cast(lib.grp_bam_parse, BAM_PARSE_FN)
     ext.records_fetch = C.cast(lib.grp_records_fetch, RECORDS_FETCH_FN)
     ext.bam_parse_ex = C.cast(lib.grp_bam_parse_ex, BAM_PARSE_EX_FN)
+    ext.reads_gather = C.cast(lib.grp_reads_gather, READS_GATHER_FN)
+    ext.rewind = C.cast(lib.grp_rewind, REWIND_FN)
     return ext
 
 

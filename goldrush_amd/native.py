@@ -134,6 +134,9 @@ SIGNATURES = {
     "grp_gzip_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
     "grp_debug_gzip_stats": (C.c_int, [_vp, _vp]),
     "grp_records_fetch": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "grp_reads_gather": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(_vp)]),
+    "grp_reads_download": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
+    "grp_rewind": (C.c_int, [_vp]),
     "grp_dev_hooks": (C.c_int, []),
     "grp_set_timing": (C.c_int, [_vp, C.c_int]),
     "grp_get_kernel_stats": (C.c_int, [_vp, C.POINTER(grp_kernel_stat)]),
@@ -769,6 +772,30 @@ class Engine:
 
     def sync(self):
         self._check(self.lib.grp_sync(self._h))
+
+    # -- one stage's reads handed to the next (csrc/grp_gather.inc)
+    def reads_gather(self, srcs, slices) -> ReadBatch:
+        """slices: rows (src, read, first_base, n_bases) out of the batches `srcs`; the new batch holds one read per row."""
+        sl = np.ascontiguousarray(np.asarray(slices, dtype=np.int64).reshape(-1, 4).astype(np.uint32))
+        handles = (C.c_void_p * max(len(srcs), 1))(*[b._h for b in srcs])
+        out = C.c_void_p()
+        self._check(self.lib.grp_reads_gather(self._h, handles, len(srcs), _ptr(sl) if len(sl) else None, len(sl), C.byref(out)))
+        return ReadBatch(self, out, len(sl), sl[:, 3].copy())
+
+    def reads_download(self, batch: ReadBatch):
+        """(packed u32, word_off u64[n+1], len u32[n]) of a batch as the device holds it."""
+        word_off = np.zeros(batch.n_reads + 1, dtype=np.uint64)
+        lens = np.zeros(batch.n_reads, dtype=np.uint32)
+        self._check(self.lib.grp_reads_download(batch._h, None, 0, _ptr(word_off), _ptr(lens) if batch.n_reads else None))
+        packed = np.zeros(int(word_off[-1]), dtype=np.uint32)
+        if packed.size:
+            self._check(self.lib.grp_reads_download(batch._h, _ptr(packed), packed.size, None, None))
+        return packed, word_off, lens
+
+    def rewind(self):
+        """Back to "created, bit vector zero": the next fill builds a new filter in this engine."""
+        self._check(self.lib.grp_rewind(self._h))
+        self.pop = 0
 
     # -- inspection
     def export_bits(self) -> np.ndarray:

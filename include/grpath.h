@@ -634,6 +634,33 @@ typedef struct grp_fetch_record grp_fetch_record;
 int grp_records_fetch(grp_ctx* ctx, int unit_kind, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const void* units, uint32_t n_units, const grp_fetch_record* recs, uint32_t n_recs, uint32_t out_flags,
                       char* out, uint64_t out_cap, double* sums, uint32_t* bad_unit, uint32_t* bad_record);
 
+/* ---- one stage's reads handed to the next on the device (csrc/grp_gather.inc) --------------------------------------------
+ * grp_reads_gather: a new batch cut out of live batches of ctx.  Read i of the result is bases
+ * [first_base, first_base + n_bases) of read `read` of srcs[src], packed as grp_reads_upload packs that string (16 bases per
+ * word, base j at bits 2j, the unused bits of a read's last word zero).  The result is an ordinary batch owned by the
+ * engine (grp_reads_free), laid out like one of grp_fastq_pack; asynchronous on the context's stream like that call.
+ * Every slice is checked before anything is launched: src < n_srcs, read < the source's reads, n_bases >= 1,
+ * first_base + n_bases <= the read's length, every source a batch of ctx — else GRP_ERR_INVALID and no batch.  The kernel
+ * reads no word outside a source read's own words (a grp_reads_wrap_device batch has no slack behind them) and writes no
+ * word outside its slice's.  GRP_ERR_NOMEM: the result does not fit the device.  n_slices 0: an empty batch.
+ * grp_reads_download (tests, tools): the packed words [0, word_off[n_reads]) of a batch, its n_reads + 1 word offsets and
+ * its n_reads lengths, each where the pointer is given; `packed` needs room for all words (n_words, else GRP_ERR_INVALID).
+ * Waits for the context's stream. */
+typedef struct { uint32_t src; uint32_t read; uint32_t first_base; uint32_t n_bases; } grp_read_slice;
+int grp_reads_gather(grp_ctx* ctx, const grp_reads* const* srcs, uint32_t n_srcs, const grp_read_slice* slices, uint32_t n_slices, grp_reads** out);
+int grp_reads_download(const grp_reads* reads, uint32_t* packed, uint64_t n_words, uint64_t* word_off, uint32_t* len);
+/* grp_rewind: a context in any state back to "created, filter size set, bit vector zero" — what grp_create (and
+ * grp_set_filter_size) left — so that a second filter is built in the place of the first without a second context.  It
+ * waits for the context's streams, joins the helper thread of grp_set_occupancy_hint, FREES the phase-2 tables, prepared or
+ * in use (they are not kept and zeroed: the next grp_finalize sizes its tables from the occupancy it measures, and the next
+ * hint prepares them beside the next fill), allocates the bit vector again where grp_finalize has released it and zeroes
+ * it, forgets the hint, clears `finalized`, the kept first decisions, the batch epochs, the debug counters and the kernel
+ * statistics.  It keeps m, the seeds, the streams, every scratch buffer, the CRC tables and all live grp_reads of the
+ * context.  GRP_ERR_STATE while a window (pipelined or streaming) or a batch is outstanding; GRP_ERR_NOMEM if the bit
+ * vector cannot be allocated.  May be followed by grp_set_occupancy_hint, grp_bv_insert and grp_finalize exactly as
+ * grp_create may. */
+int grp_rewind(grp_ctx* ctx);
+
 /* 1: the library was built with GRP_DEV_HOOKS (make DEV=1): the measurement-only prototypes of include/grpath_dev.h are
  * compiled in; 0: the product build (they are not exported) */
 int grp_dev_hooks(void);

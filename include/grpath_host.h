@@ -358,6 +358,11 @@ typedef struct
    * device as the reads of its aligned twin; without it such a run's BAM files take the host reader, as BAM files do on an
    * engine without bam_parse */
   int (*bam_parse_ex)(void* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, uint32_t accept, void** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset, uint64_t* n_skipped);
+  /* grp_reads_gather and grp_rewind (both or none): what a --golden_path run needs to hand the silver reads to its second
+   * stage on the device and to build that stage's filter in the place of the first; without them the second stage reads
+   * the silver files */
+  int (*reads_gather)(void* ctx, const void* const* srcs, uint32_t n_srcs, const grp_read_slice* slices, uint32_t n_slices, void** out);
+  int (*rewind)(void* ctx);
 } grp_engine_ext;
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */
