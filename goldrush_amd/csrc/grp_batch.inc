@@ -811,7 +811,7 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
     HIP_TRY(c, hipMemsetAsync(br.d_rec_chain, 0xFF, n * sizeof(uint32_t), c->stream)); // every batch leaves it clean (k_batch_clear)
     // touches of a rank by a second (read, block): ~ranks^2 / (2 pop) for independent reads,
     // more where reads of the batch overlap (then the batch is taken back anyway)
-    const long ovf_test = getenv("GRP_BATCH_OVF_CAP") ? atol(getenv("GRP_BATCH_OVF_CAP")) : 0; // tests: a tiny chain store, so that batches are refused on the device
+    const long ovf_test = c->sw.batch_ovf_cap; // GRP_BATCH_OVF_CAP, tests: a tiny chain store, so that batches are refused on the device
     const uint64_t no = ovf_test > 0 ? (uint64_t)ovf_test : n / 4 + 65536;
     HIP_TRY(c, br.d_ovf_next.reset(no));
     HIP_TRY(c, br.d_ovf_jb.reset(no));
@@ -834,7 +834,7 @@ grp_batch_insert_reads(grp_ctx* c, const grp_reads* r, const grp_batch_insert* i
   br.n_rec = n_rec;
   br.cur_cap = want; // this batch uses the first `want` slots of the tables
   br.first_read = first_read;
-  if (br.epoch >= c->batch_epochs) {
+  if (br.epoch >= c->sw.batch_epochs) {
     // 1023 batches since the claims were last dropped: once over the count words (the insert lines of all units)
     k_batch_sweep<<<dim3(16384), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<unsigned long long*>(c->f.buckets), c->f.n_buckets * GRP_UNIT_QW, GRP_UNIT_QW, 8u);
     k_batch_sweep<<<dim3(4096), dim3(THREADS), 0, c->stream>>>(reinterpret_cast<unsigned long long*>(c->f.far), (c->f.far_mask + 1) * 2, 2u, 1u);
@@ -905,10 +905,7 @@ grp_window_overlap(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   // one frame in 32 (round 5; one in 16 before): with the threshold halved the same overlaps are named and the pass's table
   // work is half (tools/dev/r5_ovl_sampling.sh: silver pass over C2's reads 138.2 -> 140.3 k reads/s, repeat-rich genome 97.9 -> 99.9 k;
   // one in 64 with a threshold of 2 names unrelated reads)
-  static const uint32_t ovl_shift = [] { // developer hook (measurement): 60 = one sampled frame in 16, 59 = one in 32 ...
-    const char* e = getenv("GRP_BATCH_OVERLAP_SHIFT");
-    return e ? (uint32_t)std::min(63, std::max(52, atoi(e))) : 59u;
-  }();
+  const uint32_t ovl_shift = c->sw.batch_overlap_shift; // GRP_BATCH_OVERLAP_SHIFT, developer hook (measurement): 60 = one sampled frame in 16, 59 = one in 32 ...
   const size_t lds = tab_bytes(c) + bases_bytes(c->params.tile + c->params.k + c->params.h);
   for (uint64_t b0 = 0; b0 < nt; b0 += MAX_GRID_WGS) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(nt - b0, MAX_GRID_WGS);

@@ -203,7 +203,7 @@ grp_rewind(grp_ctx* c)
   c->batch.epoch = 0; // (the claims went with the count words)
   for (QuerySlot& sl : c->slot) {
     sl.reads = nullptr;
-    sl.streaming = sl.resumable = false;
+    sl.win.streaming = sl.win.resumable = false;
   }
   c->ingest.n_pre = 0; // (bodies uploaded ahead of a parse that never came)
   c->n_overlap_calls = c->n_batch_sweeps = 0;

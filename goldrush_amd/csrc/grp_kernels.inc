@@ -925,33 +925,8 @@ struct InsertTable
   uint64_t cap_mask;
 };
 
-// ---- control block of a streaming window that applies inserts itself (grp_classify_stream_insert) ----
-// uint32 words, every hot word on its own 128-byte line
-enum : uint32_t
-{
-  SCT_GEN = 0 * 32,      // generation of the records being produced (= 1 + inserts applied by this launch); .pad of a record
-  SCT_EVENT = 1 * 32,    // master event word: (insert commands seen << 1) | exit bit; advanced by CAS (relay workgroups)
-  SCT_CMD = 2 * 32,      // the insert command, copied from host memory by the relay: [0] read (batch index) [1] tile_start
-                         //   [2] tile_end [3] block_tiles [4] first_id [5] id_offset [6] resume read (window index) [7] resume tile
-                         //   [8] decided base [9] generation
-  SCT_DECIDED = 3 * 32,  // reads decided since the last resume (+ base)
-  SCT_UNIT = 4 * 32,     // [parity] collect-unit dispenser
-  SCT_APPLY = 5 * 32,    // [parity] apply-chunk dispenser
-  SCT_IRCOUNT = 6 * 32,  // [parity] claimed table slots
-  SCT_ALIVE = 7 * 32,    // round 6: workgroups of the launch that have begun [11:0], inserts the launch has taken [30:12], bit 31: an insert
-                         //   is in progress (a workgroup that begins now is not among its members: stream_register)
-  SCT_ERR = 8 * 32,      // != 0: a grid-wide wait timed out
-  SCT_BAR = 9 * 32,      // [4 lines: parity x first / second wait] members that have arrived (zeroed with the other parity's insert)
-  SCT_MEMBERS = 13 * 32, // workgroups the insert in progress waits for (SCT_ALIVE's count when its event was published)
-  SCT_DONE = 14 * 32,    // [0] event word of the last insert that is through, [1] grid-wide waits passed with it: where a workgroup that begins late picks up
-  SCT_EV = 41 * 32,      // [16 lines] copy of the event word per group (what idle workgroups poll)
-  SCT_SCAN_END = 57 * 32,  // round 6: dispenser position the insert in progress found (tiles in front of it were handed out under the old state: they carry marks); bit 31: nothing of them is kept
-  SCT_FRONTIER = 58 * 32,  // the furthest the dispenser has stood at an insert (monotonic): the end of the second walk — tiles in front of it may carry marks
-  SCT_WORDS = 59 * 32
-};
-constexpr uint32_t SCT_GROUPS = 16;
-
-constexpr uint32_t STREAM_REL_WGS = 4096; // workgroups of a streaming launch at most (a release line each)
+// (the control block of a streaming window that applies inserts itself, SCT_*, and every other word the launch and the
+// host hand each other: grp_stream_proto.h)
 
 // Streaming window (grp_classify_stream_*): persistent k_query<.., true> workgroups draw
 // the window's tiles in order; the workgroup that finishes the LAST tile of a read takes
@@ -976,17 +951,15 @@ struct DevStreamCtl
                                          // reads that were already handed out are still processed
   uint32_t n_tiles = 0;
   uint32_t early_park = 1;               // the deciding wave parks the window at an insert / hand-back record
-  unsigned long long* executed = nullptr; // [0] probes of the tiles that were processed; round 6, behind in-launch inserts: [1] finished tiles kept,
-                                         // [2] finished tiles queried again (a probe's slot changed), [3] finished tiles queried again (fingerprints gone),
-                                         // [4] tiles in progress that went on, [5] that started over, [6] inserts that kept nothing (everything handed out again), [7] inserts that kept
+  unsigned long long* executed = nullptr; // EXE_*: probes of the tiles that were processed; round 6: what the in-launch inserts kept and redid
   grp_decide_params dp{};
   uint32_t* g_ids = nullptr;             // per-tile results (inspection) / scratch of long reads
   uint8_t* g_asg = nullptr;
   uint64_t* g_scratch = nullptr;
   // in-launch inserts: NULL ctl = the window ends at its first insert (striped windows, tests of the classic form)
   uint32_t* ctl = nullptr;            // SCT_* words, device memory
-  const uint32_t* cmd_host = nullptr; // mapped host memory: [0] sequence number of the newest command, [1..] its fields (SCT_CMD layout)
-  uint32_t* ack_host = nullptr;       // mapped host memory: [0] inserts applied [1] 1 = a grid-wide wait timed out, the pending insert was NOT applied
+  const uint32_t* cmd_host = nullptr; // mapped host memory: CMD_SEQ the sequence number of the newest command, from CMD_FIELDS on its CMD_* fields
+  uint32_t* ack_host = nullptr;       // mapped host memory: ACK_* words
   uint32_t n_reads = 0;               // reads of the window
   uint32_t n_decidable = 0;           // ... of this launch's stripes with at least one tile (the others are decided by the host)
   uint32_t cmd_while_busy = 0;        // a striped window: an insert command parks the launch wherever it is (the relays look for it between tiles)
@@ -1630,7 +1603,7 @@ stream_decide(const DevStreamCtl& sc, uint32_t rj, uint64_t a, uint32_t n, const
     // 1 300 of them finished with their fingerprints gone — more work lost per insert than parking idles away.)
     atomicMin(sc.park, rj + 1u);
     if (sc.ctl == nullptr) {
-      atomicMax(sc.next_tile, 0x40000000u);
+      atomicMax(sc.next_tile, STREAM_STOP);
     }
     // (a window that applies inserts itself parks by the `park` word alone: a workgroup that draws a tile of a read behind
     // it goes idle — the dispenser itself must stay open, for behind an insert it walks a second time, and a read whose
@@ -1921,8 +1894,8 @@ stream_grid_wait(const DevStreamCtl& sc, uint32_t k, uint32_t* sFlag, bool inval
       if ((++spins & 0x3FFu) == 0u) {
         if (ldc(sc.ctl + SCT_ERR) != 0u || wall_clock64() - t0 > sc.timeout_ticks) {
           if (ldc(sc.ctl + SCT_ERR) == 0u) { // the first one to give up: which wait, who, how many had come of how many (the host's message)
-            __hip_atomic_store(sc.ack_host + 14, (k & 0xFFFFu) | (blockIdx.x << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(sc.ack_host + 15, (members << 16) | (ldc(bar) & 0xFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(sc.ack_host + ACK_GAVE_UP_WHO, (k & 0xFFFFu) | (blockIdx.x << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(sc.ack_host + ACK_GAVE_UP_COUNT, (members << 16) | (ldc(bar) & 0xFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           }
           stc(sc.ctl + SCT_ERR, 1u);
           ok = 0u;
@@ -1980,7 +1953,6 @@ stream_register(const DevStreamCtl& sc, uint32_t* my_ev, uint32_t* phase)
 __device__ inline void
 stream_relay(const DevStreamCtl& sc)
 {
-  constexpr uint32_t STREAM_STOP = 0x40000000u;
   const uint32_t ev = ldc(sc.ctl + SCT_EVENT);
   if (ev & 1u) {
     return;
@@ -1993,23 +1965,23 @@ stream_relay(const DevStreamCtl& sc)
     stc(sc.abort, 1u);
     nev = ev | 1u;
   } else {
-    const uint32_t hseq = load_host(sc.cmd_host);
+    const uint32_t hseq = load_host(sc.cmd_host + CMD_SEQ);
     if (hseq != (ev >> 1)) {
       __builtin_amdgcn_s_waitcnt(0);
-      uint32_t w[10];
+      uint32_t w[CMD_N_FIELDS];
 #pragma unroll
-      for (int i = 0; i < 10; ++i) {
-        w[i] = load_host(sc.cmd_host + 1 + i);
+      for (int i = 0; i < (int)CMD_N_FIELDS; ++i) {
+        w[i] = load_host(sc.cmd_host + CMD_FIELDS + i);
       }
       __builtin_amdgcn_s_waitcnt(0);
-      if (load_host(sc.cmd_host) == hseq) {
+      if (load_host(sc.cmd_host + CMD_SEQ) == hseq) {
         // A striped window: the inserting read may lie in another rank's stripe (this launch knows nothing of it) — every
         // read of the window up to it has been decided by its owner (the ranks have exchanged those records), so nothing
         // this launch still holds in front of it is needed, and everything behind it is held against the insert.
         // (round 6: the command parks nothing — every workgroup takes the event behind the tile it is in, applies the
         // insert and holds the tiles it keeps of the reads behind it against the slots the insert changed)
 #pragma unroll
-        for (int i = 0; i < 10; ++i) {
+        for (int i = 0; i < (int)CMD_N_FIELDS; ++i) {
           stc(sc.ctl + SCT_CMD + i, w[i]);
         }
         __builtin_amdgcn_s_waitcnt(0);
@@ -2068,14 +2040,14 @@ stream_idle(const DevStreamCtl& sc, uint32_t* my_ev)
     if ((++spins & 0xFFFu) == 0u && wall_clock64() - t0 > 16ull * sc.timeout_ticks) {
       // nobody came for the parked window (a host that died?): never hang the device
       // what the launch was waiting on, for the host's error message
-      __hip_atomic_store(sc.ack_host + 8, ldc(sc.park), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sc.ack_host + 9, ldc(sc.ctl + SCT_DECIDED), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sc.ack_host + 10, ldc(sc.next_tile), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sc.ack_host + 11, ldc(sc.ctl + SCT_EVENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sc.ack_host + 12, load_host(sc.cmd_host), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sc.ack_host + 13, ldc(sc.ctl + SCT_GEN), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_PARK, ldc(sc.park), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_DECIDED, ldc(sc.ctl + SCT_DECIDED), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_NEXT_TILE, ldc(sc.next_tile), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_EVENT, ldc(sc.ctl + SCT_EVENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_CMD_SEQ, load_host(sc.cmd_host + CMD_SEQ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_IDLE_GEN, ldc(sc.ctl + SCT_GEN), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __builtin_amdgcn_s_waitcnt(0);
-      __hip_atomic_store(sc.ack_host + 1, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_CODE, (uint32_t)ACK_CODE_IDLE_EXIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       return STREAM_ACT_EXIT;
     }
   }
@@ -2099,9 +2071,9 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
                     const DevStreamCtl& sc, uint32_t ev, uint32_t& phase, unsigned long long* ctr, uint64_t lists_cap, const uint32_t* __restrict__ tile_idx, StreamInsertDone& done)
 {
   const uint32_t* cmd = sc.ctl + SCT_CMD;
-  const uint32_t read_idx = ldc(cmd + 0), tile_start = ldc(cmd + 1), tile_end = ldc(cmd + 2), block_tiles = ldc(cmd + 3);
-  const uint32_t first_id = ldc(cmd + 4), id_offset = ldc(cmd + 5), resume_read = ldc(cmd + 6), resume_tile = ldc(cmd + 7);
-  const uint32_t decided_base = ldc(cmd + 8), gen = ldc(cmd + 9);
+  const uint32_t read_idx = ldc(cmd + CMD_READ), tile_start = ldc(cmd + CMD_TILE_START), tile_end = ldc(cmd + CMD_TILE_END), block_tiles = ldc(cmd + CMD_BLOCK_TILES);
+  const uint32_t first_id = ldc(cmd + CMD_FIRST_ID), id_offset = ldc(cmd + CMD_ID_OFFSET), resume_read = ldc(cmd + CMD_RESUME_READ), resume_tile = ldc(cmd + CMD_RESUME_TILE);
+  const uint32_t decided_base = ldc(cmd + CMD_DECIDED_BASE), gen = ldc(cmd + CMD_GEN);
   const uint32_t par = (ev >> 1) & 1u;
   const uint32_t members = ldc(sc.ctl + SCT_MEMBERS); // the workgroups this insert waits for (those that had begun when it was published)
   uint32_t* const bar = sc.ctl + SCT_BAR + (par * 2u) * 32u;
@@ -2133,7 +2105,7 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
   uint32_t rank = 0;
   if (!stream_grid_wait(sc, ++phase, sFlag, false, members, bar, &rank)) {
     if (threadIdx.x == 0) { // nothing but the scratch table was touched: the host applies the insert (every workgroup says so: the same word)
-      __hip_atomic_store(sc.ack_host + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_CODE, (uint32_t)ACK_CODE_NOT_APPLIED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return false;
   }
@@ -2170,14 +2142,14 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
   }
   if (rank == 0u && threadIdx.x == 0) {
     uint32_t at = ldc(sc.next_tile);
-    at = max(at >= 0x40000000u ? 0u : at, ldc(sc.ctl + SCT_FRONTIER)); // the furthest the dispenser ever stood (parked: recorded then)
+    at = max(at >= STREAM_STOP ? 0u : at, ldc(sc.ctl + SCT_FRONTIER)); // the furthest the dispenser ever stood (parked: recorded then)
     stc(sc.ctl + SCT_FRONTIER, at);
     at = min(at, sc.n_tiles);
-    if (sc.n_fp == 0u || load_coherent(&ctr[3]) > (lists_cap / 4u) * 3u) {
+    if (sc.n_fp == 0u || load_coherent(&ctr[QCTR_LIST_CURSOR]) > (lists_cap / 4u) * 3u) {
       // Nothing is kept (no room for fingerprints in this geometry's LDS; or the list arena, which kept tiles pin, is
       // three quarters full): everything behind the read is queried again, the form of rounds 3 - 5.  The list arena
       // starts over with it: every read up to the inserted one has been decided (the lists of its tiles are dead).
-      store_coherent(&ctr[3], 0ull);
+      store_coherent(&ctr[QCTR_LIST_CURSOR], 0ull);
       stc(sc.ctl + SCT_SCAN_END, STREAM_FULL_RESET | at);
     } else {
       stc(sc.ctl + SCT_SCAN_END, at);
@@ -2194,7 +2166,7 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
   const unsigned long long t_apply_own = wall_clock64();
   if (!stream_grid_wait(sc, ++phase, sFlag, true, members, bar + 32)) {
     if (threadIdx.x == 0) {
-      __hip_atomic_store(sc.ack_host + 1, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sc.ack_host + ACK_CODE, (uint32_t)ACK_CODE_WAIT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return false;
   }
@@ -2206,12 +2178,12 @@ stream_apply_insert(const DevFilter& f, const DevReads& rd, const DevSeeds* __re
     __builtin_amdgcn_s_waitcnt(0);
     (void)__hip_atomic_fetch_and(sc.ctl + SCT_ALIVE, ~STREAM_ALIVE_LOCK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_s_waitcnt(0);
-    __hip_atomic_store(sc.ack_host + 4, (uint32_t)(t_collect_own - t_enter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(sc.ack_host + 5, (uint32_t)(t_collected - t_collect_own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(sc.ack_host + 6, (uint32_t)(t_apply_own - t_collected), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(sc.ack_host + 7, (uint32_t)(wall_clock64() - t_apply_own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(sc.ack_host + ACK_PHASE + 0, (uint32_t)(t_collect_own - t_enter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(sc.ack_host + ACK_PHASE + 1, (uint32_t)(t_collected - t_collect_own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(sc.ack_host + ACK_PHASE + 2, (uint32_t)(t_apply_own - t_collected), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(sc.ack_host + ACK_PHASE + 3, (uint32_t)(wall_clock64() - t_apply_own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __builtin_amdgcn_s_waitcnt(0);
-    __hip_atomic_store(sc.ack_host, ev >> 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(sc.ack_host + ACK_APPLIED, ev >> 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   done.resume_read = resume_read;
   done.resume_tile = resume_tile;
@@ -2472,7 +2444,6 @@ k_query(DevFilter f,
   // from a dispenser, in window order; an abort parks the dispenser beyond the last
   // tile, so a stale window ends as soon as the resident tiles are done.  The next
   // index is fetched while the current tile is being processed.
-  constexpr uint32_t STREAM_STOP = 0x40000000u;
   uint32_t nxt = 0;
   uint32_t stop = 0; // thread 0: the device abort flag, read while the previous tile was finishing
   uint32_t my_ev = 0;   // thread 0: the last event of the control block this workgroup acted on
@@ -2569,7 +2540,7 @@ k_query(DevFilter f,
           sGen = done.gen;
         }
         if (done.rank == 0u && threadIdx.x == 0) {
-          atomicAdd(sc.executed + (keep_none ? 6 : 7), 1ull);
+          atomicAdd(sc.executed + (keep_none ? EXE_INSERTS_KEPT_NONE : EXE_INSERTS_KEPT), 1ull);
         }
         {
           const uint32_t* const changed = sc.fp_tab[done.par];
@@ -2601,7 +2572,7 @@ k_query(DevFilter f,
             const bool any_dirty = __syncthreads_or(dirty ? 1 : 0) != 0;
             if (any_dirty) {
               if (threadIdx.x == 0) { // one of its probes reads another ID now: this workgroup queries it again, first thing
-                atomicAdd(sc.executed + 2, 1ull);
+                atomicAdd(sc.executed + EXE_REDONE_DIRTY, 1ull);
                 stc(&sc.tile_ver[th], STREAM_TILE_BUSY);
                 sOwnRedo[sOwnRedoN++] = th;
                 sHeldTile[hb] = STREAM_REDO_NONE;
@@ -2611,7 +2582,7 @@ k_query(DevFilter f,
             // untouched by the insert: the summary stands — counted again for its read, which may be complete with it
             const uint32_t nt_h = (uint32_t)(rd.tile0[rh + 1] - rd.tile0[rh]);
             if (threadIdx.x == 0) {
-              atomicAdd(sc.executed + 1, 1ull);
+              atomicAdd(sc.executed + EXE_KEPT, 1ull);
               stc(&sc.tile_ver[th], done.gen);
               __builtin_amdgcn_s_waitcnt(0);
               sTile = (atomicAdd(&sc.tiles_done[rjh], 1u) + 1u == nt_h) ? 1u : 0u;
@@ -2656,7 +2627,7 @@ k_query(DevFilter f,
               continue;
             }
             if (v != 0u) {
-              atomicAdd(sc.executed + 3, 1ull); // finished under an older generation, nobody's: queried again
+              atomicAdd(sc.executed + EXE_REDONE_LOST, 1ull); // finished under an older generation, nobody's: queried again
             }
           }
           pick = cand;
@@ -2747,7 +2718,7 @@ k_query(DevFilter f,
   __syncthreads();
   if constexpr (ST) {
     if (threadIdx.x == 0) {
-      atomicAdd(sc.executed, (unsigned long long)frames * hn);
+      atomicAdd(sc.executed + EXE_PROBES, (unsigned long long)frames * hn);
     }
   }
   uint32_t* const fp_cur = (ST && sFp != nullptr) ? sFp + sBuf * sc.fp_words : nullptr; // (sBuf is final behind the barrier above)
@@ -3146,14 +3117,14 @@ k_query(DevFilter f,
     if (direct_stride != 0u) {
       lo = (uint64_t)out_idx * direct_stride;
     } else if (n && !flagged) {
-      lo = atomicAdd(&ctr[3], (unsigned long long)n);
+      lo = atomicAdd(&ctr[QCTR_LIST_CURSOR], (unsigned long long)n);
     }
     sListOff = (uint32_t)lo;
     if (flagged) {
       sListN = 0; // nothing is copied out; the full-capacity launch redoes this tile
       if (direct_stride == 0u) {
-        atomicAdd(&ctr[1], 1ull); // statistics: tiles with more distinct IDs than this launch's table takes
-        const unsigned long long fi = atomicAdd(&ctr[4], 1ull);
+        atomicAdd(&ctr[QCTR_FLAGGED_DISTINCT], 1ull); // statistics: tiles with more distinct IDs than this launch's table takes
+        const unsigned long long fi = atomicAdd(&ctr[QCTR_FLAGGED], 1ull);
         if (flagged_out && fi < flagged_cap) {
           flagged_out[fi] = out_idx;
         }

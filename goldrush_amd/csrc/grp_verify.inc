@@ -268,7 +268,7 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
         n_max += dKeys[i] != 0u ? 1u : 0u;
       }
     }
-    sListOff = n_max ? (uint32_t)atomicAdd(&ctr[3], (unsigned long long)n_max) : 0u;
+    sListOff = n_max ? (uint32_t)atomicAdd(&ctr[QCTR_LIST_CURSOR], (unsigned long long)n_max) : 0u;
   }
   __syncthreads();
   uint32_t bc = 0, bid = 0;
@@ -382,16 +382,16 @@ k_batch_delta(DevFilter f, DevReads rd, const DevSeeds* __restrict__ sd, uint32_
     ts.misses = (uint32_t)((int)T0.misses + sDM);
     if (bad) {
       ts.list_n = GRP_TILE_FLAGGED;
-      const unsigned long long fi = atomicAdd(&ctr[4], 1ull);
+      const unsigned long long fi = atomicAdd(&ctr[QCTR_FLAGGED], 1ull);
       if (fi < flagged_cap) {
         flagged_out[fi] = out_idx;
       }
       if (sBad & 2u) {
-        atomicAdd(&ctr[5], 1ull); // an impossible delta: reported by the host (the tile is still redone exactly)
+        atomicAdd(&ctr[QCTR_IMPOSSIBLE], 1ull); // an impossible delta: reported by the host (the tile is still redone exactly)
       }
-      // why the patch was given up (statistics): [6] the old top lost frames and no count > 2 is left, [7] anything else
-      // (delta table full, the batch's first ID shared with the read in front, a first summary that was itself flagged)
-      atomicAdd(&ctr[(sBad == 0u && !(T0.list_n == GRP_TILE_FLAGGED)) ? 6 : 7], 1ull);
+      // why the patch was given up (statistics): uncertified — the old top lost frames and no count > 2 is left; unpatched — anything
+      // else (delta table full, the batch's first ID shared with the read in front, a first summary that was itself flagged)
+      atomicAdd(&ctr[(sBad == 0u && !(T0.list_n == GRP_TILE_FLAGGED)) ? QCTR_UNCERTIFIED : QCTR_UNPATCHED], 1ull);
     }
     tiles_out[out_idx] = ts;
   }
@@ -411,8 +411,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   }
   BatchRun& br = c->batch;
   const grp_ctx::Carry cy = c->carry;
-  const char* off_env = getenv("GRP_BATCH_VERIFY"); // developer switch / tests: always the second query
-  const bool off = off_env && !strcmp(off_env, "off");
+  const bool off = c->sw.batch_verify_off; // GRP_BATCH_VERIFY=off, developer switch / tests: always the second query
   if (off || !cy.valid || cy.reads != r || cy.first > first || (uint64_t)first + count > (uint64_t)cy.first + cy.count || c->slot[0].busy || c->slot[1].busy) {
     // the first decisions' summaries are gone (or never were this engine's): the window is queried again
     ++c->n_verify_fallbacks;
@@ -513,7 +512,7 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       bq.skip_read_ins = d_read_ins;
       bq.skip_reads = count;
       c->view = &bq;
-      lrc = launch_query(c, r, nt_batch, t0, nullptr, g, so.list_cap);
+      lrc = launch_query(c, r, QueryLaunch{ nt_batch, t0, g, so.list_cap });
       c->view = nullptr;
       if (lrc != GRP_OK) {
         return lrc;
@@ -522,7 +521,10 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
     }
     if (extra) { // the reads behind the batch: the plain query (the next window's first decisions)
       Timer t(c, GRP_K_QUERY, x_probes);
-      lrc = launch_query(c, r, nt_all - nt_batch, t0, nullptr, g, so.list_cap, nullptr, nullptr, 0, nullptr, (uint32_t)nt_batch, false, true);
+      QueryLaunch ql{ nt_all - nt_batch, t0, g, so.list_cap };
+      ql.blk0 = (uint32_t)nt_batch;
+      ql.plain = true;
+      lrc = launch_query(c, r, ql);
       if (lrc != GRP_OK) {
         return lrc;
       }
@@ -536,10 +538,11 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       // A list longer than the launch takes the old way below.
       Timer t(c, GRP_K_QUERY, 0);
       DevBatchView bf = bv;
-      bf.redo_count = reinterpret_cast<const unsigned long long*>(so.d_qctr.p) + 4;
+      bf.redo_count = reinterpret_cast<const unsigned long long*>(so.d_qctr.p) + QCTR_FLAGGED;
       c->view = &bf;
-      const QueryGeom gf = query_geom(c, true);
-      lrc = launch_query(c, r, VERIFY_REDO_ON_DEVICE, t0, so.d_flag_idx, gf, so.list_cap);
+      QueryLaunch ql{ VERIFY_REDO_ON_DEVICE, t0, query_geom(c, true), so.list_cap };
+      ql.d_tile_idx = so.d_flag_idx;
+      lrc = launch_query(c, r, ql);
       c->view = nullptr;
       if (lrc != GRP_OK) {
         return lrc;
@@ -561,24 +564,23 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
   HIP_TRY(c, hipEventSynchronize(so.done));
   bool done = false;
   for (int attempt = 0; attempt < 8 && !done; ++attempt) { // (worst case 5: arena too small for the window, then for the redone tiles' lists)
-    if (so.h_qctr[5] && attempt == 0) {
+    if (so.h_qctr[QCTR_IMPOSSIBLE] && attempt == 0) {
       // the patch's self-check (an older ID gained a frame / a count below zero): such a tile is flagged like any tile
       // whose patch was given up and is queried again through the log below — exact — so the run goes on; the count is
       // kept and said once (ADVICE r04: this used to end the run with the carry and the slot half updated)
-      c->n_verify_impossible += so.h_qctr[5];
-      static const bool strict = getenv("GRP_VERIFY_STRICT") != nullptr; // developer switch: a logic error of the patch ends the run (the GPU tests assert the count is 0)
-      if (strict) {
+      c->n_verify_impossible += so.h_qctr[QCTR_IMPOSSIBLE];
+      if (c->sw.verify_strict) { // GRP_VERIFY_STRICT, developer switch: a logic error of the patch ends the run (the GPU tests assert the count is 0)
         (void)grp_batch_undo(c, br.first_read, id_floor[0] & 0x7FFFFFFFu);
-        return set_err(c, GRP_ERR_STATE, "grp_batch_verify: %llu tiles with an impossible delta (GRP_VERIFY_STRICT; the batch was taken back)", (unsigned long long)so.h_qctr[5]);
+        return set_err(c, GRP_ERR_STATE, "grp_batch_verify: %llu tiles with an impossible delta (GRP_VERIFY_STRICT; the batch was taken back)", (unsigned long long)so.h_qctr[QCTR_IMPOSSIBLE]);
       }
       static bool said = false;
       if (!said) {
         said = true;
-        fprintf(stderr, "grp_batch_verify: %llu tiles with an impossible delta (patch given up, the tiles are queried again; grp_verify_stats counts them)\n", (unsigned long long)so.h_qctr[5]);
+        fprintf(stderr, "grp_batch_verify: %llu tiles with an impossible delta (patch given up, the tiles are queried again; grp_verify_stats counts them)\n", (unsigned long long)so.h_qctr[QCTR_IMPOSSIBLE]);
       }
     }
-    if (so.h_qctr[3] > so.list_cap) { // list arena too small: grow and redo the window (the inputs are untouched)
-      so.list_cap = 2 * so.h_qctr[3] + 4096; // (room for the lists of tiles that are redone: they are not in this count yet)
+    if (so.h_qctr[QCTR_LIST_CURSOR] > so.list_cap) { // list arena too small: grow and redo the window (the inputs are untouched)
+      so.list_cap = 2 * so.h_qctr[QCTR_LIST_CURSOR] + 4096; // (room for the lists of tiles that are redone: they are not in this count yet)
       rc = enqueue();
       if (rc != GRP_OK) {
         return rc;
@@ -586,17 +588,17 @@ grp_batch_verify(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count,
       HIP_TRY(c, hipEventSynchronize(so.done));
       continue;
     }
-    c->n_verify_uncertified += so.h_qctr[6];
-    c->n_verify_unpatched += so.h_qctr[7];
-    if (so.h_qctr[4] && redo_on_device && so.h_qctr[4] <= VERIFY_REDO_ON_DEVICE && so.h_qctr[4] <= so.d_flag_idx.cap) {
+    c->n_verify_uncertified += so.h_qctr[QCTR_UNCERTIFIED];
+    c->n_verify_unpatched += so.h_qctr[QCTR_UNPATCHED];
+    if (so.h_qctr[QCTR_FLAGGED] && redo_on_device && so.h_qctr[QCTR_FLAGGED] <= VERIFY_REDO_ON_DEVICE && so.h_qctr[QCTR_FLAGGED] <= so.d_flag_idx.cap) {
       // redone behind the patch, inside the launches that have just been waited for
-      c->n_verify_flagged += so.h_qctr[4];
-      c->n_flagged_tiles += so.h_qctr[4];
-      c->n_flagged_distinct += so.h_qctr[1];
-      c->n_flagged_list += so.h_qctr[2];
+      c->n_verify_flagged += so.h_qctr[QCTR_FLAGGED];
+      c->n_flagged_tiles += so.h_qctr[QCTR_FLAGGED];
+      c->n_flagged_distinct += so.h_qctr[QCTR_FLAGGED_DISTINCT];
+      c->n_flagged_list += so.h_qctr[QCTR_FLAGGED_LIST];
       ++c->n_redo_launches;
-    } else if (so.h_qctr[4]) { // tiles that could not be patched / needed the worst-case table: through the log, decide again
-      c->n_verify_flagged += so.h_qctr[4];
+    } else if (so.h_qctr[QCTR_FLAGGED]) { // tiles that could not be patched / needed the worst-case table: through the log, decide again
+      c->n_verify_flagged += so.h_qctr[QCTR_FLAGGED];
       QueryRun q;
       q.t0 = t0;
       c->q = &so;

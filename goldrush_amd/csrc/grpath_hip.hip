@@ -2,6 +2,8 @@
 // include/grpath.h.  Integer / bit-vector work, HBM-transaction bound: no MFMA.
 // This file: context, launch logic and the exported functions; the kernels live in
 // grp_kernels.inc (hot path), grp_ingest.inc (FASTQ), grp_inflate.inc (BGZF input), grp_ntcard.inc (--ntcard).
+// The k_query launch is grp_query.inc, the streaming window's host side grp_stream.inc, the words the two sides of
+// a launch hand each other grp_stream_proto.h.
 //
 // Kernels
 //   k_fill        spaced-seed ntHash of every read position + test-and-set of
@@ -19,6 +21,8 @@
 // pick it); the forms of spans up to 64 are untouched.
 #include "grp_buffers.h"
 #include "grp_device.h"
+#include "grp_stream_proto.h"
+#include "host/gr_stream_stripes.hpp"
 #include "host/gr_tile_geom.hpp"
 #include "host/gr_tiles_core.hpp"
 #include "host/gr_bam.hpp"
@@ -78,32 +82,35 @@ struct QuerySlot
   Event done;                  // decisions of the window are in h_dec
   Event qdone;                 // the window's query kernel has finished (decide stream waits on it)
   bool side_used = false;      // `done` was last recorded on the decide stream
-  // streaming window (grp_classify_stream_*)
-  HostBuf<grp_read_decision> h_sdec;      // mapped, coherent: the kernel publishes decisions here
-  // abort flag: the host raises the one in mapped host memory (a plain store); every
-  // 64th workgroup reads that one when it starts and relays it to the flag in DEVICE
-  // memory, which is what all workgroups test (a PCIe round trip in every workgroup
-  // costs the kernel 2.4x, measured; a 4-byte hipMemcpyAsync takes ~1.5 ms to land
-  // beside a full-device kernel, measured)
-  DevBuf<uint32_t> d_abort;
-  HostBuf<uint32_t> h_abort;              // mapped, coherent
-  DevBuf<uint32_t> d_tiles_done;
-  DevBuf<unsigned long long> d_executed;
-  HostBuf<unsigned long long> h_executed; // pinned
-  bool streaming = false;
-  // a streaming window that applies inserts itself (grp_classify_stream_insert)
-  DevBuf<uint32_t> d_tile_ver; // round 6: per tile of a resumable window, the generation its summary belongs to (DevStreamCtl::tile_ver)
-  DevBuf<uint32_t> d_rel;      // release words of a resumable window's grid-wide waits: a 128-byte line per workgroup (STREAM_REL_WGS of them)
-  DevBuf<uint32_t> d_dbg;      // developer (GRP_STREAM_DEBUG): a state word per workgroup of the streaming launch
-  DevBuf<uint32_t> d_sctl;     // SCT_* control block
-  HostBuf<uint32_t> h_cmd;     // mapped, coherent: [0] sequence number, [1..10] the command
-  HostBuf<uint32_t> h_ack;     // mapped, coherent: [0] inserts applied by the launch, [1] failure code
-  bool resumable = false;       // the window in flight takes grp_classify_stream_insert
-  uint32_t stripe_reads = 0, n_owners = 1, owner = 0; // its stripes (0: the whole window is this launch's)
-  uint32_t gen = 1;             // generation of the records the host is waiting for
-  uint32_t cmd_seq = 0;         // commands posted to the window in flight
-  HostBuf<uint32_t> h_stripe_tiles; // pinned: this rank's tiles of a striped window
-  DevBuf<uint32_t> d_stripe_tiles;
+  // streaming window (grp_classify_stream_*, grp_stream.inc); the words it shares with the launch: grp_stream_proto.h
+  struct StreamWindow
+  {
+    HostBuf<grp_read_decision> h_sdec;      // mapped, coherent: the kernel publishes decisions here
+    // abort flag: the host raises the one in mapped host memory (a plain store); every
+    // 64th workgroup reads that one when it starts and relays it to the flag in DEVICE
+    // memory, which is what all workgroups test (a PCIe round trip in every workgroup
+    // costs the kernel 2.4x, measured; a 4-byte hipMemcpyAsync takes ~1.5 ms to land
+    // beside a full-device kernel, measured)
+    DevBuf<uint32_t> d_abort;               // ABORT_* words
+    HostBuf<uint32_t> h_abort;              // mapped, coherent
+    DevBuf<uint32_t> d_tiles_done;
+    DevBuf<unsigned long long> d_executed;  // EXE_* counters
+    HostBuf<unsigned long long> h_executed; // pinned
+    bool streaming = false;
+    // a streaming window that applies inserts itself (grp_classify_stream_insert)
+    DevBuf<uint32_t> d_tile_ver; // round 6: per tile of a resumable window, the generation its summary belongs to (DevStreamCtl::tile_ver)
+    DevBuf<uint32_t> d_rel;      // release words of a resumable window's grid-wide waits: a 128-byte line per workgroup (STREAM_REL_WGS of them)
+    DevBuf<uint32_t> d_dbg;      // developer (GRP_STREAM_DEBUG): a state word per workgroup of the streaming launch
+    DevBuf<uint32_t> d_sctl;     // SCT_* control block
+    HostBuf<uint32_t> h_cmd;     // mapped, coherent: CMD_SEQ, then the command's CMD_* fields from CMD_FIELDS on
+    HostBuf<uint32_t> h_ack;     // mapped, coherent: ACK_* words
+    bool resumable = false;       // the window in flight takes grp_classify_stream_insert
+    gr::stripes::Window stripes;  // its reads and whose they are (one owner: the whole window is this launch's)
+    uint32_t gen = 1;             // generation of the records the host is waiting for
+    uint32_t cmd_seq = 0;         // commands posted to the window in flight
+    HostBuf<uint32_t> h_stripe_tiles; // pinned: this rank's tiles of a striped window
+    DevBuf<uint32_t> d_stripe_tiles;
+  } win;
   bool busy = false;
   const grp_reads* reads = nullptr;
   uint32_t first = 0, count = 0;
@@ -196,9 +203,27 @@ struct grp_ctx : CtxStreams
   uint64_t n_far = 0;    // count words living in the far table
   uint32_t uniform_weight = 0; // weight shared by all seeds, 0 if they differ
 
-  // developer switches, read once at grp_create (not on every call of a latency path)
-  bool env_no_direct = false, env_stream_resume_off = false, env_no_early_park = false, env_trace_abort = false;
-  uint32_t env_small_hist = 0; // GRP_SMALL_HIST (developer hook / tests): slots of the first-step count table
+  // Developer switches and test hooks: every one the library reads, read once, when the context is created (read_switches;
+  // not on every call of a latency path).  DESIGN.md has the table.
+  struct Switches
+  {
+    bool no_direct = false;          // GRP_NO_DIRECT: grp_query_tiles takes the general path for small windows too
+    bool stream_resume_off = false;  // GRP_STREAM_RESUME=off: every streaming window ends where it parks
+    bool no_early_park = false;      // GRP_NO_EARLY_PARK (the engine-level API contract assumes it is not set)
+    int trace_abort = 0;             // GRP_TRACE_ABORT: 1 = set, 2 = its value begins with '2' (every in-launch insert's phase times)
+    uint32_t small_hist = 0;         // GRP_SMALL_HIST: slots of the first-step count table (forces the two-step scheme)
+    uint32_t batch_epochs = GRP_EPOCH_MAX; // GRP_BATCH_EPOCHS (tests): batches between two sweeps of the claims
+    int stream_keep = 2;             // GRP_STREAM_KEEP: fingerprint buffers per workgroup, 0 .. 2 (0: rounds 3 - 5's form)
+    int stream_wgs_per_cu = 0;       // GRP_STREAM_WGS_PER_CU: resident workgroups per CU of a streaming launch (0: three)
+    bool stream_debug = false;       // GRP_STREAM_DEBUG: a state word per workgroup of the streaming launch, dumped when a wait times out
+    double stream_wait_s = 2.0;      // GRP_STREAM_WAIT_S: time limit of a grid-wide wait (seconds)
+    bool verify_strict = false;      // GRP_VERIFY_STRICT: an impossible delta in grp_batch_verify ends the run
+    long batch_ovf_cap = 0;          // GRP_BATCH_OVF_CAP (tests): a tiny chain store, so that batches are refused on the device
+    uint32_t batch_overlap_shift = 59; // GRP_BATCH_OVERLAP_SHIFT (measurement): 60 = one sampled frame in 16, 59 = one in 32 ...
+    bool batch_verify_off = false;   // GRP_BATCH_VERIFY=off: grp_batch_verify always takes the second query
+    bool shared_halves_off = false;  // GRP_SHARED_HALVES=off: every seed of a frame hashed on its own
+    bool debug_stats = false;        // GRP_DEBUG_STATS: grp_destroy prints the context's path counters
+  } sw;
   // grp_window_overlap (grp_batch.inc): samples per tile, their table, the result per read
   struct OverlapBuf
   {
@@ -208,7 +233,6 @@ struct grp_ctx : CtxStreams
     DevBuf<uint32_t> d_prev;
   } ovl;
   uint64_t n_overlap_calls = 0;
-  uint32_t batch_epochs = GRP_EPOCH_MAX; // batches between two sweeps of the claims (GRP_BATCH_EPOCHS: tests)
   uint64_t n_batch_sweeps = 0; // times the batch epochs wrapped and the claims were swept out of the count words
   uint64_t n_stream_keep[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; // grp_debug_stream_stats
   uint64_t n_stream_idle_exits = 0, n_stream_coop_refused = 0; // parked windows that left by themselves (idle limit); resumable windows whose cooperative launch was refused
@@ -676,242 +700,55 @@ constexpr size_t LDS_PER_WORKGROUP = 160 * 1024 - 512; // gfx950, less the kerne
 // samples, tile-hash inspection): their LDS grows with the span, and fits at the longest span and tile there are
 static_assert(GRP_DEV_MAX_H * GRP_DEV_MAX_W * 4u * sizeof(ulonglong2) + bases_bytes(GRP_MAX_TILE + GRP_MAX_SPAN + GRP_DEV_MAX_H) <= LDS_PER_WORKGROUP,
               "a tile of the longest span does not fit the LDS beside the seed tables");
-constexpr uint32_t GT_SLICE = 256;                     // workgroups of one launch with global count tables
+} // namespace
 
-struct QueryGeom
-{
-  uint32_t hist_cap;       // slots of the per-tile count table (even; 6 bytes each: a key and a 16-bit count)
-  uint32_t distinct_limit; // distinct IDs it takes (the rest is room for the claims in flight)
-  size_t lds;
-  bool global_table = false; // the worst-case table does not fit the LDS: it lives in global memory (k_query<..., GT>; the redo launches only)
-};
+#include "grp_query.inc"
 
-// The per-tile count table (k_query).  full = worst case: every probe of the tile a different ID — tile * h slots
-// plus one claim per lane and seed in flight.  Round 4: at 6 bytes per slot and without power-of-two rounding the
-// worst case of the default geometries fits the LDS share that lets three workgroups (h = 5: 48 KB) or four (h = 3:
-// 27 KB) onto a CU, so it is what every launch uses and no tile is flagged; only geometries beyond that (h = 8 with
-// tiles of 1000: 69 KB; long tiles) keep the two-step scheme: a table of the budget's size first, the tiles whose
-// distinct IDs do not fit flagged and recomputed by the same kernel with the worst-case table.
-QueryGeom
-query_geom(const grp_ctx* c, bool full)
-{
-  const uint32_t h = c->params.h, tile = c->params.tile;
-  const uint64_t max_ids = (uint64_t)tile_frames(c) * h; // (tile + 1 frames at odd k)
-  auto lds_of = [&](uint32_t cap) { return tab_bytes(c) + (size_t)cap * 6 + bases_bytes(tile + c->params.k + h); };
-  const uint32_t cap_full = (uint32_t)((max_ids + (uint64_t)THREADS * h + 2 + 1023) / 1024 * 1024);
-  const uint32_t forced_small = c->env_small_hist; // developer hook / tests (GRP_SMALL_HIST, read when the context is created): slots of the first-step table — forces the two-step scheme
-  QueryGeom g;
-  g.hist_cap = cap_full;
-  if (!full) {
-    if (forced_small && forced_small < cap_full && forced_small > (uint32_t)THREADS * h + 64) {
-      g.hist_cap = forced_small;
-    } else if (lds_of(cap_full) > 52 * 1024) {
-      // the largest table that still lets three workgroups share a CU's 160 KB
-      const size_t fixed = lds_of(0);
-      const uint32_t cap = (uint32_t)((52 * 1024 - std::min<size_t>(fixed, 40 * 1024)) / 6 / 1024 * 1024);
-      if (cap > (uint32_t)THREADS * h + 1024 && cap < cap_full) {
-        g.hist_cap = cap;
-      }
-    }
-    if (g.hist_cap == cap_full && lds_of(cap_full) > LDS_PER_WORKGROUP) {
-      // no room for the three-workgroups table beside large seed tables (h > 8 of heavy seeds): the largest table
-      // the LDS takes, the tiles it cannot hold redone with the worst-case one
-      const size_t fixed = lds_of(0);
-      const uint32_t cap = fixed < LDS_PER_WORKGROUP ? (uint32_t)((LDS_PER_WORKGROUP - fixed) / 6 / 1024 * 1024) : 0u;
-      if (cap > (uint32_t)THREADS * h + 64) {
-        g.hist_cap = cap;
-      }
-    }
-  }
-  g.distinct_limit = g.hist_cap - THREADS * h - 1;
-  g.lds = lds_of(g.hist_cap);
-  if (full && g.lds > LDS_PER_WORKGROUP) {
-    // Round 5: tiles beyond ~9 000 frames at h = 3 (the reference has no such limit).  The first step's table is LDS-sized
-    // (above: the three-workgroups budget); what it cannot hold is redone with the worst-case table in global memory.
-    g.global_table = true;
-    g.lds = lds_of(0);
-  }
-  return g;
-}
+namespace {
 
-template<int HH, int QWT>
-int
-launch_query_wt(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles, grp_id_count* out_lists, uint32_t direct_stride, const DevStreamCtl* stream_ctl,
-                uint32_t blk0, bool list_flags, bool plain)
+// the environment's switches (grp_ctx::Switches): the library's only getenv calls
+grp_ctx::Switches
+read_switches()
 {
-  if (!out_tiles) {
-    out_tiles = c->q->d_tiles;
-    out_lists = c->q->d_lists;
-  }
-  size_t launch_lds = g.lds; // dynamic LDS of the launch (the streaming form adds its fingerprint buffers)
-  auto go = [&](auto kern) -> int {
-    int rc = ensure_lds(c, kern, launch_lds);
-    if (rc != GRP_OK) {
-      return rc;
-    }
-    if (stream_ctl && stream_ctl->ctl) {
-      // A window that applies inserts itself: its workgroups wait for each other inside the launch.  The grid is sized
-      // from the occupancy query below and launched cooperatively — the runtime checks that it fits the device (or
-      // refuses: another process on it).  That is a check of sizes, not of residency: now and then a few
-      // workgroups begin only when others leave, so the waits count the workgroups that have begun (stream_register).
-      // GRP_ERR_BUSY: refused — the caller begins the window in its classic form (it ends where it parks).
-      {
-        DevFilter a_f = c->f;
-        DevReads a_rd = r->dev;
-        const DevSeeds* a_sd = c->d_seeds;
-        uint32_t a_tile = c->params.tile;
-        uint64_t a_t0 = t0;
-        const uint32_t* a_idx = d_tile_idx;
-        uint32_t a_cap = g.hist_cap, a_lim = g.distinct_limit;
-        grp_tile_summary* a_tiles = out_tiles;
-        grp_id_count* a_lists = out_lists;
-        uint64_t a_lcap = list_cap;
-        unsigned long long* a_ctr = reinterpret_cast<unsigned long long*>(c->q->d_qctr.p);
-        uint32_t* a_flag = (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx;
-        uint32_t a_fcap = (uint32_t)c->q->d_flag_idx.cap, a_ds = direct_stride, a_blk0 = blk0;
-        DevStreamCtl a_sc = *stream_ctl;
-        DevBatchView a_bv{};
-        uint32_t* a_gtab = nullptr;
-        void* args[] = { &a_f, &a_rd, &a_sd, &a_tile, &a_t0, &a_idx, &a_cap, &a_lim, &a_tiles, &a_lists, &a_lcap, &a_ctr, &a_flag, &a_fcap, &a_ds, &a_blk0, &a_sc, &a_bv, &a_gtab };
-        const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(kern), dim3((uint32_t)n_launch), dim3(THREADS), args, (unsigned int)launch_lds, c->stream);
-        if (e == hipSuccess) {
-          return GRP_OK;
-        }
-        (void)hipGetLastError();
-        return set_err(c, GRP_ERR_BUSY, "cooperative launch of a resumable window refused: %s", hipGetErrorString(e));
-      }
-    }
-    kern<<<dim3((uint32_t)n_launch), dim3(THREADS), launch_lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, d_tile_idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx, (uint32_t)c->q->d_flag_idx.cap, direct_stride, blk0, stream_ctl ? *stream_ctl : DevStreamCtl{}, (c->view && !plain) ? *c->view : DevBatchView{}, nullptr);
-    return GRP_OK;
+  grp_ctx::Switches s;
+  const auto set = [](const char* name) { return getenv(name) != nullptr; };
+  const auto off = [](const char* name) {
+    const char* e = getenv(name);
+    return e && !strcmp(e, "off");
   };
-  // The synchronous forms (large windows, the two queries of a batch): two frames per lane and pass
-  // up to h = 3; from h = 4 on one frame per lane with the software-pipelined pass (222 -> 171 VGPRs
-  // at h = 5; C4 geometry +4 %, h = 3 -3 %: measured, tools/dev/r3_fr1.sh of round 3; round 4 again with the 24 KB count table:
-  // the head of C2 2.94 - 3.04 s against 2.94 - 2.96 s, no gain, the switch is gone)
-  constexpr int SFR = (HH <= 3) ? 2 : 1;
-  if (g.global_table) {
-    // the worst-case table in global memory, GT_SLICE workgroups (and tables) per launch
-    if (stream_ctl || direct_stride) {
-      return set_err(c, GRP_ERR_STATE, "launch_query: a global count table in a streaming / zero-copy launch");
-    }
-    const uint64_t words = (uint64_t)g.hist_cap + g.hist_cap / 2u;
-    if (const int rc = ensure_dev(c, c->d_gtab, words * GT_SLICE); rc != GRP_OK) {
-      return rc;
-    }
-    const bool ver = c->view && !plain;
-    for (uint64_t off = 0; off < n_launch; off += GT_SLICE) {
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(GT_SLICE, n_launch - off);
-      const uint32_t* idx = d_tile_idx ? d_tile_idx + off : nullptr;
-      const uint32_t b0 = d_tile_idx ? blk0 : blk0 + (uint32_t)off;
-      uint32_t* const flag_out = (d_tile_idx && !list_flags) ? nullptr : c->q->d_flag_idx;
-      if (ver) {
-        DevBatchView v = *c->view;
-        if (v.redo_count && off) {
-          break; // (a launch sized before its list was known covers one slice: longer lists take the host's way)
-        }
-        auto kern = k_query<HH, 1, QWT, false, true, true>;
-        if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
-          return rc;
-        }
-        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), flag_out, (uint32_t)c->q->d_flag_idx.cap, 0u, b0, DevStreamCtl{}, v, c->d_gtab);
-      } else {
-        auto kern = k_query<HH, 1, QWT, false, false, true>;
-        if (const int rc = ensure_lds(c, kern, g.lds); rc != GRP_OK) {
-          return rc;
-        }
-        kern<<<dim3(nb), dim3(THREADS), g.lds, c->stream>>>(c->f, r->dev, c->d_seeds, c->params.tile, t0, idx, g.hist_cap, g.distinct_limit, out_tiles, out_lists, list_cap, reinterpret_cast<unsigned long long*>(c->q->d_qctr.p), flag_out, (uint32_t)c->q->d_flag_idx.cap, 0u, b0, DevStreamCtl{}, DevBatchView{}, c->d_gtab);
-      }
-    }
-    return GRP_OK;
+  s.no_direct = set("GRP_NO_DIRECT");
+  s.stream_resume_off = off("GRP_STREAM_RESUME");
+  s.no_early_park = set("GRP_NO_EARLY_PARK");
+  if (const char* e = getenv("GRP_TRACE_ABORT")) {
+    s.trace_abort = e[0] == '2' ? 2 : 1;
   }
-  if (c->view && !stream_ctl && !plain) { // grp_batch_classify: every read sees the state in front of its own insert
-    return go(k_query<HH, SFR, QWT, false, true>);
+  if (const char* e = getenv("GRP_SMALL_HIST")) {
+    s.small_hist = (uint32_t)atoi(e) / 2u * 2u;
   }
-  if (stream_ctl) {
-    // persistent workgroups: exactly what is resident at once
-    // one frame per lane and pass: fewer registers, more resident workgroups — measured
-    // better than two for the persistent form (h = 3: +3 %, h = 5: +19 %)
-    auto kern = k_query<HH, 1, QWT, true>;
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, THREADS, g.lds));
-    // Round 6: a window that applies inserts itself keeps the probes' fingerprints of the tile in progress and of the
-    // tile before it in LDS (DevStreamCtl::n_fp) — as many of the two buffers as fit WITHOUT costing a resident workgroup
-    // (three per CU is what the launch runs at, below — or fewer, where the kernel's registers allow no more): C2's geometry
-    // 27.9 + 2 x 12.3 KB, three of them in the CU's 160 KB; h = 5 with tiles of 1000 (48 KB of count table) would have no
-    // room beside three, but it does keep on the MI355X (its instance must be resident twice per CU there: ONE buffer, 25 KB,
-    // fits beside that).  h = 5 with tiles of 1500 (one buffer: 36 KB) has no room: such a window hands everything behind an insert out
-    // again (tests/test_gpu_stream_striped.py holds both).
-    DevStreamCtl sc_fit = *stream_ctl;
-    QueryGeom g_fit = g;
-    sc_fit.n_fp = 0;
-    if (stream_ctl->ctl && stream_ctl->n_fp) {
-      static const int keep_env = [] { // developer switch / tests: fingerprint buffers per workgroup (0: rounds 3 - 5's form)
-        const char* e = getenv("GRP_STREAM_KEEP");
-        return e ? std::max(0, std::min(2, atoi(e))) : 2;
-      }();
-      const uint32_t fb = gr::geom::helper_pass_frames(HH); // frames per pass at least (k_query: the helper-lane layout)
-      const uint32_t passes = (tile_frames(c) + fb - 1u) / fb;
-      const uint32_t words = passes * (uint32_t)THREADS * (uint32_t)HH;
-      const int want_cu = std::min(per_cu, 3);
-      for (int nf = std::min<int>(keep_env, (int)stream_ctl->n_fp); nf >= 1; --nf) {
-        const size_t lds = g.lds + (size_t)nf * words * 4u;
-        int fit = 0;
-        if (lds <= LDS_PER_WORKGROUP && ensure_lds(c, kern, lds) == GRP_OK && hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, THREADS, lds) == hipSuccess && fit >= want_cu) {
-          sc_fit.n_fp = (uint32_t)nf;
-          sc_fit.fp_off = (uint32_t)g.lds;
-          sc_fit.fp_words = words;
-          g_fit.lds = lds;
-          break;
-        }
-        (void)hipGetLastError();
-      }
-    }
-    stream_ctl = &sc_fit;
-    launch_lds = g_fit.lds; // (the launch takes the geometry with the fingerprint buffers)
-    int rc = ensure_lds(c, kern, launch_lds);
-    if (rc != GRP_OK) {
-      return rc;
-    }
-    static const int cap_per_cu = [] { // developer hook
-      const char* e = getenv("GRP_STREAM_WGS_PER_CU");
-      return e ? atoi(e) : 0;
-    }();
-    // 3 .. 6 resident workgroups per CU run equally fast (the kernel is bound by the DRAM
-    // access rate, not by occupancy); 4 keeps the amount of work in flight — what an abort
-    // throws away — small and leaves room on every CU for other kernels (copies, a
-    // collective) beside the persistent launch
-    // Round 4: THREE, not four.  With the 24 KB count table a fourth workgroup fits a CU by LDS and VGPRs (128: four
-    // waves per SIMD, every wave slot of the device), and the occupancy query — and hipLaunchCooperativeKernel — say
-    // so; but the launch then is NOT fully resident in practice (the kernel keeps 4 VGPRs in scratch, and the
-    // dispatcher admits fewer scratch waves than wave slots): on the C1 stream the grid-wide waits of the in-launch
-    // insert timed out (inserts handed back to the host: 243 k reads/s instead of 489 k, or code 2 with the
-    // cooperative launch), profiles/r04_c1_workgroups_per_cu.txt.  Rounds 1 - 3 ran three (the 43.6 KB table allowed
-    // no more); three leave a wave slot per SIMD free, and are as fast (C1 559 k reads/s in the steady state, two: 500 k).
-    per_cu = std::min(per_cu, cap_per_cu > 0 ? cap_per_cu : 3);
-    const uint64_t resident = std::min<uint64_t>((uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(c->n_cus, 1), STREAM_REL_WGS);
-    n_launch = std::min<uint64_t>(n_launch, resident);
-    c->dbg_stream_lds = (uint32_t)launch_lds;
-    c->dbg_stream_grid = (uint32_t)n_launch;
-    return go(kern);
+  if (const char* e = getenv("GRP_BATCH_EPOCHS")) { // the claims are swept every n batches instead of every 1023
+    s.batch_epochs = (uint32_t)std::min<long>(std::max<long>(atol(e), 1), (long)GRP_EPOCH_MAX);
   }
-  // (round 2 had a second form for windows of a few reads, the care loop unrolled for weight-16
-  // seeds: 346 VGPRs + 14 spilled at h = 3.  With the shared halves the hash is a third of the
-  // instructions it was and the batches took the insert-heavy phases over: the form is gone — the
-  // CLI's silver run takes the same time with and without it, tools/dev/r3_latform.sh.)
-  return go(k_query<HH, SFR, QWT, false>);
-}
-
-// The query of `n_launch` tiles in the form of the context's h and hash form (QWT of launch_query_wt: 0, or GRP_WT_LONG
-// for seeds of spans beyond 64 bases)
-int
-launch_query(grp_ctx* c, const grp_reads* r, uint64_t n_launch, uint64_t t0, const uint32_t* d_tile_idx, const QueryGeom& g, uint64_t list_cap, grp_tile_summary* out_tiles = nullptr, grp_id_count* out_lists = nullptr, uint32_t direct_stride = 0, const DevStreamCtl* stream_ctl = nullptr,
-             uint32_t blk0 = 0,          // no tile list: the launch covers tiles [blk0, blk0 + n_launch) of the window
-             bool list_flags = false,    // a tile list that is NOT the redo of flagged tiles: flagged tiles are collected as without a list
-             bool plain = false)         // the plain query even while a batch view is set (the reads behind the batch)
-{
-  int rc = GRP_OK;
-  DISPATCH_H_SPAN(c, (rc = launch_query_wt<HH, WW>(c, r, n_launch, t0, d_tile_idx, g, list_cap, out_tiles, out_lists, direct_stride, stream_ctl, blk0, list_flags, plain)));
-  return rc;
+  if (const char* e = getenv("GRP_STREAM_KEEP")) {
+    s.stream_keep = std::max(0, std::min(2, atoi(e)));
+  }
+  if (const char* e = getenv("GRP_STREAM_WGS_PER_CU")) {
+    s.stream_wgs_per_cu = atoi(e);
+  }
+  s.stream_debug = set("GRP_STREAM_DEBUG");
+  if (const char* e = getenv("GRP_STREAM_WAIT_S")) {
+    s.stream_wait_s = atof(e);
+  }
+  s.verify_strict = set("GRP_VERIFY_STRICT");
+  if (const char* e = getenv("GRP_BATCH_OVF_CAP")) {
+    s.batch_ovf_cap = atol(e);
+  }
+  if (const char* e = getenv("GRP_BATCH_OVERLAP_SHIFT")) {
+    s.batch_overlap_shift = (uint32_t)std::min(63, std::max(52, atoi(e)));
+  }
+  s.batch_verify_off = off("GRP_BATCH_VERIFY");
+  s.shared_halves_off = off("GRP_SHARED_HALVES");
+  s.debug_stats = set("GRP_DEBUG_STATS");
+  return s;
 }
 
 int
@@ -977,10 +814,9 @@ build_seed_tables(grp_ctx* c)
   // frame (GRP_SHARED_HALVES=off: developer switch, every seed on its own as before).
   sd.n_left = 0;
   {
-    const char* e = getenv("GRP_SHARED_HALVES");
     const std::string& s0 = c->seeds[0];
     const size_t cut = s0.size() / 2;
-    bool family = sd.h >= 2 && !(e && !strcmp(e, "off"));
+    bool family = sd.h >= 2 && !c->sw.shared_halves_off;
     for (uint32_t s2 = 1; s2 < sd.h && family; ++s2) {
       family = c->seeds[s2] == s0.substr(0, cut) + std::string(s2, '0') + s0.substr(cut);
     }
@@ -1054,19 +890,7 @@ grp_create(const grp_params* p, grp_ctx** out)
     set_err(c, GRP_ERR_NO_DEVICE, "hipGetDevice failed");
     return fail(GRP_ERR_NO_DEVICE);
   }
-  {
-    const char* e = getenv("GRP_STREAM_RESUME");
-    c->env_stream_resume_off = e && !strcmp(e, "off");
-    c->env_no_direct = getenv("GRP_NO_DIRECT") != nullptr;
-    if (const char* e = getenv("GRP_BATCH_EPOCHS")) { // tests: the claims are swept every n batches instead of every 1023
-      c->batch_epochs = (uint32_t)std::min<long>(std::max<long>(atol(e), 1), (long)GRP_EPOCH_MAX);
-    }
-    c->env_no_early_park = getenv("GRP_NO_EARLY_PARK") != nullptr;
-    if (const char* e = getenv("GRP_SMALL_HIST")) {
-      c->env_small_hist = (uint32_t)atoi(e) / 2u * 2u;
-    }
-    c->env_trace_abort = getenv("GRP_TRACE_ABORT") != nullptr;
-  }
+  c->sw = read_switches();
   int rc = build_seed_tables(c);
   if (rc != GRP_OK) {
     return fail(rc);
@@ -1127,25 +951,26 @@ grp_create(const grp_params* p, grp_ctx** out)
     CREATE_TRY(hipMemsetAsync(c->f.bv, 0, (c->n_bv_words + 3) * sizeof(uint32_t), c->stream));
   }
   for (QuerySlot& sl : c->slot) {
-    CREATE_TRY(sl.d_qctr.reset(8));
+    CREATE_TRY(sl.d_qctr.reset(QCTR_WORDS));
     if (const int arc = slot_dec_alloc(c, sl, 1024); arc != GRP_OK) {
       return fail(arc);
     }
-    CREATE_TRY(hipMemsetAsync(sl.d_qctr, 0, 8 * sizeof(uint64_t), c->stream));
+    CREATE_TRY(hipMemsetAsync(sl.d_qctr, 0, QCTR_WORDS * sizeof(uint64_t), c->stream));
     CREATE_TRY(sl.done.create(hipEventDisableTiming));
     CREATE_TRY(sl.qdone.create(hipEventDisableTiming));
-    CREATE_TRY(sl.d_abort.reset(64)); // (256 bytes) [0] abort flag, [32] tile dispenser (its own 128-byte line), [48] park
-    CREATE_TRY(hipMemsetAsync(sl.d_abort, 0, 256, c->stream));
-    CREATE_TRY(sl.h_abort.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
-    *sl.h_abort = 0;
-    CREATE_TRY(sl.d_sctl.reset(SCT_WORDS));
-    CREATE_TRY(sl.d_rel.reset((uint64_t)STREAM_REL_WGS * 32u));
-    CREATE_TRY(sl.h_cmd.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
-    CREATE_TRY(sl.h_ack.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(sl.h_cmd, 0, 64);
-    memset(sl.h_ack, 0, 64);
-    CREATE_TRY(sl.d_executed.reset(8));
-    CREATE_TRY(sl.h_executed.reset(8, hipHostMallocDefault));
+    QuerySlot::StreamWindow& w = sl.win;
+    CREATE_TRY(w.d_abort.reset(ABORT_WORDS));
+    CREATE_TRY(hipMemsetAsync(w.d_abort, 0, ABORT_BYTES, c->stream));
+    CREATE_TRY(w.h_abort.reset(16, hipHostMallocMapped | hipHostMallocCoherent));
+    *w.h_abort = 0;
+    CREATE_TRY(w.d_sctl.reset(SCT_WORDS));
+    CREATE_TRY(w.d_rel.reset((uint64_t)STREAM_REL_WGS * 32u));
+    CREATE_TRY(w.h_cmd.reset(CMD_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
+    CREATE_TRY(w.h_ack.reset(ACK_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(w.h_cmd, 0, CMD_WORDS * sizeof(uint32_t));
+    memset(w.h_ack, 0, ACK_WORDS * sizeof(uint32_t));
+    CREATE_TRY(w.d_executed.reset(EXE_WORDS));
+    CREATE_TRY(w.h_executed.reset(EXE_WORDS, hipHostMallocDefault));
   }
   CREATE_TRY(c->h_lists.reset(LIST_PREFIX, hipHostMallocDefault));
   CREATE_TRY(c->h_small_tiles.reset(SMALL_TILES, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1162,7 +987,7 @@ grp_destroy(grp_ctx* c)
   if (!c) {
     return;
   }
-  if (getenv("GRP_DEBUG_STATS")) {
+  if (c->sw.debug_stats) {
     fprintf(stderr, "grp stats: direct windows %llu (fallbacks %llu), general windows %llu, redo launches %llu, flagged tiles %llu, FASTQ prefetches dropped %llu\n", (unsigned long long)c->n_direct_windows,
             (unsigned long long)c->n_direct_fallbacks, (unsigned long long)c->n_general_windows, (unsigned long long)c->n_redo_launches, (unsigned long long)c->n_flagged_tiles, (unsigned long long)c->ingest.n_dropped);
   }
@@ -1753,316 +1578,6 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   return GRP_OK;
 }
 
-// ---- query --------------------------------------------------------------------------
-
-} // extern "C"
-
-namespace {
-
-struct QueryRun
-{
-  uint64_t t0 = 0, nt = 0, probes = 0;
-  uint64_t used = 0;    // list arena entries
-  uint64_t flagged = 0; // tiles redone with the worst-case geometry
-};
-
-// a slot's tile summaries, list arena and flagged-tile indices for a window of `nt` tiles
-int
-slot_query_bufs(grp_ctx* c, QuerySlot& sl, uint64_t nt, uint64_t lists)
-{
-  HIP_TRY(c, sl.d_tiles.ensure(nt));
-  HIP_TRY(c, sl.d_lists.ensure(lists));
-  HIP_TRY(c, sl.d_flag_idx.ensure(nt));
-  return GRP_OK;
-}
-
-// a slot's decide scratch for a window of `nt` tiles: three arrays of one capacity
-int
-slot_dec_scratch(grp_ctx* c, QuerySlot& sl, uint64_t nt)
-{
-  if (nt + 1 > sl.d_dec_cap) {
-    clear_all(sl.d_dec_ids, sl.d_dec_asg, sl.d_dec_scratch);
-    sl.d_dec_cap = 0;
-    const uint64_t cap = nt + nt / 4 + 64;
-    HIP_TRY(c, sl.d_dec_ids.reset(cap));
-    HIP_TRY(c, sl.d_dec_asg.reset(cap));
-    HIP_TRY(c, sl.d_dec_scratch.reset(cap));
-    sl.d_dec_cap = cap;
-  }
-  return GRP_OK;
-}
-
-uint64_t
-count_probes(const grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count)
-{
-  uint64_t probes = 0;
-  for (uint32_t i = first; i < first + count; ++i) {
-    const uint32_t ntile = r->len[i] / c->params.tile;
-    if (ntile == 0) {
-      continue;
-    }
-    // all tiles but the last are full; the last may be clipped
-    probes += ((uint64_t)(ntile - 1) * tile_frames(c) + tile_extent(c, r->len[i], ntile - 1).frames) * c->params.h;
-  }
-  return probes;
-}
-
-// Enqueue the query kernel for the window (results stay in c->q->d_tiles /
-// c->q->d_lists).  No synchronisation.
-int
-enqueue_query(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, uint64_t list_cap, QueryRun& q)
-{
-  q.t0 = r->tile0[first];
-  q.nt = r->tile0[first + count] - q.t0;
-  q.probes = count_probes(c, r, first, count);
-  if (const int rc = slot_query_bufs(c, *c->q, q.nt, std::max<uint64_t>(list_cap, 1)); rc != GRP_OK) {
-    return rc;
-  }
-  if (c->q->side_used) {
-    // the slot's previous window may still be in its decision kernel on the other stream
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->q->done, 0));
-    c->q->side_used = false;
-  }
-  const QueryGeom g = query_geom(c, false);
-  Timer t(c, GRP_K_QUERY, q.probes);
-  int lrc = launch_query(c, r, q.nt, q.t0, nullptr, g, list_cap);
-  if (lrc != GRP_OK) {
-    return lrc;
-  }
-  HIP_TRY(c, hipGetLastError());
-  return GRP_OK;
-}
-
-// tiles whose ID set did not fit the small LDS table (indices collected on the
-// device): redo them with the worst-case geometry — same kernel, same arithmetic.
-// Expects h_qctr to hold the counters of the first launch.
-int
-enqueue_redo_flagged(grp_ctx* c, const grp_reads* r, uint64_t list_cap, QueryRun& q)
-{
-  q.flagged = c->q->h_qctr[4];
-  c->n_flagged_tiles += q.flagged;
-  c->n_flagged_distinct += c->q->h_qctr[1];
-  c->n_flagged_list += c->q->h_qctr[2];
-  ++c->n_redo_launches;
-  // continue the list arena where the first launch stopped
-  uint64_t cursor[8] = { 0, 0, 0, c->q->h_qctr[3], 0, 0, 0, 0 };
-  HIP_TRY(c, hipMemcpyAsync(c->q->d_qctr, cursor, sizeof(cursor), hipMemcpyHostToDevice, c->stream));
-  const QueryGeom g = query_geom(c, true);
-  Timer t(c, GRP_K_QUERY, 0);
-  int lrc = launch_query(c, r, q.flagged, q.t0, c->q->d_flag_idx, g, list_cap);
-  if (lrc != GRP_OK) {
-    return lrc;
-  }
-  HIP_TRY(c, hipGetLastError());
-  return GRP_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int
-grp_query_tiles(grp_ctx* c,
-                const grp_reads* r,
-                uint32_t first,
-                uint32_t count,
-                grp_tile_summary* tiles_out,
-                grp_id_count* lists_out,
-                uint64_t list_cap,
-                uint64_t* list_used,
-                grp_query_stats* stats)
-{
-  if (c) {
-    c->carry.valid = false;
-  }
-  if (!c || !r || r->ctx != c || (uint64_t)first + count > r->n_reads) {
-    return set_err(c, GRP_ERR_INVALID, "grp_query_tiles: bad range");
-  }
-  if (!c->finalized) {
-    return set_err(c, GRP_ERR_STATE, "grp_query_tiles before grp_finalize");
-  }
-  if (c->slot[0].busy) {
-    return set_err(c, GRP_ERR_STATE, "grp_query_tiles while an asynchronous window is in flight in slot 0");
-  }
-  c->q = &c->slot[0];
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->q->side_used) {
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->q->done, 0));
-    c->q->side_used = false;
-  }
-  const uint64_t nt = r->tile0[first + count] - r->tile0[first];
-  if (list_used) {
-    *list_used = 0;
-  }
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-  }
-  if (nt == 0) {
-    return GRP_OK;
-  }
-  if (nt > MAX_GRID_WGS) {
-    return set_err(c, GRP_ERR_INVALID, "grp_query_tiles: %llu tiles in one call (limit 2^22)", (unsigned long long)nt);
-  }
-  if (!tiles_out) {
-    return set_err(c, GRP_ERR_INVALID, "grp_query_tiles: tiles_out is NULL");
-  }
-  if (nt <= SMALL_TILES && !c->env_no_direct) { // (GRP_NO_DIRECT, developer hook: force the general path)
-    // latency path (insert-heavy phases query one read at a time): the kernel
-    // writes summaries and lists straight into mapped host memory, no copies,
-    // no counters; one stream synchronisation
-    const uint64_t t0 = r->tile0[first];
-    const uint64_t probes = count_probes(c, r, first, count);
-    constexpr uint32_t PENDING = 0xFFFFFFFEu; // list_n of a summary the kernel has not written yet
-    for (uint64_t i = 0; i < nt; ++i) {
-      c->h_small_tiles[i].list_n = PENDING;
-    }
-    {
-      const QueryGeom g = query_geom(c, false);
-      Timer t(c, GRP_K_QUERY_LAT, probes);
-      int lrc = launch_query(c, r, nt, t0, nullptr, g, (uint64_t)SMALL_TILES * SMALL_STRIDE, c->h_small_tiles.dev, c->h_small_lists.dev, SMALL_STRIDE);
-      if (lrc != GRP_OK) {
-        return lrc;
-      }
-    }
-    HIP_TRY(c, hipGetLastError());
-    // the summaries arrive in host memory while the launch runs (lists first, the word with
-    // list_n last): spin on them instead of waiting for the end-of-kernel signal; a launch
-    // that never delivers falls back to the stream synchronisation
-    {
-      uint64_t i = 0;
-      uint32_t spins = 0;
-      while (i < nt) {
-        if (__atomic_load_n(&c->h_small_tiles[i].list_n, __ATOMIC_ACQUIRE) != PENDING) {
-          ++i;
-          continue;
-        }
-        __builtin_ia32_pause();
-        if ((++spins & 0xFFFFu) == 0 && hipStreamQuery(c->stream) != hipErrorNotReady) {
-          HIP_TRY(c, hipStreamSynchronize(c->stream));
-          for (uint64_t j = i; j < nt; ++j) {
-            if (__atomic_load_n(&c->h_small_tiles[j].list_n, __ATOMIC_ACQUIRE) == PENDING) {
-              return set_err(c, GRP_ERR_HIP, "grp_query_tiles: the launch ended without delivering tile %llu", (unsigned long long)j);
-            }
-          }
-          break;
-        }
-      }
-    }
-    ++c->n_direct_windows;
-    bool any_flagged = false;
-    uint64_t used = 0;
-    for (uint64_t i = 0; i < nt; ++i) {
-      any_flagged = any_flagged || c->h_small_tiles[i].list_n == GRP_TILE_FLAGGED;
-      used += c->h_small_tiles[i].list_n;
-    }
-    if (!any_flagged) {
-      if (list_used) {
-        *list_used = used;
-      }
-      if (used > list_cap) {
-        return set_err(c, GRP_ERR_NOMEM, "grp_query_tiles: %llu list entries needed, capacity %llu", (unsigned long long)used, (unsigned long long)list_cap);
-      }
-      uint64_t off = 0;
-      for (uint64_t i = 0; i < nt; ++i) {
-        grp_tile_summary ts = c->h_small_tiles[i];
-        grp_id_count* src = c->h_small_lists + i * SMALL_STRIDE;
-        if (ts.list_n) {
-          memcpy(lists_out + off, src, ts.list_n * sizeof(grp_id_count));
-          if (ts.list_n > 1) {
-            std::sort(lists_out + off, lists_out + off + ts.list_n, [](const grp_id_count& a, const grp_id_count& b) {
-              return a.count != b.count ? a.count > b.count : a.id < b.id;
-            });
-          }
-        }
-        ts.list_off = (uint32_t)off;
-        off += ts.list_n;
-        tiles_out[i] = ts;
-        if (stats) {
-          stats->hits += ts.hits;
-          stats->misses += ts.misses;
-        }
-      }
-      if (stats) {
-        stats->queries = probes / c->params.h;
-      }
-      return GRP_OK;
-    }
-    // a tile needs the worst-case table or a longer list: take the general path
-    ++c->n_direct_fallbacks;
-  }
-  if (nt > c->h_tiles.cap) {
-    HIP_TRY(c, c->h_tiles.reset(std::max<uint64_t>(nt + nt / 4, 4096), hipHostMallocDefault));
-  }
-  ++c->n_general_windows;
-  QueryRun q;
-  int rc = enqueue_query(c, r, first, count, list_cap, q);
-  if (rc != GRP_OK) {
-    return rc;
-  }
-  const uint64_t prefix = std::min<uint64_t>(list_cap, LIST_PREFIX);
-  // one round trip: counters, tile summaries and the first LIST_PREFIX list
-  // entries come back together; the counters are re-zeroed for the next call
-  auto fetch = [&]() -> int {
-    HIP_TRY(c, hipMemcpyAsync(c->q->h_qctr, c->q->d_qctr, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->h_tiles, c->q->d_tiles, nt * sizeof(grp_tile_summary), hipMemcpyDeviceToHost, c->stream));
-    if (prefix) {
-      HIP_TRY(c, hipMemcpyAsync(c->h_lists, c->q->d_lists, prefix * sizeof(grp_id_count), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipMemsetAsync(c->q->d_qctr, 0, 8 * sizeof(uint64_t), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GRP_OK;
-  };
-  rc = fetch();
-  if (rc != GRP_OK) {
-    return rc;
-  }
-  if (c->q->h_qctr[4]) {
-    rc = enqueue_redo_flagged(c, r, list_cap, q);
-    if (rc == GRP_OK) {
-      rc = fetch();
-    }
-    if (rc != GRP_OK) {
-      return rc;
-    }
-  }
-  drain_events(c);
-  memcpy(tiles_out, c->h_tiles, nt * sizeof(grp_tile_summary));
-  const uint64_t used = c->q->h_qctr[3];
-  if (list_used) {
-    *list_used = used;
-  }
-  if (stats) {
-    stats->queries = q.probes / c->params.h; /* one query per frame (goldrush_path.cpp:567-568) */
-    for (uint64_t i = 0; i < nt; ++i) {
-      stats->hits += tiles_out[i].hits;
-      stats->misses += tiles_out[i].misses;
-    }
-  }
-  if (used > list_cap) {
-    return set_err(c, GRP_ERR_NOMEM, "grp_query_tiles: %llu list entries needed, capacity %llu", (unsigned long long)used, (unsigned long long)list_cap);
-  }
-  if (used) {
-    if (!lists_out) {
-      return set_err(c, GRP_ERR_INVALID, "grp_query_tiles: lists_out is NULL");
-    }
-    if (used <= prefix) {
-      memcpy(lists_out, c->h_lists, used * sizeof(grp_id_count));
-    } else {
-      HIP_TRY(c, hipMemcpy(lists_out, c->q->d_lists, used * sizeof(grp_id_count), hipMemcpyDeviceToHost));
-    }
-    // canonical order inside each tile's list: count descending, id ascending
-    for (uint64_t i = 0; i < nt; ++i) {
-      grp_tile_summary& ts = tiles_out[i];
-      if (ts.list_n > 1) {
-        std::sort(lists_out + ts.list_off, lists_out + ts.list_off + ts.list_n, [](const grp_id_count& a, const grp_id_count& b) {
-          return a.count != b.count ? a.count > b.count : a.id < b.id;
-        });
-      }
-    }
-  }
-  return GRP_OK;
-}
-
 } // extern "C"
 
 namespace {
@@ -2112,8 +1627,8 @@ int
 classify_enqueue_fetch(grp_ctx* c, QuerySlot& sl, hipStream_t st)
 {
   if (sl.count == 0) { // no decide launch: the counters alone
-    HIP_TRY(c, hipMemcpyAsync(sl.h_qctr, sl.d_qctr, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemsetAsync(sl.d_qctr, 0, 8 * sizeof(uint64_t), st));
+    HIP_TRY(c, hipMemcpyAsync(sl.h_qctr, sl.d_qctr, QCTR_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemsetAsync(sl.d_qctr, 0, QCTR_WORDS * sizeof(uint64_t), st));
   } else {
     HIP_TRY(c, hipMemcpyAsync(sl.h_dec_raw, sl.d_dec_raw, ((size_t)sl.count + 2) * sizeof(grp_read_decision), hipMemcpyDeviceToHost, st));
   }
@@ -2220,7 +1735,7 @@ grp_classify_reads_begin(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_
 int
 grp_classify_reads_end(grp_ctx* c, uint32_t slot, grp_read_decision* out)
 {
-  if (!c || slot > 1 || !c->slot[slot].busy || c->slot[slot].streaming) {
+  if (!c || slot > 1 || !c->slot[slot].busy || c->slot[slot].win.streaming) {
     return set_err(c, GRP_ERR_STATE, "grp_classify_reads_end: no window in flight in this slot");
   }
   QuerySlot& sl = c->slot[slot];
@@ -2236,8 +1751,8 @@ grp_classify_reads_end(grp_ctx* c, uint32_t slot, grp_read_decision* out)
   c->q = &sl;
   HIP_TRY(c, hipEventSynchronize(sl.done));
   for (int attempt = 0; attempt < 8; ++attempt) {
-    if (sl.h_qctr[3] > sl.list_cap) { // list arena too small: grow (with room for the lists of tiles that are redone) and redo the window
-      sl.list_cap = 2 * sl.h_qctr[3] + 4096;
+    if (sl.h_qctr[QCTR_LIST_CURSOR] > sl.list_cap) { // list arena too small: grow (with room for the lists of tiles that are redone) and redo the window
+      sl.list_cap = 2 * sl.h_qctr[QCTR_LIST_CURSOR] + 4096;
       int rc = classify_enqueue(c, sl, false);
       if (rc != GRP_OK) {
         return rc;
@@ -2245,7 +1760,7 @@ grp_classify_reads_end(grp_ctx* c, uint32_t slot, grp_read_decision* out)
       HIP_TRY(c, hipEventSynchronize(sl.done));
       continue;
     }
-    if (sl.h_qctr[4]) { // some tiles needed the worst-case table: redo them, decide again
+    if (sl.h_qctr[QCTR_FLAGGED]) { // some tiles needed the worst-case table: redo them, decide again
       QueryRun q;
       q.t0 = sl.t0;
       int rc = enqueue_redo_flagged(c, sl.reads, sl.list_cap, q);
@@ -2296,547 +1811,11 @@ grp_classify_reads(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t coun
   return rc;
 }
 
-// ---- streaming window --------------------------------------------------------------
+} // extern "C"
 
-// the scratch table of a whole-read insert (k_insert_collect / k_insert_apply and the in-launch
-// insert of a streaming window): room for `max_ranks` distinct ranks at load <= 1/2.  Growing it
-// waits for the stream (never while a window that holds its address is in flight: see the caller).
-static int
-ensure_insert_table(grp_ctx* c, uint64_t max_ranks)
-{
-  const uint64_t want = next_pow2_64(max_ranks * 2);
-  if (want <= c->ir_cap) {
-    return GRP_OK;
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  clear_all(c->d_ir_keys, c->d_ir_masks, c->d_ir_locs, c->d_ir_slots, c->d_fp_tab[0], c->d_fp_tab[1]);
-  c->ir_cap = 0;
-  HIP_TRY(c, c->d_fp_tab[0].reset(want));
-  HIP_TRY(c, c->d_fp_tab[1].reset(want));
-  HIP_TRY(c, c->d_ir_keys.reset(want));
-  HIP_TRY(c, c->d_ir_masks.reset(want));
-  HIP_TRY(c, c->d_ir_locs.reset(want));
-  HIP_TRY(c, c->d_ir_slots.reset(want));
-  HIP_TRY(c, hipMemsetAsync(c->d_ir_keys, 0, want * 8, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_ir_masks, 0, want * 8, c->stream));
-  if (!c->d_ir_counter) {
-    HIP_TRY(c, c->d_ir_counter.reset(2));
-    HIP_TRY(c, hipMemsetAsync(c->d_ir_counter, 0, 2 * sizeof(uint32_t), c->stream));
-  }
-  c->ir_cap = want;
-  return GRP_OK;
-}
+#include "grp_stream.inc"
 
-static int
-stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, uint32_t stripe_reads, uint32_t n_owners, uint32_t owner, const grp_read_decision** decisions, bool want_resumable);
-
-int
-grp_classify_stream_begin(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, const grp_read_decision** decisions)
-{
-  return stream_begin_impl(c, r, first, count, dp, slot, 0, 1, 0, decisions, false);
-}
-
-int
-grp_classify_stream_begin_striped(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, uint32_t stripe_reads, uint32_t n_owners, uint32_t owner, const grp_read_decision** decisions)
-{
-  return stream_begin_impl(c, r, first, count, dp, slot, stripe_reads, n_owners, owner, decisions, false);
-}
-
-int
-grp_classify_stream_begin_resumable(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, const grp_read_decision** decisions)
-{
-  return stream_begin_impl(c, r, first, count, dp, slot, 0, 1, 0, decisions, true);
-}
-
-int
-grp_classify_stream_begin_striped_resumable(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, uint32_t stripe_reads, uint32_t n_owners, uint32_t owner, const grp_read_decision** decisions)
-{
-  return stream_begin_impl(c, r, first, count, dp, slot, stripe_reads, n_owners, owner, decisions, true);
-}
-
-int
-grp_classify_stream_insert_done(grp_ctx* c, uint32_t slot)
-{
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_insert_done: no streaming window in this slot");
-  }
-  QuerySlot& sl = c->slot[slot];
-  if (__atomic_load_n(&sl.h_ack[0], __ATOMIC_ACQUIRE) == sl.cmd_seq) {
-    return 1;
-  }
-  if (__atomic_load_n(&sl.h_ack[1], __ATOMIC_ACQUIRE) != 0) {
-    return 2;
-  }
-  const hipError_t e = hipEventQuery(sl.done);
-  if (e == hipSuccess) {
-    return __atomic_load_n(&sl.h_ack[0], __ATOMIC_ACQUIRE) == sl.cmd_seq ? 1 : 2;
-  }
-  if (e != hipErrorNotReady) {
-    return set_err(c, GRP_ERR_HIP, "grp_classify_stream_insert_done: %s", hipGetErrorString(e));
-  }
-  return 0;
-}
-
-int
-grp_classify_stream_resumable(grp_ctx* c, uint32_t slot)
-{
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
-    return 0;
-  }
-  return c->slot[slot].resumable ? 1 : 0;
-}
-
-static int
-stream_begin_impl(grp_ctx* c, const grp_reads* r, uint32_t first, uint32_t count, const grp_decide_params* dp, uint32_t slot, uint32_t stripe_reads, uint32_t n_owners, uint32_t owner, const grp_read_decision** decisions, bool want_resumable)
-{
-  if (c) {
-    c->carry.valid = false;
-  }
-  if (!c || !r || r->ctx != c || (uint64_t)first + count > r->n_reads || !dp || slot > 1 || !decisions || n_owners == 0 || owner >= n_owners ||
-      (n_owners > 1 && stripe_reads == 0)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_classify_stream_begin: bad argument");
-  }
-  if (!c->finalized) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_begin before grp_finalize");
-  }
-  if (!c->coherent_arch) {
-    // the hand-over between workgroups inside the launch relies on agent-scope accesses being
-    // served by the memory side, in issue order (gfx942 / gfx950); not a portable guarantee
-    return set_err(c, GRP_ERR_INVALID, "grp_classify_stream_begin: streaming windows are only enabled on gfx942 / gfx950 (this device is %s)", c->arch.c_str());
-  }
-  QuerySlot& sl = c->slot[slot];
-  if (sl.busy) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_begin: slot %u still has a window in flight", slot);
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t t0 = r->tile0[first];
-  const uint64_t nt = r->tile0[first + count] - t0;
-  if (nt > (1u << 30)) {
-    return set_err(c, GRP_ERR_INVALID, "grp_classify_stream_begin: %llu tiles in one call (limit 2^30)", (unsigned long long)nt);
-  }
-  {
-    // Growing a buffer frees the old one, and hipFree / hipHostFree wait for the device.  A
-    // resumable window in the other slot may be parked, waiting for THIS thread's answer — the
-    // wait would never end (found on C2: a window with a record number of tiles, begun while
-    // the current one still had an insert to take; the launch gave up after its idle limit).
-    // Not now, then: the caller begins this window once the other one has ended.
-    const QuerySlot& other = c->slot[slot ^ 1u];
-    const bool grows = count > sl.h_sdec.cap || std::max<uint64_t>(count, 1) > sl.d_tiles_done.cap || nt + 1 > sl.d_dec_cap || std::max<uint64_t>(nt, 1) > sl.d_tiles.cap ||
-                       std::max<uint64_t>(sl.d_lists.cap, (want_resumable ? 8 : 4) * nt + 4096) > sl.d_lists.cap || std::max<uint64_t>(nt, 1) > sl.d_flag_idx.cap ||
-                       (want_resumable && std::max<uint64_t>(nt, 1) > sl.d_tile_ver.cap);
-    if (grows && other.busy && other.streaming && other.resumable) {
-      return set_err(c, GRP_ERR_BUSY, "grp_classify_stream_begin: the slot's buffers must grow while a resumable window is in flight in the other slot: begin this window when that one has ended");
-    }
-  }
-  c->q = &sl;
-  if (count > sl.h_sdec.cap) {
-    HIP_TRY(c, sl.h_sdec.reset(std::max<uint64_t>((uint64_t)count + count / 2, 1024), hipHostMallocMapped | hipHostMallocCoherent));
-  }
-  int rc = ensure_dev(c, sl.d_tiles_done, std::max<uint64_t>(count, 1));
-  if (rc != GRP_OK) {
-    return rc;
-  }
-  if (rc = slot_dec_scratch(c, sl, nt); rc != GRP_OK) {
-    return rc;
-  }
-  // (a window that keeps tiles across its inserts does not start its list arena over at each of them: twice the room)
-  sl.list_cap = std::max<uint64_t>(sl.d_lists.cap, (want_resumable ? 8 : 4) * nt + 4096);
-  rc = slot_query_bufs(c, sl, std::max<uint64_t>(nt, 1), sl.list_cap);
-  if (rc == GRP_OK && want_resumable) { // (round 6) what a window keeps across an in-launch insert: a mark per tile (DevStreamCtl::tile_ver)
-    rc = ensure_dev(c, sl.d_tile_ver, std::max<uint64_t>(nt, 1));
-  }
-  if (rc != GRP_OK) {
-    return rc;
-  }
-  // striped window (several ranks share it): stripe t = reads [t*stripe, (t+1)*stripe) of
-  // the window belongs to rank t % n_owners; this launch draws only the owner's tiles
-  uint64_t n_mine = nt;
-  const bool striped = n_owners > 1;
-  if (striped) {
-    n_mine = 0;
-    for (uint32_t j = 0; j < count; ++j) {
-      if ((j / stripe_reads) % n_owners == owner) {
-        n_mine += r->tile0[first + j + 1] - r->tile0[first + j];
-      }
-    }
-    if (n_mine > sl.d_stripe_tiles.cap) {
-      clear_all(sl.h_stripe_tiles, sl.d_stripe_tiles);
-      const uint64_t cap = n_mine + n_mine / 4 + 1024;
-      HIP_TRY(c, sl.h_stripe_tiles.reset(cap, hipHostMallocDefault));
-      HIP_TRY(c, sl.d_stripe_tiles.reset(cap));
-    }
-    uint64_t w = 0;
-    for (uint32_t j = 0; j < count; ++j) {
-      if ((j / stripe_reads) % n_owners == owner) {
-        for (uint64_t t = r->tile0[first + j]; t < r->tile0[first + j + 1]; ++t) {
-          sl.h_stripe_tiles[w++] = (uint32_t)(t - t0);
-        }
-      }
-    }
-  }
-  // reads without a single tile are never completed by a workgroup: decided here
-  memset(sl.h_sdec, 0, (size_t)count * sizeof(grp_read_decision));
-  uint32_t n_decidable = 0; // ... of THIS launch: a striped window completes when its own stripes' reads are decided
-  uint64_t max_tiles_read = 0;
-  for (uint32_t j = 0; j < count; ++j) {
-    const uint64_t ntj = r->tile0[first + j + 1] - r->tile0[first + j];
-    max_tiles_read = std::max(max_tiles_read, ntj);
-    if (ntj == 0) {
-      grp_read_decision d{};
-      gr::core::decide(dp->threshold, dp->unassigned_min, dp->assigned_max, 0, nullptr, nullptr, nullptr, nullptr, nullptr, d);
-      d.pad = 1;
-      sl.h_sdec[j] = d;
-    } else if (!striped || (j / stripe_reads) % n_owners == owner) {
-      ++n_decidable;
-    }
-  }
-  // A resumable window (grp_classify_stream_begin_resumable) does not end where it parks: it
-  // waits for the host's word — _abort, or _insert: the insert the host has committed, applied
-  // inside the launch.  Not when the scratch table would have to grow while the other slot's
-  // window holds its address (the window is then an ordinary one; _insert says so).
-  const bool resume_off = c->env_stream_resume_off; // GRP_STREAM_RESUME=off (developer switch / tests, read at grp_create): every window ends where it parks
-  sl.resumable = false;
-  if (want_resumable && !resume_off && n_mine != 0) {
-    const uint64_t need_ranks = max_tiles_read * tile_frames(c) * c->params.h;
-    const bool other_streaming = c->slot[slot ^ 1u].busy && c->slot[slot ^ 1u].streaming;
-    if (next_pow2_64(need_ranks * 2) <= c->ir_cap || !other_streaming) {
-      rc = ensure_insert_table(c, need_ranks);
-      if (rc != GRP_OK) {
-        return rc;
-      }
-      sl.resumable = true;
-    }
-  }
-  sl.gen = 1;
-  sl.cmd_seq = 0;
-  sl.stripe_reads = striped ? stripe_reads : 0;
-  sl.n_owners = n_owners;
-  sl.owner = owner;
-  __atomic_store_n(sl.h_abort.p, 0u, __ATOMIC_RELEASE);
-  sl.reads = r;
-  sl.first = first;
-  sl.count = count;
-  sl.dp = *dp;
-  sl.nt = nt;
-  sl.t0 = t0;
-  sl.busy = true;
-  sl.streaming = true;
-  *decisions = sl.h_sdec;
-  if (sl.side_used) {
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.done, 0));
-    sl.side_used = false;
-  }
-  if (n_mine) {
-    if (striped) {
-      HIP_TRY(c, hipMemcpyAsync(sl.d_stripe_tiles, sl.h_stripe_tiles, n_mine * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(c, hipMemsetAsync(sl.d_abort, 0, 256, c->stream));
-    HIP_TRY(c, hipMemsetAsync(sl.d_abort + 48, 0xFF, sizeof(uint32_t), c->stream)); // park: nothing stale yet
-    HIP_TRY(c, hipMemsetAsync(sl.d_tiles_done, 0, (size_t)count * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(sl.d_executed, 0, 8 * sizeof(unsigned long long), c->stream));
-    if (sl.resumable) {
-      HIP_TRY(c, hipMemsetAsync(sl.d_sctl, 0, SCT_WORDS * sizeof(uint32_t), c->stream));
-      HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sl.d_sctl + SCT_GEN), 1, 1, c->stream));
-      HIP_TRY(c, hipMemsetAsync(sl.d_tile_ver, 0, std::max<uint64_t>(nt, 1) * sizeof(uint32_t), c->stream));
-      HIP_TRY(c, hipMemsetAsync(sl.d_rel, 0, (size_t)STREAM_REL_WGS * 32u * sizeof(uint32_t), c->stream));
-      // the changed-slot sets of the window's inserts start empty (the sets of the window before may hold its last two)
-      HIP_TRY(c, hipMemsetAsync(c->d_fp_tab[0], 0, c->ir_cap * sizeof(uint32_t), c->stream));
-      HIP_TRY(c, hipMemsetAsync(c->d_fp_tab[1], 0, c->ir_cap * sizeof(uint32_t), c->stream));
-      __atomic_store_n(&sl.h_cmd[0], 0u, __ATOMIC_RELEASE);
-      sl.h_ack[0] = 0;
-      sl.h_ack[1] = 0;
-    }
-    DevStreamCtl sc;
-    sc.first = first;
-    sc.tiles_done = sl.d_tiles_done;
-    sc.abort = sl.d_abort;
-    sc.abort_host = sl.h_abort.dev;
-    sc.next_tile = sl.d_abort + 32;
-    sc.park = sl.d_abort + 48;
-    sc.early_park = c->env_no_early_park ? 0u : 1u; // GRP_NO_EARLY_PARK, developer hook (the engine-level API contract assumes 1)
-    sc.n_tiles = (uint32_t)n_mine;
-    sc.dec = sl.h_sdec.dev;
-    sc.executed = sl.d_executed;
-    sc.dp = *dp;
-    sc.g_ids = sl.d_dec_ids;
-    sc.g_asg = sl.d_dec_asg;
-    sc.g_scratch = sl.d_dec_scratch;
-    sc.n_reads = count;
-    sc.n_decidable = n_decidable;
-    if (sl.resumable) {
-      sc.ctl = sl.d_sctl;
-      sc.cmd_while_busy = striped ? 1u : 0u;
-      sc.cmd_host = sl.h_cmd.dev;
-      sc.ack_host = sl.h_ack.dev;
-      sc.tb = InsertTable{ c->d_ir_keys, c->d_ir_masks, c->d_ir_locs, c->d_ir_slots, c->d_ir_counter, c->ir_cap - 1 };
-      static const bool dbg_on = getenv("GRP_STREAM_DEBUG") != nullptr;
-      if (dbg_on) {
-        if (!sl.d_dbg) {
-          HIP_TRY(c, sl.d_dbg.reset(8192));
-        }
-        HIP_TRY(c, hipMemsetAsync(sl.d_dbg, 0, 8192 * sizeof(uint32_t), c->stream));
-        sc.dbg = sl.d_dbg;
-      }
-      sc.rel = sl.d_rel;
-      sc.tile_ver = sl.d_tile_ver;
-      sc.fp_tab[0] = c->d_fp_tab[0];
-      sc.fp_tab[1] = c->d_fp_tab[1];
-      sc.fp_mask = (uint32_t)(c->ir_cap - 1);
-      sc.n_fp = 2; // asked for; launch_query gives what this geometry's LDS has room for beside three workgroups per CU (0: nothing is kept)
-      static const double wait_s = [] { // developer hook: time limit of a grid-wide wait (seconds)
-        const char* e = getenv("GRP_STREAM_WAIT_S");
-        return e ? atof(e) : 2.0;
-      }();
-      sc.timeout_ticks = (unsigned long long)(wait_s * 1e8); // wall_clock64 counts at 100 MHz
-    }
-    const QueryGeom g = query_geom(c, false);
-    {
-      Timer t(c, GRP_K_QUERY, 0); // the probes actually executed are added at _end
-      int lrc = launch_query(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc);
-      if (lrc == GRP_ERR_BUSY && sl.resumable) {
-        // the runtime cannot keep every workgroup of the window resident (the device is shared): the window is
-        // begun in its classic form — it ends where it parks, grp_classify_stream_insert says GRP_ERR_STATE
-        sl.resumable = false;
-        sc.ctl = nullptr;
-        ++c->n_stream_coop_refused;
-        lrc = launch_query(c, r, n_mine, t0, striped ? sl.d_stripe_tiles : nullptr, g, sl.list_cap, nullptr, nullptr, 0, &sc);
-      }
-      if (lrc != GRP_OK) {
-        sl.busy = false;
-        sl.streaming = false;
-        return lrc;
-      }
-      HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipMemcpyAsync(sl.h_executed, sl.d_executed, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemsetAsync(sl.d_qctr, 0, 8 * sizeof(uint64_t), c->stream));
-  } else {
-    memset(sl.h_executed, 0, 8 * sizeof(unsigned long long));
-  }
-  HIP_TRY(c, hipEventRecord(sl.done, c->stream));
-  return GRP_OK;
-}
-
-int
-grp_classify_stream_abort(grp_ctx* c, uint32_t slot)
-{
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_abort: no streaming window in this slot");
-  }
-  __atomic_store_n(c->slot[slot].h_abort.p, 1u, __ATOMIC_RELEASE);
-  return GRP_OK;
-}
-
-int
-grp_classify_stream_poll(grp_ctx* c, uint32_t slot)
-{
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_poll: no streaming window in this slot");
-  }
-  hipError_t e = hipEventQuery(c->slot[slot].done);
-  if (e == hipSuccess) {
-    return 1;
-  }
-  if (e == hipErrorNotReady) {
-    return 0;
-  }
-  return set_err(c, GRP_ERR_HIP, "grp_classify_stream_poll: %s", hipGetErrorString(e));
-}
-
-int
-grp_classify_stream_end(grp_ctx* c, uint32_t slot, uint32_t* reads_decided)
-{
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_end: no streaming window in this slot");
-  }
-  QuerySlot& sl = c->slot[slot];
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipEventSynchronize(sl.done));
-  sl.busy = false;
-  sl.streaming = false;
-  c->kstat[GRP_K_QUERY].units += *sl.h_executed;
-  for (int i = 1; i < 8; ++i) { // what the window's in-launch inserts kept and redid (grp_debug_stream_stats)
-    c->n_stream_keep[i] += sl.h_executed[i];
-  }
-  if (reads_decided) {
-    uint32_t n = 0;
-    for (uint32_t j = 0; j < sl.count; ++j) {
-      n += sl.h_sdec[j].pad != 0;
-    }
-    *reads_decided = n;
-  }
-  if (c->pending.size() > 64) {
-    drain_events(c);
-  }
-  if (sl.resumable) {
-    sl.resumable = false;
-    const uint32_t code = __atomic_load_n(&sl.h_ack[1], __ATOMIC_ACQUIRE);
-    const uint32_t applied = __atomic_load_n(&sl.h_ack[0], __ATOMIC_ACQUIRE);
-    if ((code == 2 || code == 1) && sl.d_dbg) { // developer: where every workgroup was
-      std::vector<uint32_t> st(8192);
-      if (hipMemcpy(st.data(), sl.d_dbg, st.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-        std::string line;
-        for (size_t i = 0; i < st.size(); ++i) {
-          if (i < 1024 && st[i] != 0 && ((st[i] >> 28) != 5u || (st[i] & 0xFFFFu) != ((sl.cmd_seq << 1) & 0xFFFFu))) {
-            char b[64];
-            snprintf(b, sizeof(b), " %zu:%08x", i, st[i]);
-            line += b;
-          }
-        }
-        {
-          // when the workgroups came to the event and reached the first wait (100 MHz ticks, relative to the earliest)
-          const uint32_t grid = std::min<uint32_t>(st[4095], 1000u);
-          uint32_t t_min = 0xFFFFFFFFu;
-          for (uint32_t i = 0; i < grid; ++i) {
-            t_min = std::min(t_min, st[2048 + i]);
-          }
-          std::vector<std::pair<uint32_t, uint32_t>> late;
-          for (uint32_t i = 0; i < grid; ++i) {
-            late.push_back({ st[2048 + i] - t_min, i });
-          }
-          std::sort(late.begin(), late.end());
-          char b[200];
-          snprintf(b, sizeof(b), " | grid %u; reached the first wait (us behind the earliest): median %.1f", st[4095], late[grid / 2].first * 1e-2);
-          line += b;
-          for (uint32_t q = grid >= 6 ? grid - 6 : 0; q < grid; ++q) {
-            const uint32_t w = late[q].second;
-            snprintf(b, sizeof(b), "; wg %u %.1f us (came to the event %.1f us earlier; began %.1f us before that; xcc %u se %u cu %u)", w, late[q].first * 1e-2, (st[2048 + w] - st[1024 + w]) * 1e-2,
-                     (st[1024 + w] - st[4096 + w]) * 1e-2, st[5120 + w] >> 16, (st[5120 + w] >> 13) & 7u, (st[5120 + w] >> 8) & 15u);
-            line += b;
-          }
-          uint32_t t_start = 0xFFFFFFFFu, t_last = 0;
-          for (uint32_t i = 0; i < grid; ++i) {
-            t_start = std::min(t_start, st[4096 + i]);
-          }
-          uint32_t n_late = 0;
-          for (uint32_t i = 0; i < grid; ++i) {
-            t_last = std::max(t_last, st[4096 + i] - t_start);
-            n_late += (st[4096 + i] - t_start) > 100000u ? 1u : 0u; // more than a millisecond behind the first
-          }
-          snprintf(b, sizeof(b), " | the last workgroup began %.1f us behind the first, %u of them more than 1 ms behind", t_last * 1e-2, n_late);
-          line += b;
-        }
-        fprintf(stderr, "  last streaming launch: %u workgroups, %u bytes of LDS each\n", c->dbg_stream_grid, c->dbg_stream_lds);
-        fprintf(stderr, "  window: reads [%u, %u), %llu tiles; command: read %u tiles [%u, %u) block %u first id %u offset %u resume read %u tile %u decided base %u gen %u\n", sl.first, sl.first + sl.count, (unsigned long long)sl.nt,
-                sl.h_cmd[1], sl.h_cmd[2], sl.h_cmd[3], sl.h_cmd[4], sl.h_cmd[5], sl.h_cmd[6], sl.h_cmd[7], sl.h_cmd[8], sl.h_cmd[9], sl.h_cmd[10]);
-        fprintf(stderr, "grp_classify_stream_end: code %u, first to give up: wait %u, workgroup %u, %u of the insert's %u workgroups had arrived; workgroups not inside insert %u (index:state):%s\n", code, sl.h_ack[14] & 0xFFFFu, sl.h_ack[14] >> 16, sl.h_ack[15] & 0xFFFFu, sl.h_ack[15] >> 16, sl.cmd_seq, line.c_str());
-      }
-    }
-    if (code == 2) {
-      return set_err(c, GRP_ERR_STATE, "grp_classify_stream_end: a grid-wide wait timed out in the middle of an insert (the ID array may be inconsistent); first to give up: wait %u, workgroup %u, %u of the insert's %u workgroups had arrived",
-                     sl.h_ack[14] & 0xFFFFu, sl.h_ack[14] >> 16, sl.h_ack[15] & 0xFFFFu, sl.h_ack[15] >> 16);
-    }
-    if (code == 3) {
-      // The parked window was told nothing for its idle limit (16 x GRP_STREAM_WAIT_S: a host stopped by a
-      // debugger or SIGSTOP, a stalled file system) and left by itself.  It had modified nothing: not an error
-      //  — the records it did not produce stay open and the caller begins the window again behind
-      // the last one it has; what the launch was waiting on is kept as the context's last message.
-      uint32_t first_open = sl.count;
-      for (uint32_t j = 0; j < sl.count; ++j) {
-        if (sl.h_sdec[j].pad != sl.gen) {
-          first_open = j;
-          break;
-        }
-      }
-      ++c->n_stream_idle_exits;
-      (void)set_err(c, GRP_OK,
-                    "grp_classify_stream_end: the parked window was never told how to go on (idle time limit) and left; launch: park %u decided %u next tile %u / %llu event %u command seen %u "
-                    "generation %u; host: %u reads, generation %u, commands posted %u applied %u, first open record %u",
-                    sl.h_ack[8], sl.h_ack[9], sl.h_ack[10], (unsigned long long)sl.nt, sl.h_ack[11], sl.h_ack[12], sl.h_ack[13], sl.count, sl.gen, sl.cmd_seq, applied, first_open);
-      if (c->env_trace_abort) {
-        fprintf(stderr, "%s\n", c->err.c_str());
-      }
-    }
-    if (applied != sl.cmd_seq) {
-      // The launch ended without the insert posted last (an abort overtook it or the launch had left already: 1; the
-      // first grid-wide wait timed out, the device is shared: 2).  Only the scratch table may have been
-      // touched; the caller applies the insert with grp_insert_read.
-      HIP_TRY(c, hipMemsetAsync(c->d_ir_keys, 0, c->ir_cap * 8, c->stream));
-      HIP_TRY(c, hipMemsetAsync(c->d_ir_masks, 0, c->ir_cap * 8, c->stream));
-      return code == 1 ? 2 : 1;
-    }
-  }
-  return GRP_OK;
-}
-
-int
-grp_classify_stream_insert(grp_ctx* c, uint32_t slot, uint32_t read_idx, uint32_t tile_start, uint32_t tile_end, uint32_t block_tiles, uint32_t first_id, uint32_t id_offset, uint32_t* generation)
-{
-  if (c) {
-    c->carry.valid = false;
-  }
-  if (!c || slot > 1 || !c->slot[slot].busy || !c->slot[slot].streaming || block_tiles == 0 || id_offset > 1 || !generation) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_insert: no streaming window in this slot / bad argument");
-  }
-  QuerySlot& sl = c->slot[slot];
-  const grp_reads* r = sl.reads;
-  if (!sl.resumable) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_insert: this window ends where it parks (not begun with grp_classify_stream_begin_resumable, or GRP_STREAM_RESUME=off)");
-  }
-  if (read_idx < sl.first || read_idx >= sl.first + sl.count) {
-    return set_err(c, GRP_ERR_INVALID, "grp_classify_stream_insert: read %u is not in the window", read_idx);
-  }
-  const uint64_t ntile = r->tile0[read_idx + 1] - r->tile0[read_idx];
-  if (tile_start >= tile_end || tile_end > ntile) {
-    return set_err(c, GRP_ERR_INVALID, "grp_classify_stream_insert: tiles [%u,%u) outside the read's %llu tiles", tile_start, tile_end, (unsigned long long)ntile);
-  }
-  if ((tile_end - tile_start + block_tiles - 1) / block_tiles > 64) {
-    return set_err(c, GRP_ERR_STATE, "grp_classify_stream_insert: more than 64 ID blocks (the caller ends the window and uses grp_insert_read)");
-  }
-  if (sl.cmd_seq != 0 && c->env_trace_abort) { // GRP_TRACE_ABORT, developer trace: phase times of the previous in-launch insert (100 MHz ticks)
-    static double t_ph[4] = { 0, 0, 0, 0 };
-    static uint64_t n_tr = 0;
-    for (int i = 0; i < 4; ++i) {
-      t_ph[i] += sl.h_ack[4 + i] * 1e-2;
-    }
-    if (getenv("GRP_TRACE_ABORT")[0] == '2') {
-      fprintf(stderr, "  previous in-launch insert, workgroup 0: collect %.1f us, first wait %.1f us, apply %.1f us, second wait %.1f us\n", sl.h_ack[4] * 1e-2, sl.h_ack[5] * 1e-2, sl.h_ack[6] * 1e-2, sl.h_ack[7] * 1e-2);
-    }
-    if ((++n_tr & 511u) == 0) {
-      fprintf(stderr, "in-launch inserts %llu: workgroup 0 spent %.1f us collecting, %.1f us in the first wait, %.1f us applying, %.1f us in the second wait\n", (unsigned long long)n_tr, t_ph[0] / n_tr,
-              t_ph[1] / n_tr, t_ph[2] / n_tr, t_ph[3] / n_tr);
-    }
-  }
-  // (records of the new generation can overtake the launch's acknowledgement of the insert in front of them by a moment)
-  for (uint32_t spins = 0; __atomic_load_n(&sl.h_ack[0], __ATOMIC_ACQUIRE) != sl.cmd_seq; ++spins) {
-    if (spins > (1u << 26) || __atomic_load_n(&sl.h_ack[1], __ATOMIC_ACQUIRE) != 0) {
-      return set_err(c, GRP_ERR_STATE, "grp_classify_stream_insert: the previous insert of this window has not been applied");
-    }
-    __builtin_ia32_pause();
-  }
-  const uint32_t x = read_idx - sl.first;
-  uint32_t decided_base = 0; // this launch's decidable reads up to the insert, and its tiles up to there (= where its dispenser starts over)
-  uint64_t resume_tile = 0;
-  for (uint32_t j = 0; j <= x; ++j) {
-    if (sl.stripe_reads == 0 || (j / sl.stripe_reads) % sl.n_owners == sl.owner) {
-      const uint64_t ntj = r->tile0[sl.first + j + 1] - r->tile0[sl.first + j];
-      decided_base += ntj != 0;
-      resume_tile += ntj;
-    }
-  }
-  const uint32_t gen = ++sl.gen;
-  for (uint32_t j = x + 1; j < sl.count; ++j) { // the host's own records (reads without tiles) move to the new generation
-    if (r->tile0[sl.first + j + 1] == r->tile0[sl.first + j]) {
-      __atomic_store_n(&sl.h_sdec[j].pad, gen, __ATOMIC_RELEASE);
-    }
-  }
-  uint32_t* w = sl.h_cmd + 1;
-  w[0] = read_idx;
-  w[1] = tile_start;
-  w[2] = tile_end;
-  w[3] = block_tiles;
-  w[4] = first_id;
-  w[5] = id_offset;
-  w[6] = x + 1;
-  w[7] = (uint32_t)resume_tile;
-  w[8] = decided_base;
-  w[9] = gen;
-  __atomic_store_n(&sl.h_cmd[0], ++sl.cmd_seq, __ATOMIC_RELEASE);
-  c->kstat[GRP_K_INSERT].launches += 1;
-  c->kstat[GRP_K_INSERT].units += (uint64_t)(tile_end - tile_start) * tile_frames(c) * c->params.h;
-  *generation = gen;
-  return GRP_OK;
-}
+extern "C" {
 
 // ---- insert -------------------------------------------------------------------------
 

@@ -165,8 +165,7 @@ create_engine(PathRun& run, uint64_t filter_size)
   gp.tile = (uint32_t)run.opt.tile_length;
   gp.m = filter_size;
   gp.seeds = sp.data();
-  gp.device = run.world > 1 ? (int32_t)env_u32("GRP_LOCAL_RANK", "LOCAL_RANK", run.rank) : -1;
-  run.device = gp.device;
+  gp.device = run.device; // (run_stage)
   if (run.vt.create(&gp, &run.ctx) != GRP_OK) {
     std::cerr << "goldrush-path: cannot set up the MI355X engine: " << (run.vt.last_error ? run.vt.last_error(nullptr) : "") << std::endl;
     return false;
@@ -268,6 +267,13 @@ run_stage(PathRun& run, void* shm_h, GoldenCarry* collect = nullptr, GoldenCarry
   // pass already uses the GPU ingest); the reference's messages keep their order.
   // With --ntcard the filter size is only known after the ntcard pass.
   uint64_t filter_size = use_ntcard ? 0 : calc_optimal_size(opt.hash_universe, 1, opt.occupancy);
+  run.device = run.world > 1 ? (int32_t)env_u32("GRP_LOCAL_RANK", "LOCAL_RANK", run.rank) : -1;
+  if (run.world > 1 && shm_h && gr_ranks_share_device(shm_h, run.world, run.device) == 1) {
+    // ranks on one device (a test box): their windows' launches must all fit it at once — the in-launch inserts of
+    // the ranks' windows wait grid-wide.  In front of the engine: it reads its switches when its context is created
+    // (an explicit setting stands; the second stage of --golden_path takes over a context created behind this line)
+    setenv("GRP_STREAM_WGS_PER_CU", "1", 0);
+  }
   if (from) {
     // the first stage's engine, returned to its fill state: its tables go, this stage's take their place
     run.ctx = from->ctx;
@@ -308,11 +314,6 @@ run_stage(PathRun& run, void* shm_h, GoldenCarry* collect = nullptr, GoldenCarry
     // the ID / count tables of phase 2 are sized by the occupancy the fill will reach: -o, by construction of the filter
     // size (:1183-1184) — the engine allocates them beside the fill instead of between the passes (a hint: ignored where wrong)
     (void)run.vt.occupancy_hint(run.ctx, opt.occupancy);
-  }
-  if (run.world > 1 && shm_h && gr_ranks_share_device(shm_h, run.world, run.device) == 1) {
-    // ranks on one device (a test box): their windows' launches must all fit it at once — the in-launch inserts of
-    // the ranks' windows wait grid-wide (read at the engine's first streaming launch; an explicit setting stands)
-    setenv("GRP_STREAM_WGS_PER_CU", "1", 0);
   }
   if (run.world > 1 && !getenv("GRP_REPLICATED_FILL")) {
     // A sharded fill needs a way to merge: RCCL inside the engine (one GPU per rank), else the

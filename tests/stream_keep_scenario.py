@@ -1,7 +1,8 @@
 """Test helper (GPU): ONE resumable streaming window over a stream in which a few reads insert among many that do not,
 driven the way tests/test_gpu_stream_insert.py drives it; returns the records the host saw, the engine's final ID / count
 arrays' digest and what the in-launch inserts kept (grp_debug_stream_stats).  Run as a script it prints that as JSON —
-tests/test_gpu_stream_keep.py starts it with GRP_STREAM_KEEP = 0 / 1 / 2 (the engine reads the switch once per process)."""
+tests/test_gpu_stream_keep.py starts it with GRP_STREAM_KEEP = 0 / 1 / 2 (the engine reads the switch when a context is created; a process per setting keeps the
+settings' runs apart)."""
 import hashlib
 import json
 import os
