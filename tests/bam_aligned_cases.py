@@ -34,6 +34,26 @@ def aligned_twin(records):
     return b"".join(out)
 
 
+def model_table(body, records, accept, sum_phred):
+    """The record table that grp_bam_parse[_ex] reports for `body` (the records written one behind the other), by the
+    definitions alone: the offsets and lengths of walk(), the ACGT flag and the Phred sums of the twin's lines (sum_phred:
+    the host library's gr_sum_phred), GRP_FQ_REVERSED where an accepted 0x10 is set.  ingest_cases.RECORD_DTYPE."""
+    import numpy as np
+
+    import ingest_cases as IC
+
+    recs, used, bad, _ = walk(body, True, accept)
+    reads = [r for r in records if not r.get("flag", 4) & SKIPPED]
+    assert bad is None and used == len(body) and len(recs) == len(reads)
+    table = np.zeros(len(recs), dtype=IC.RECORD_DTYPE)
+    for i, (w, r) in enumerate(zip(recs, reads)):
+        bases, qual = twin_read(r["bases"], r["quals"], r.get("flag", 4))
+        flags = (IC.NON_ACGT if bases.strip(b"ACGT") else 0) | (2 if w["flag"] & accept & REVERSE else 0)
+        n = w["l_seq"]
+        table[i] = (w["off"] + 36, w["seq_off"], w["qual_off"], len(w["name"]), n, n, flags, sum_phred(qual), sum_phred(qual[:n // 2]) if n >= 2 else 0.0)
+    return table
+
+
 def counts(records):
     """(records skipped, records read in reverse)"""
     flags = [r.get("flag", 4) for r in records]

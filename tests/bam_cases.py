@@ -3,7 +3,10 @@ field of a record from the test, the FASTQ twin of what it writes, and a walk of
 specification §4.2) that the C++ walk is compared with."""
 import struct
 
+import numpy as np
+
 import bgzf_cases as B
+import ingest_cases as IC
 
 CODES = b"=ACMGRSVTWYHKDBN"
 CODE_OF = {c: i for i, c in enumerate(CODES)}
@@ -83,3 +86,98 @@ def walk(buf, final=True):
         recs.append(dict(off=pos, name=name, l_seq=l_seq, seq_off=seq_off, qual_off=seq_off + (l_seq + 1) // 2, end=pos + 4 + bs, flag=flag))
         pos += 4 + bs
     return recs, pos, (pos if final and pos < n else None)
+
+
+# ---- the edge sweeps (tests/test_gpu_bam_edges.py; ingest_cases.py has the FASTQ side and the kernels' geometry) --------------
+# the lengths of the FASTQ sweep, and those whose code bytes (half as many as the bases) end round 1024 and 2048
+SWEEP_LENGTHS = IC.S1_LENGTHS + [2079, 2080, 2081, 4128]
+BAD_CODES = [c for c in range(16) if c not in (1, 2, 4, 8)]  # the 12 codes that are none of A, C, G, T
+BAD_SHORT = list(range(1, 50))
+BAD_LONG = [2047, 2048, 2049, 2063, 2064, 2065, 2079, 2080, 2081, 4128]
+BAD_KINDS = IC.S2_KINDS + ["odd"]  # "odd": the last base of an odd length, the high half of the byte behind the whole bytes
+BAD_CASE = np.dtype([("rec", "<i8"), ("twin", "<i8"), ("len", "<i4"), ("align", "<i4"), ("pos", "<i4"), ("code", "<i4"), ("kind", "<i4")])
+_ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def steered_name(i, pos, want):
+    """a name for the record at byte `pos` of the stream (no CIGAR) that puts its bases at want (mod 16)"""
+    k = (want - (pos + 37)) % 16
+    n = k if k >= 4 else k + 16
+    name = (b"s%d" % i).ljust(n, b"_")[:n]
+    assert (pos + 36 + len(name) + 1) % 16 == want
+    return name
+
+
+def record_size(r):
+    return 36 + len(r["name"]) + 1 + 4 * len(r.get("cigar", ())) + (len(r["bases"]) + 1) // 2 + len(r["bases"]) + len(r.get("tags", b""))
+
+
+def sweep_records(seed=201, lengths=None, aligns=range(16)):
+    """length x alignment: every length at all 16 values of seq_off % 16 (qual_off % 16 follows), random A / C / G / T,
+    qualities 0..93; the padding code behind an odd length takes all 16 values (it is the alignment)"""
+    rng = np.random.default_rng(seed)
+    recs, pos = [], 0
+    for L in SWEEP_LENGTHS if lengths is None else lengths:
+        for a in aligns:
+            quals = bytes(rng.integers(0, 94, size=L).astype(np.uint8)) if len(recs) % 7 else b"\x5d" * L
+            r = dict(name=steered_name(len(recs), pos, a), bases=_ACGT[rng.integers(0, 4, size=L)].tobytes(), quals=quals, pad=a, flag=4)
+            recs.append(r)
+            pos += record_size(r)
+    return recs
+
+
+def bad_code_records(seed=202, short=None, long=None, aligns=range(16)):
+    """-> (records, cases[BAD_CASE]): as ingest_cases.s2_text — a clean record per (length, alignment) and behind it one
+    copy per planted base with that one code replaced.  Short records: every base.  Long ones: both halves of the code
+    bytes at the swept positions of the aligned middle, and the last base of an odd length."""
+    rng = np.random.default_rng(seed)
+    recs, cases, pos, turn = [], [], 0, 0
+
+    def put(bases, a, pad):
+        nonlocal pos
+        r = dict(name=steered_name(len(recs), pos, a), bases=bytes(bases), quals=b"\x28" * len(bases), pad=pad, flag=4)
+        recs.append(r)
+        pos += record_size(r)
+        return len(recs) - 1
+
+    for lengths, every in ((BAD_SHORT if short is None else short, True), (BAD_LONG if long is None else long, False)):
+        for L in lengths:
+            for a in aligns:
+                clean = bytearray(_ACGT[rng.integers(0, 4, size=L)].tobytes())
+                twin = put(clean, a, a)  # (the padding code behind an odd length: every value on clean records)
+                if every:
+                    planted = [("every", p) for p in range(L)]
+                else:
+                    planted = [(k, 2 * b + half) for k, b in IC.edge_positions(a, L // 2) for half in (0, 1)] + ([("odd", L - 1)] if L & 1 else [])
+                for kind, p in planted:
+                    bases = bytearray(clean)
+                    code = BAD_CODES[turn % len(BAD_CODES)]
+                    bases[p] = CODES[code]
+                    cases.append((put(bases, a, turn % 16), twin, L, a, p, code, BAD_KINDS.index(kind)))
+                    turn += 1
+    return recs, np.array(cases, dtype=BAD_CASE)
+
+
+QUAL_REFUSED = (94, 127, 128, 0xFF)
+QUAL_CASE = np.dtype([("rec", "<i8"), ("pos", "<i4"), ("kind", "U12")])
+
+
+def qual_sweep_records(seed=203):
+    """-> (records, positions[QUAL_CASE]): one small stream for the range test over the qualities, a byte of which is patched
+    per case: records of 2100 bases (an aligned middle of two rounds), of 40 and of 5 (no middle) at four alignments of the
+    quality bytes, on either strand; the swept positions of ingest_cases.edge_positions and the four byte lanes of a word"""
+    rng = np.random.default_rng(seed)
+    recs, at, pos = [], [], 0
+    for qa in (0, 1, 7, 14):
+        for L in (2100, 40, 5):
+            a = (qa - (L + 1) // 2) % 16
+            r = dict(name=steered_name(len(recs), pos, a), bases=_ACGT[rng.integers(0, 4, size=L)].tobytes(), quals=bytes(rng.integers(0, 60, size=L).astype(np.uint8)),
+                     pad=3, flag=(4, 0x10)[len(recs) % 2])
+            f = IC.middle(qa, L)[0]
+            where = [("every", p) for p in range(L)] if L == 5 else IC.edge_positions(qa, L)
+            if L == 2100:
+                where += [("lane", f + j) for j in (1, 2, 3)] + [("lane-1024", f + 1024 + j) for j in (1, 2, 3)]
+            at += [(len(recs), p, k) for k, p in where]
+            recs.append(r)
+            pos += record_size(r)
+    return recs, np.array(at, dtype=QUAL_CASE)

@@ -6,37 +6,9 @@ import numpy as np
 import pytest
 
 from helpers import default_seeds, random_reads
+from ingest_cases import host_parse as _host_parse  # the host reader's semantics: one model for every ingest test
 
 pytestmark = pytest.mark.gpu
-
-
-def _host_parse(text: bytes, final=True):
-    """The host reader's semantics (gr_fastq.cpp): 4-line records, rtrim of CR / blank / tab,
-    id up to the first whitespace; stops at a header that does not start with '@'."""
-    lines, pos = [], 0
-    while True:
-        nl = text.find(b"\n", pos)
-        if nl < 0:
-            if final and pos < len(text):
-                lines.append((pos, len(text)))
-            break
-        lines.append((pos, nl))
-        pos = nl + 1
-    recs = []
-    for r in range(len(lines) // 4):
-        ext = []
-        for s, e in lines[4 * r: 4 * r + 4]:
-            while e > s and text[e - 1:e] in (b"\r", b" ", b"\t"):
-                e -= 1
-            ext.append((s, e))
-        (hs, he), (ss, se), _, (qs, qe) = ext
-        if he == hs or text[hs:hs + 1] != b"@":
-            return recs, True
-        ie = hs + 1
-        while ie < he and not text[ie:ie + 1].isspace():
-            ie += 1
-        recs.append((hs + 1, ie - hs - 1, ss, se - ss, qs, qe - qs))
-    return recs, False
 
 
 def _mk_text(seed, n=40, crlf=False, lower=False, with_n=False, no_final_nl=False):
