@@ -665,4 +665,20 @@ grp_debug_verify_stats(const grp_ctx* c, uint64_t out[12])
   return GRP_OK;
 }
 
+int
+grp_debug_filter_geometry(const grp_ctx* c, uint64_t out[4])
+{
+  if (!c || !out) {
+    return GRP_ERR_INVALID;
+  }
+  if (!c->finalized) {
+    return GRP_ERR_STATE; // (a const context: no message is kept)
+  }
+  out[0] = c->f.W;
+  out[1] = c->f.n_buckets;
+  out[2] = c->n_ovf;
+  out[3] = c->n_far;
+  return GRP_OK;
+}
+
 } // extern "C"

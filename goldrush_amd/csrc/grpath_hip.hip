@@ -1456,13 +1456,13 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   const uint64_t h_pop = h_scalars[0];
   // bucket width: ~6 set bits per bucket on average at the measured occupancy;
   // with W <= 13 a bucket can never overflow its 13 ID slots
-  const double occ = (double)h_pop / (double)c->f.m;
+  // (floor(6 m / pop) in integers, m < 2^50: the quotient in double precision came out one below at exact ratios —
+  // 6.0 / (pop / m) = 58.99999999999999 where 6 m = 59 pop)
   uint32_t W = 64;
-  if (occ > 0) {
-    const double w = 6.0 / occ;
-    W = (w >= 64.0) ? 64u : (uint32_t)w;
+  if (h_pop > 0) {
+    W = (uint32_t)std::min<uint64_t>(6 * c->f.m / h_pop, 64);
   }
-  W = std::max<uint32_t>(GRP_BUCKET_IDS, std::min<uint32_t>(W, 64u));
+  W = std::max<uint32_t>(GRP_BUCKET_IDS, W);
   c->f.W = W;
   c->f.w_magic = (uint64_t)((((unsigned __int128)1) << 64) / W) + 1;
   c->f.n_buckets = (c->f.m + W - 1) / W;
@@ -1520,6 +1520,15 @@ grp_finalize(grp_ctx* c, uint64_t* pop)
   HIP_TRY(c, hipMemcpyAsync(h_scalars, d_scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (h_scalars[1] != h_pop) {
+    // the popcount runs over whole words, the buckets end at m: an imported or merged vector with bits behind m (grpath.h)
+    uint32_t last = 0;
+    if ((c->f.m & 31u) != 0 && hipMemcpy(&last, c->f.bv + (c->n_bv_words - 1), sizeof(last), hipMemcpyDeviceToHost) == hipSuccess) {
+      const uint32_t stray = (uint32_t)__builtin_popcount(last >> (c->f.m & 31u));
+      if (stray != 0 && h_scalars[1] + stray == h_pop) {
+        return set_err(c, GRP_ERR_INVALID, "grp_finalize: the bit vector holds %u set bits at positions >= m=%llu (a vector given to grp_bv_import_device / grp_bv_merge_device must be zero there); grp_rewind starts over", stray,
+                       (unsigned long long)c->f.m);
+      }
+    }
     return set_err(c, GRP_ERR_HIP, "internal: bucket scan counted %llu set bits, popcount %llu", h_scalars[1], (unsigned long long)h_pop);
   }
   {

@@ -114,6 +114,7 @@ SIGNATURES = {
     "grp_window_overlap": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "grp_debug_verify_stats": (C.c_int, [_vp, _vp]),
     "grp_debug_stream_stats": (C.c_int, [_vp, _vp]),
+    "grp_debug_filter_geometry": (C.c_int, [_vp, _vp]),
     "grp_batch_undo": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "grp_batch_end": (C.c_int, [_vp]),
     "grp_insert_tiles": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -739,6 +740,14 @@ class Engine:
         out = np.zeros(12, dtype=np.uint64)
         self._check(self.lib.grp_debug_verify_stats(self._h, _ptr(out)))
         return dict(zip(("patched", "queried", "flagged", "fallbacks", "uncertified", "unpatched", "window_flagged", "flagged_distinct", "flagged_list", "claim_sweeps", "impossible_deltas", "far_count_words"), (int(x) for x in out)))
+
+    def filter_geometry(self) -> list:
+        """[W, buckets, IDs in the overflow table, count words in the far table] of the finalized filter"""
+        out = np.zeros(4, dtype=np.uint64)
+        rc = self.lib.grp_debug_filter_geometry(self._h, _ptr(out))
+        if rc != GRP_OK:
+            raise GrpError(rc, "grp_debug_filter_geometry: needs a finalized filter")
+        return [int(x) for x in out]
 
     def stream_stats(self) -> dict:
         """what the in-launch inserts of the streaming windows did with the tiles queried behind the inserting read"""

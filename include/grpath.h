@@ -172,6 +172,11 @@ int grp_bv_insert(grp_ctx* ctx, const grp_reads* reads, uint32_t first, uint32_t
  *   grp_bv_export_device  copy it into caller-provided DEVICE memory
  *   grp_bv_merge_device   bv |= another rank's copy (device memory, 16-B aligned)
  * All three are only valid before grp_finalize.
+ * The bits at positions >= m of the vector's last word are zero in what grp_bv_export_device hands out and MUST be zero
+ * in what grp_bv_merge_device and grp_bv_import_device are given.  Neither call looks (the vector stays on the device):
+ * grp_finalize refuses a vector with such bits with GRP_ERR_INVALID ("... set bits at positions >= m ...") before it
+ * hands out a pop; the context is not finalized then and builds nothing until grp_rewind (or a grp_bv_import_device of
+ * a clean vector followed by grp_finalize).
  */
 int grp_bv_words(const grp_ctx* ctx, uint64_t* n_words32);
 int grp_bv_export_device(grp_ctx* ctx, void* d_dst);
@@ -184,7 +189,7 @@ int grp_bv_merge_device(grp_ctx* ctx, const void* d_src);
  *   grp_words_or_device   dst |= src for n 32-bit words of DEVICE memory (16-byte aligned;
  *                         any buffers of ctx's device, not the bit vector itself)
  *   grp_bv_import_device  overwrite the bit vector with caller-provided DEVICE memory
- *                         (grp_bv_words words; the merged vector)
+ *                         (grp_bv_words words; the merged vector; no bits at positions >= m, see above)
  */
 int grp_words_or_device(grp_ctx* ctx, void* d_dst, const void* d_src, uint64_t n_words32);
 int grp_bv_import_device(grp_ctx* ctx, const void* d_src);
@@ -559,7 +564,8 @@ uint64_t grp_pop(const grp_ctx* ctx);
 /* plain bit vector, bit i = word i>>6 bit i&63 (sdsl::bit_vector layout,
  * MIBFConstructSupport.hpp:140-142); n_words = ceil(m/64) */
 int grp_export_bits(grp_ctx* ctx, uint64_t* words, uint64_t n_words);
-/* bit[i] / rank[i] (= ones in [0,pos[i])) for n positions; needs finalize */
+/* bit[i] / rank[i] (= ones in [0,pos[i])) for n positions; needs finalize; a position >= m is refused (GRP_ERR_INVALID,
+ * nothing is written) */
 int grp_rank(grp_ctx* ctx, const uint64_t* pos, uint64_t n, uint8_t* bit, uint64_t* rank);
 /* ids / counts of ranks [first, first+n) */
 int grp_export_ids(grp_ctx* ctx, uint64_t first, uint64_t n, uint32_t* ids, uint32_t* counts);
@@ -606,6 +612,12 @@ int grp_debug_decide(grp_ctx* ctx, uint32_t n_reads, const uint64_t* tile0, cons
  * (an impossible delta: queried again through the log, the run goes on), [11] count words living in the far table
  * (ranks beyond their bucket's 8th set bit, csrc/grp_device.h) */
 int grp_debug_verify_stats(const grp_ctx* ctx, uint64_t out[12]);
+
+/* The directory grp_finalize built (csrc/grp_device.h): [0] W, the filter bits per bucket (13..64, floor(6 m / pop) clamped,
+ * 64 for an empty filter), [1] buckets = ceil(m / W), [2] IDs living in the overflow table (ranks beyond their bucket's
+ * 13th set bit), [3] count words living in the far table (ranks beyond its 8th).  Needs a finalized context
+ * (GRP_ERR_STATE otherwise). */
+int grp_debug_filter_geometry(const grp_ctx* ctx, uint64_t out[4]);
 
 /* What the in-launch inserts of the streaming windows ended so far (since grp_create) did with the tiles the launches had
  * queried behind the inserting read (round 6): [1] finished tiles kept (no probe of theirs read a slot the insert changed),

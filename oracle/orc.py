@@ -95,7 +95,7 @@ def load():
         "orc_mibf_create": (vp, [u64, C.c_uint]), "orc_mibf_destroy": (None, [vp]),
         "orc_mibf_insert_bv": (None, [vp, vp, sz]), "orc_mibf_finalize": (None, [vp]),
         "orc_mibf_bit": (C.c_int, [vp, u64]), "orc_mibf_rank": (u64, [vp, u64]),
-        "orc_mibf_reset_ids": (None, [vp]),
+        "orc_mibf_reset_ids": (None, [vp]), "orcpy_mibf_bits_ranks": (None, [vp, vp, sz, vp, vp]),
         "orcpy_bv_insert_read": (None, [vp, vp, C.c_uint, C.c_char_p, sz]),
         "orcpy_bv_insert_reads": (None, [vp, vp, C.c_uint, vp, vp, sz]),
         "orcpy_insert_read_tiles": (None, [vp, vp, C.c_uint, C.c_char_p, sz, sz, sz, sz, sz, u32]),
@@ -221,6 +221,7 @@ class MiBF:
         self.h = seeds.h
         self.tile, self.k = tile, k
         self._own = handle is None
+        self._finalized = handle is not None
         self._h = self.lib.orc_mibf_create(m, self.h) if handle is None else handle
         self.m = m
 
@@ -234,8 +235,20 @@ class MiBF:
         lens = np.array([len(s) for s in seqs], dtype=np.uint64)
         self.lib.orcpy_bv_insert_reads(self._h, self.seeds._h, self.h, C.cast(arr, C.c_void_p), _p(lens), n)
 
+    def plant_bits(self, words):
+        """bv |= words (uint64, ceil(m/64) of them, no bit at a position >= m), before finalize: any vector a test likes"""
+        n = self.lib.orcpy_mibf_n_words(self._h)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if words.size != n or (self.m & 63 and int(words[-1]) >> (self.m & 63)):
+            raise ValueError("plant_bits: ceil(m/64) words without bits at positions >= m")
+        if self._finalized:
+            raise ValueError("plant_bits after finalize: the rank support is built")
+        live = np.ctypeslib.as_array(C.cast(self.lib.orcpy_mibf_bv(self._h), C.POINTER(C.c_uint64)), shape=(n,))
+        live |= words
+
     def finalize(self) -> int:
         self.lib.orc_mibf_finalize(self._h)
+        self._finalized = True
         return self.pop
 
     @property
@@ -260,6 +273,16 @@ class MiBF:
 
     def bit(self, pos: int) -> int:
         return self.lib.orc_mibf_bit(self._h, pos)
+
+    def bits_ranks(self, pos):
+        """(orc_mibf_bit, orc_mibf_rank) at every position of an array (all < m; finalized)"""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        if not self._finalized or (pos.size and int(pos.max()) >= self.m):
+            raise ValueError("bits_ranks: needs a finalized filter and positions below m")
+        bit = np.zeros(pos.size, dtype=np.uint8)
+        rank = np.zeros(pos.size, dtype=np.uint64)
+        self.lib.orcpy_mibf_bits_ranks(self._h, _p(pos), pos.size, _p(bit), _p(rank))
+        return bit, rank
 
     def query_tile(self, hashes: np.ndarray):
         """Returns (top_id, top_count, list[(id,count)], (queries, hits, misses))."""

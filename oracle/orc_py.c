@@ -74,6 +74,16 @@ orcpy_insert_read_tiles(orc_mibf* f, const orc_seed* seeds, unsigned h, const ch
   orc_tile_hashes_free(&th);
 }
 
+/* orc_mibf_bit / orc_mibf_rank at n positions (a test that asks every position of a filter) */
+void
+orcpy_mibf_bits_ranks(const orc_mibf* f, const uint64_t* pos, size_t n, uint8_t* bit, uint64_t* rank)
+{
+  for (size_t i = 0; i < n; ++i) {
+    bit[i] = (uint8_t)orc_mibf_bit(f, pos[i]);
+    rank[i] = orc_mibf_rank(f, pos[i]);
+  }
+}
+
 uint64_t* orcpy_mibf_bv(orc_mibf* f) { return f->bv; }
 uint64_t orcpy_mibf_n_words(const orc_mibf* f) { return f->n_words; }
 uint64_t orcpy_mibf_pop(const orc_mibf* f) { return f->pop; }

@@ -65,6 +65,23 @@ def compare_queries(eng, omf, batch, reads, first=0, count=None):
     return q, hh, ms
 
 
+def thicken_engine(eng):
+    """Between grp_bv_insert and grp_finalize: every 64-bit word of the engine's bit vector that holds a bit becomes all ones
+    (the tail masked to m), on the device — filter_cases.thicken is the oracle's side.  Returns the thickened words."""
+    import torch
+
+    t = torch.zeros((eng.m + 63) // 64, dtype=torch.int64, device="cuda")  # (whole 64-bit words: at least grp_bv_words 32-bit ones)
+    torch.cuda.synchronize()
+    assert t.numel() * 8 >= eng.bv_words() * 4
+    eng.bv_export_device(t.data_ptr())
+    t = torch.where(t != 0, torch.full_like(t, -1), t)
+    if eng.m & 63:
+        t[-1] &= (1 << (eng.m & 63)) - 1
+    torch.cuda.synchronize()
+    eng.bv_import_device(t.data_ptr())
+    return t.cpu().numpy().view(np.uint64)
+
+
 # ---- streams of reads with few errors, and ONE resumable window over them ----
 LOW_ERRORS = dict(sub=0.004, ins=0.0005, dele=0.0005)
 

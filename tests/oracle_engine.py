@@ -380,15 +380,18 @@ class OracleEngine:
         return vt
 
 
-def serial_reference(orc, m, seeds, tile, k, reads, block=10, threshold=10, u=5, a=1, silver=False, target_bases=0, max_paths=1, counters=None):
+def serial_reference(orc, m, seeds, tile, k, reads, block=10, threshold=10, u=5, a=1, silver=False, target_bases=0, max_paths=1, counters=None, plant=None):
     """The reference's serial loop (process_read, goldrush_path.cpp:892-1094)
     stated with oracle primitives; returns the commit tuples the classifier
     should produce: (read, kind, num_tiles, num_assigned, trim_start, trim_end, first_id, path).
-    `counters`: a list that takes (hits, misses) of every read's query, at the ID state the loop queried it in."""
+    `counters`: a list that takes (hits, misses) of every read's query, at the ID state the loop queried it in.
+    `plant`: called with the oracle filter between the fill and finalize (MiBF.plant_bits: a filter other than the fill's)."""
     oseeds = orc.Seeds(seeds)
     mf = orc.MiBF(m, oseeds, tile, k)
     for s in reads:
         mf.bv_insert_read(s)
+    if plant is not None:
+        plant(mf)
     mf.finalize()
     out = []
     ids_inserted = 0

@@ -86,15 +86,25 @@ def batch_commit(eng, b, reads, tile, block, window, stats, verify=None):
                 shrink += 1
             continue
         extra = 0
-        if verify is None:
-            d1 = eng.batch_classify(b, pos, cnt, floors)
-        else:
-            extra = min(max(1, window // 2), n - pos - cnt)
-            dv = eng.batch_verify(b, pos, cnt, extra, floors + [0x7FFFFFFF] * extra)
-            d1 = dv[:cnt]
-            if verify == "check":
-                dq = eng.batch_classify(b, pos, cnt + extra, floors + [0x7FFFFFFF] * extra)
-                assert dv.tobytes() == dq.tobytes(), [(j, dv[j], dq[j]) for j in range(cnt + extra) if dv[j].tobytes() != dq[j].tobytes()][:3]
+        try:
+            if verify is None:
+                d1 = eng.batch_classify(b, pos, cnt, floors)
+            else:
+                extra = min(max(1, window // 2), n - pos - cnt)
+                dv = eng.batch_verify(b, pos, cnt, extra, floors + [0x7FFFFFFF] * extra)
+                d1 = dv[:cnt]
+                if verify == "check":
+                    dq = eng.batch_classify(b, pos, cnt + extra, floors + [0x7FFFFFFF] * extra)
+                    assert dv.tobytes() == dq.tobytes(), [(j, dv[j], dq[j]) for j in range(cnt + extra) if dv[j].tobytes() != dq[j].tobytes()][:3]
+        except native_mod.GrpError as e:
+            # the same refusal found on the device (include/grpath.h: too many ranks shared by several ID blocks of the batch):
+            # the owners' touches are taken back, nothing is inserted, the batch is over — a smaller window
+            assert e.code == native_mod.GRP_ERR_NOMEM and cnt > 1
+            stats["refused_on_device"] = stats.get("refused_on_device", 0) + 1
+            shrink = 1
+            while (window >> shrink) >= cnt:
+                shrink += 1
+            continue
         bad = next((j for j in range(cnt) if not _same(d0[j], d1[j])), None)
         stats["batches"] += 1
         if bad is None:
