@@ -62,6 +62,9 @@ enum InfStatus : uint32_t
   INF_NO_FINAL = 18,
   INF_STATUS_COUNT = 19,
 };
+// the open form's own (grp_gzip_walk): it is no word on the stream, so it stands outside the table of a stream's faults
+constexpr uint32_t INF_NO_ROOM = 19;
+constexpr const char* INF_NO_ROOM_TEXT = "the text of the step's blocks does not fit its room";
 
 const char* const INF_STATUS_TEXT[INF_STATUS_COUNT] = {
   "ok",
@@ -313,7 +316,22 @@ inf_flush(InfLds& s, char* out, uint32_t a, uint32_t b)
   INF_FENCE();
 }
 
-// Inflates one stream, text to out[0, text_len), and returns its status.  Two forms, chosen at compile time:
+// what the open form of inf_stream reports beside its status: only where the status is INF_OK
+struct InfOpenEnd
+{
+  uint64_t bits;     // consumed, from comp_bit on: the step ended at that block boundary
+  uint32_t text_len; // that came out
+  uint32_t final;    // 1: the boundary lies behind a final block
+};
+
+enum InfForm : int
+{
+  INF_MEMBER = 0,
+  INF_SEGMENT = 1,
+  INF_OPEN = 2,
+};
+
+// Inflates one stream, text to out[0, text_len), and returns its status.  Three forms, chosen at compile time:
 //   a member (SEG false)   the payload is the BYTES comp[start, start + length), it has no history and ends with its final
 //                          block; at most 64 KiB of text (the host checks that)
 //   a segment (SEG true)   start and length are BITS, comp_bit and n_bits below: a run of whole blocks out of the middle of a serial stream (include/grpath_ingest.h:
@@ -323,10 +341,21 @@ inf_flush(InfLds& s, char* out, uint32_t a, uint32_t b)
 //                          behind a final block if and only if seg_flags says that it ends its member.  A stored block
 //                          aligns to a byte of the FILE, so the padding and the block's address come from the absolute
 //                          bit position comp_bit + n_bits - avail.  text_len is any 32-bit number.
-template <bool SEG>
+//   an open step (OPEN)    a segment whose end is not known (include/grpath_ingest.h: grp_gzip_walk): it starts like a segment,
+//                          n_bits are the bits there ARE, text_len the room of `out`, seg_flags the least text it is to
+//                          produce (min_text).  It decodes whole blocks and stops behind the first block where at least
+//                          min_text bytes have come out, or behind a final block, whichever comes first, and says where
+//                          that was (*end).  Text that would not fit the room: INF_NO_ROOM; the bits ending inside a
+//                          block or in front of the next one: INF_INPUT_ENDS.  The last min(32768, dict_len + text)
+//                          bytes of history and text — the history of the step behind it — go to hist_out, their
+//                          number to *hist_len.
+template <int FORM>
 INF_FN uint32_t
-inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, const uint8_t* dict, uint32_t dict_len, uint32_t seg_flags, char* out, uint32_t text_len)
+inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, const uint8_t* dict, uint32_t dict_len, uint32_t seg_flags, char* out, uint32_t text_len, InfOpenEnd* end = nullptr, uint8_t* hist_out = nullptr,
+           uint32_t* hist_len = nullptr)
 {
+  constexpr bool SEG = FORM != INF_MEMBER, OPEN = FORM == INF_OPEN;
+  constexpr uint32_t TOO_LONG = OPEN ? INF_NO_ROOM : INF_TEXT_TOO_LONG;
   const uint64_t comp_bit = start, n_bits = length;    // (a segment's)
   const uint64_t comp_off = SEG ? start >> 3 : start;  // a member's payload; a segment's first byte
   const uint32_t comp_len = SEG ? 0u : (uint32_t)length;
@@ -398,7 +427,7 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
         return INF_INPUT_ENDS;
       }
       if (len > text_len - p) {
-        return INF_TEXT_TOO_LONG;
+        return TOO_LONG;
       }
       uint64_t at = SEG ? (comp_bit + n_bits - (uint64_t)rd.avail) >> 3 : comp_off + comp_len - (uint64_t)(rd.avail >> 3); // the block's bytes inside comp
       rd.avail -= (int64_t)len * 8;
@@ -527,7 +556,7 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
         }
         if (sym < 256) {
           if (p >= text_len) {
-            return INF_TEXT_TOO_LONG;
+            return TOO_LONG;
           }
           s.ring[p & INF_RMASK] = (uint8_t)sym;
           p += 1;
@@ -569,7 +598,7 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
             return INF_DIST_TOO_FAR;
           }
           if (len > text_len - p) {
-            return INF_TEXT_TOO_LONG;
+            return TOO_LONG;
           }
           // every source lies in front of p: written before this copy, whatever the overlap
           INF_FENCE();
@@ -592,7 +621,29 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
         }
       }
     }
-    if constexpr (SEG) {
+    if constexpr (OPEN) {
+      if (last || p >= seg_flags) {
+        INF_FENCE();
+        if (p != flushed) {
+          inf_flush(s, out, flushed, p);
+        }
+        // the ring holds text [p - 32768, p), the history as text [-dict_len, 0)
+        const uint32_t keep = dict_len + p < INF_RING ? dict_len + p : INF_RING;
+        INF_LANES
+        {
+          for (uint32_t j = (uint32_t)lane; j < keep; j += 64) {
+            hist_out[j] = s.ring[(p - keep + j) & INF_RMASK];
+          }
+          if (lane == 0) {
+            end->bits = n_bits - (uint64_t)rd.avail;
+            end->text_len = p;
+            end->final = last;
+            *hist_len = keep;
+          }
+        }
+        return INF_OK;
+      }
+    } else if constexpr (SEG) {
       if (last) {
         if (!(seg_flags & 1u)) {
           return INF_FINAL_INSIDE;
@@ -628,13 +679,72 @@ inf_stream(InfLds& s, const uint8_t* comp, uint64_t start, uint64_t length, cons
 INF_FN uint32_t
 inf_entry(InfLds& s, const uint8_t* comp, const uint8_t*, const grp_bgzf_block& b, char* out)
 {
-  return inf_stream<false>(s, comp, b.comp_off, b.comp_len, nullptr, 0, 0, out, b.text_len);
+  return inf_stream<INF_MEMBER>(s, comp, b.comp_off, b.comp_len, nullptr, 0, 0, out, b.text_len);
 }
 
 INF_FN uint32_t
 inf_entry(InfLds& s, const uint8_t* comp, const uint8_t* dict, const grp_gzip_segment& g, char* out)
 {
-  return inf_stream<true>(s, comp, g.comp_bit, g.n_bits, dict + g.dict_off, g.dict_len, g.flags, out, g.text_len);
+  return inf_stream<INF_SEGMENT>(s, comp, g.comp_bit, g.n_bits, dict + g.dict_off, g.dict_len, g.flags, out, g.text_len);
+}
+
+static_assert(GRP_GZIP_WALK_INPUT_ENDS == INF_INPUT_ENDS && GRP_GZIP_WALK_NO_ROOM == INF_NO_ROOM, "the two statuses the walk acts on, as grpath_ingest.h names them");
+
+// a step of grp_gzip_walk: the open form.  The entry says where its answer and the history of the step behind it go
+struct InfWalkEntry
+{
+  grp_gzip_walk_step step;
+  grp_gzip_walk_result* res; // one lane writes it
+  uint8_t* hist;             // 32768 bytes
+};
+
+INF_FN uint32_t
+inf_entry(InfLds& s, const uint8_t* comp, const uint8_t* dict, const InfWalkEntry& w, char* out)
+{
+  InfOpenEnd end{ 0, 0, 0 };
+  uint32_t hist_len = 0;
+  const uint32_t st = inf_stream<INF_OPEN>(s, comp, w.step.comp_bit, w.step.n_bits, dict + w.step.dict_off, w.step.dict_len, w.step.min_text, out, w.step.room, &end, w.hist, &hist_len);
+  INF_LANES
+  {
+    if (lane == 0) {
+      *w.res = grp_gzip_walk_result{ end.bits, end.text_len, 0, end.final, st, hist_len, 0 };
+    }
+  }
+  return st;
+}
+
+// what k_inflate_crc does with an entry: the length of its text, and the CRC32 of it — a member and a segment bring the
+// CRC32 their text must have, a step of the walk takes the one its text has
+INF_FN uint32_t
+inf_crc_len(const grp_bgzf_block& b)
+{
+  return b.text_len;
+}
+INF_FN uint32_t
+inf_crc_len(const grp_gzip_segment& g)
+{
+  return g.text_len;
+}
+INF_FN uint32_t
+inf_crc_len(const InfWalkEntry& w)
+{
+  return w.res->text_len;
+}
+INF_FN uint32_t
+inf_crc_done(const grp_bgzf_block& b, uint32_t c)
+{
+  return c != b.crc32 ? INF_CRC_MISMATCH : INF_OK;
+}
+INF_FN uint32_t
+inf_crc_done(const grp_gzip_segment& g, uint32_t c)
+{
+  return c != g.crc32 ? INF_CRC_MISMATCH : INF_OK;
+}
+INF_FN uint32_t
+inf_crc_done(const InfWalkEntry& w, uint32_t c)
+{
+  w.res->crc32 = c;
+  return INF_OK;
 }
 
 // ---- CRC32 (the gzip polynomial, reflected: 0xedb88320) of a member's text by one wave --------------------------------
@@ -737,8 +847,8 @@ k_inflate_crc(const Entry* __restrict__ entries, const uint64_t* __restrict__ to
   if (i >= n_entries || status[i] != INF_OK) {
     return;
   }
-  const uint32_t c = crc_member(s, tables, text + toff[i], entries[i].text_len);
-  if (threadIdx.x == 0 && c != entries[i].crc32) {
+  const uint32_t c = crc_member(s, tables, text + toff[i], inf_crc_len(entries[i]));
+  if (threadIdx.x == 0 && inf_crc_done(entries[i], c) != INF_OK) {
     status[i] = INF_CRC_MISMATCH;
   }
 }
@@ -1031,6 +1141,46 @@ inflate_check_table(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint
   return GRP_OK;
 }
 
+// What the launches of all three entry types share.  inflate_reserve: the pool's device buffers for n entries of `per`
+// elements of the pool's entry type each, grown, never shrunk (like the ingest's buffers) — the kernels read whole words: 8
+// bytes of padding behind the compressed bytes, the histories and the text — and its page-locked staging; the caller then
+// writes the entries and the text offsets into the staging.  inflate_send: the compressed bytes with their padding, the
+// histories, the entries and the offsets go up on `st`.
+template <class Pool>
+int
+inflate_reserve(grp_ctx* c, Pool& p, uint64_t n_comp, uint64_t n_dict, uint64_t total, uint32_t n, uint64_t per = 1)
+{
+  HIP_TRY(c, p.d_comp.ensure(n_comp + 8));
+  HIP_TRY(c, p.d_dict.ensure(n_dict + 8));
+  HIP_TRY(c, p.d_text.ensure(total + 8));
+  HIP_TRY(c, p.d_entries.ensure((uint64_t)n * per));
+  HIP_TRY(c, p.d_toff.ensure(n));
+  HIP_TRY(c, p.d_status.ensure(n));
+  if (p.h_toff.cap < n) {
+    const uint64_t cap = (uint64_t)n + n / 4 + 64;
+    HIP_TRY(c, p.h_entries.reset(cap * per, hipHostMallocDefault));
+    HIP_TRY(c, p.h_toff.reset(cap, hipHostMallocDefault));
+    HIP_TRY(c, p.h_status.reset(cap, hipHostMallocDefault));
+  }
+  return GRP_OK;
+}
+
+template <class Pool>
+int
+inflate_send(grp_ctx* c, Pool& p, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, uint32_t n, uint64_t per, hipStream_t st)
+{
+  if (n_comp) {
+    HIP_TRY(c, hipMemcpyAsync(p.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemsetAsync(p.d_comp + n_comp, 0, 8, st));
+  if (n_dict) {
+    HIP_TRY(c, hipMemcpyAsync(p.d_dict, dict, n_dict, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(p.d_entries, p.h_entries.p, (size_t)n * per * sizeof(*p.h_entries.p), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(p.d_toff, p.h_toff.p, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  return GRP_OK;
+}
+
 // grp_bgzf_inflate and grp_gzip_inflate (a BGZF call has no histories: dict == nullptr, n_dict == 0).  `keep_text`: the
 // text is not copied to the caller (text_out and text_cap are not looked at): it is in p.d_text, entry i's at p.h_toff[i],
 // when the call returns GRP_OK (grp_records_fetch)
@@ -1058,19 +1208,8 @@ inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp,
     HIP_TRY(c, p.ev0.create(hipEventDefault));
     HIP_TRY(c, p.ev1.create(hipEventDefault));
   }
-  // grown, never shrunk (like the ingest's buffers); the kernels read whole words: 8 bytes of padding behind the
-  // compressed bytes, the histories and the text
-  HIP_TRY(c, p.d_comp.ensure(n_comp + 8));
-  HIP_TRY(c, p.d_dict.ensure(n_dict + 8));
-  HIP_TRY(c, p.d_text.ensure(total + 8));
-  HIP_TRY(c, p.d_entries.ensure(n));
-  HIP_TRY(c, p.d_toff.ensure(n));
-  HIP_TRY(c, p.d_status.ensure(n));
-  if (p.h_entries.cap < n) {
-    const uint64_t cap = (uint64_t)n + n / 4 + 64;
-    HIP_TRY(c, p.h_entries.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, p.h_toff.reset(cap, hipHostMallocDefault));
-    HIP_TRY(c, p.h_status.reset(cap, hipHostMallocDefault));
+  if (const int rc = inflate_reserve(c, p, n_comp, n_dict, total, n)) {
+    return rc;
   }
   memcpy(p.h_entries.p, entries, (size_t)n * sizeof(Entry));
   uint64_t off = 0;
@@ -1078,15 +1217,9 @@ inflate_entries(grp_ctx* c, grp_ctx::InflatePool<Entry>& p, const uint8_t* comp,
     p.h_toff.p[i] = off;
     off += entries[i].text_len;
   }
-  if (n_comp) {
-    HIP_TRY(c, hipMemcpyAsync(p.d_comp, comp, n_comp, hipMemcpyHostToDevice, st));
+  if (const int rc = inflate_send(c, p, comp, n_comp, dict, n_dict, n, 1, st)) {
+    return rc;
   }
-  HIP_TRY(c, hipMemsetAsync(p.d_comp + n_comp, 0, 8, st));
-  if (n_dict) {
-    HIP_TRY(c, hipMemcpyAsync(p.d_dict, dict, n_dict, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipMemcpyAsync(p.d_entries, p.h_entries.p, (size_t)n * sizeof(Entry), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(p.d_toff, p.h_toff.p, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipEventRecord(p.ev0, st));
   k_inflate<Entry><<<n, 64, 0, st>>>(p.d_comp, p.d_dict, p.d_entries, p.d_toff, n, reinterpret_cast<char*>(p.d_text.p), p.d_status);
   k_inflate_crc<Entry><<<n, 64, 0, st>>>(p.d_entries, p.d_toff, n, reinterpret_cast<const char*>(p.d_text.p), c->d_crc_tab, p.d_status);
@@ -1154,6 +1287,96 @@ grp_gzip_inflate(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t
     *bad_seg = UINT32_MAX;
   }
   return inflate_entries(c, c->gzip, comp, n_comp, dict, n_dict, segs, n_segs, text_out, text_cap, bad_seg);
+}
+
+// One open step per entry: k_inflate<InfWalkEntry>, then k_inflate_crc<InfWalkEntry> for the CRC32 of what came out, over
+// the buffers and uploads of inflate_entries (inflate_reserve, inflate_send).  What differs from it is what comes back: a
+// step's status is its answer, not the call's, and every step has its answer and its new history.
+extern "C" int
+grp_gzip_walk(grp_ctx* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n, grp_gzip_walk_result* results, uint8_t* hist_out, char* text_out, uint64_t text_cap,
+              uint32_t* bad_step)
+{
+  if (!c) {
+    return GRP_ERR_INVALID;
+  }
+  if (bad_step) {
+    *bad_step = UINT32_MAX;
+  }
+  if ((!comp && n_comp) || (!dict && n_dict) || (n && (!steps || !results || !hist_out)) || n_comp > (1ull << 32) || n_dict > (1ull << 32) || n > MAX_GRID_WGS) {
+    return set_err(c, GRP_ERR_INVALID, "grp_gzip_walk: bad argument (at most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 steps per call)");
+  }
+  // the table is checked before anything is launched
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const grp_gzip_walk_step& g = steps[i];
+    total += g.room;
+    const char* why = g.comp_bit > n_comp * 8 || g.n_bits > n_comp * 8 - g.comp_bit ? "its bits do not lie inside the compressed bytes"
+                      : g.dict_len > INF_RING                                       ? "a history of more than 32768 bytes"
+                      : g.dict_off > n_dict || g.dict_len > n_dict - g.dict_off     ? "its history does not lie inside the histories"
+                      : g.reserved != 0                                             ? "a reserved field that is not 0"
+                      : total > (1ull << 34)                                        ? "the rooms up to this step are more than 2^34 bytes"
+                      : text_out && total > text_cap                                ? "the rooms up to this step are more than the caller's buffer"
+                                                                                    : nullptr;
+    if (why) {
+      if (bad_step) {
+        *bad_step = i;
+      }
+      return set_err(c, GRP_ERR_INVALID, "grp_gzip_walk: step %u: %s (bits [%llu, +%llu) of %llu bytes, history [%llu, +%u) of %llu, min_text %u, room %u, rooms so far %llu of %llu)", i, why, (unsigned long long)g.comp_bit,
+                     (unsigned long long)g.n_bits, (unsigned long long)n_comp, (unsigned long long)g.dict_off, g.dict_len, (unsigned long long)n_dict, g.min_text, g.room, (unsigned long long)total,
+                     (unsigned long long)(text_out ? text_cap : 1ull << 34));
+    }
+  }
+  if (n == 0) {
+    return GRP_OK;
+  }
+  hipStream_t st = c->stream2;
+  if (const int rc = inflate_crc_tables(c)) {
+    return rc;
+  }
+  grp_ctx::WalkPool& w = c->walk;
+  auto& p = w.io;
+  // (the pool keeps its entries as bytes: InfWalkEntry is this file's)
+  if (const int rc = inflate_reserve(c, p, n_comp, n_dict, total, n, sizeof(InfWalkEntry))) {
+    return rc;
+  }
+  HIP_TRY(c, w.d_res.ensure(n));
+  HIP_TRY(c, w.d_hist.ensure((uint64_t)n * INF_RING));
+  if (w.h_res.cap < n) {
+    HIP_TRY(c, w.h_res.reset((uint64_t)n + n / 4 + 64, hipHostMallocDefault));
+  }
+  InfWalkEntry* he = reinterpret_cast<InfWalkEntry*>(p.h_entries.p);
+  InfWalkEntry* de = reinterpret_cast<InfWalkEntry*>(p.d_entries.p);
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    he[i] = InfWalkEntry{ steps[i], w.d_res.p + i, w.d_hist.p + (uint64_t)i * INF_RING };
+    p.h_toff.p[i] = off;
+    off += steps[i].room;
+  }
+  if (const int rc = inflate_send(c, p, comp, n_comp, dict, n_dict, n, sizeof(InfWalkEntry), st)) {
+    return rc;
+  }
+  k_inflate<InfWalkEntry><<<n, 64, 0, st>>>(p.d_comp, p.d_dict, de, p.d_toff, n, reinterpret_cast<char*>(p.d_text.p), p.d_status);
+  k_inflate_crc<InfWalkEntry><<<n, 64, 0, st>>>(de, p.d_toff, n, reinterpret_cast<const char*>(p.d_text.p), c->d_crc_tab, p.d_status);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(w.h_res.p, w.d_res, (size_t)n * sizeof(grp_gzip_walk_result), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hist_out, w.d_hist, (size_t)n * INF_RING, hipMemcpyDeviceToHost, st));
+  if (text_out && total) {
+    HIP_TRY(c, hipMemcpyAsync(text_out, p.d_text, total, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < n; ++i) {
+    results[i] = w.h_res.p[i];
+    if (results[i].status != INF_OK) { // (nothing of a step that did not reach a boundary is an answer)
+      results[i] = grp_gzip_walk_result{ 0, 0, 0, 0, results[i].status, 0, 0 };
+    }
+  }
+  return GRP_OK;
+}
+
+extern "C" const char*
+grp_gzip_status_text(uint32_t status)
+{
+  return status < INF_STATUS_COUNT ? INF_STATUS_TEXT[status] : status == INF_NO_ROOM ? INF_NO_ROOM_TEXT : "unknown status";
 }
 
 namespace {

@@ -347,6 +347,15 @@ struct grp_ctx : CtxStreams
   };
   InflatePool<grp_bgzf_block> bgzf;
   InflatePool<grp_gzip_segment> gzip;
+  // grp_gzip_walk (grp_inflate.inc): beside the buffers above (its entries are InfWalkEntry, kept as bytes here) the
+  // per-step answers and the 32 KiB of new history of every step; grown, never shrunk
+  struct WalkPool
+  {
+    InflatePool<uint8_t> io;
+    DevBuf<grp_gzip_walk_result> d_res;
+    DevBuf<uint8_t> d_hist;
+    HostBuf<grp_gzip_walk_result> h_res;
+  } walk;
   // grp_records_fetch: the record table, the formatted records and their Phred sums of one call; grown, never shrunk
   struct FetchPool
   {

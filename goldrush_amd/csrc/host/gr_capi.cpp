@@ -8,6 +8,7 @@
 #include "gr_tiles.hpp"
 #include "gr_fastq.hpp"
 #include "gr_gzidx.hpp"
+#include "gr_gzwalk.hpp"
 
 #include <cstddef>
 #include <cstring>
@@ -328,10 +329,12 @@ gr_input_read(const char* path, uint64_t request_bytes, char* dst, uint64_t cap)
 
 struct gr_gzidx
 {
-  std::unique_ptr<gr::GzIndexReader> rd;
+  std::unique_ptr<gr::GzIndexReader> rd; // (none: the handle of gr_gzidx_build_device)
   std::unique_ptr<gr::GzIndex> idx; // the complete index, else rd->partial()
   uint64_t n_text = 0;
-  const gr::GzIndex* get() const { return idx ? idx.get() : rd->partial(); }
+  const char* left = nullptr; // the walk: why the file was left to zlib ...
+  uint32_t left_status = 0;   // ... and the decoder's status, where that was the reason
+  const gr::GzIndex* get() const { return idx ? idx.get() : rd ? rd->partial() : nullptr; }
 };
 
 gr_gzidx*
@@ -369,8 +372,8 @@ gr_gzidx_info(const gr_gzidx* h, uint64_t out[8])
   out[1] = ix ? ix->segs.size() : 0;
   out[2] = h->n_text;
   out[3] = ix ? ix->bytes() : 0;
-  out[4] = h->rd->dropped() && !h->idx;
-  out[5] = h->rd->failed();
+  out[4] = (h->rd ? h->rd->dropped() : true) && !h->idx;
+  out[5] = h->rd ? h->rd->failed() : false;
   out[6] = ix ? ix->max_text : 0;
   out[7] = ix ? ix->file_size : 0;
 }
@@ -395,6 +398,67 @@ gr_gzidx_matches(const gr_gzidx* h, const char* path)
 {
   const gr::GzIndex* ix = h->get();
   return ix && path && ix->matches(path) ? 1 : 0;
+}
+
+int
+gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, gr_gzidx** out, uint64_t stats[8])
+{
+  if (!ext || ext->struct_size < offsetof(grp_engine_ext, gzip_walk) + sizeof(ext->gzip_walk) || !ext->gzip_walk || (n && (!paths || !out))) {
+    return -1;
+  }
+  std::vector<std::string> files;
+  for (uint32_t i = 0; i < n; ++i) {
+    files.push_back(paths[i] ? paths[i] : "");
+  }
+  const auto launch = [&](const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n_steps, grp_gzip_walk_result* res, uint8_t* hist) {
+    return ext->gzip_walk(engine_ctx, comp, n_comp, dict, n_dict, steps, n_steps, res, hist, nullptr, 0, nullptr) == GRP_OK;
+  };
+  gr::GzWalkStats st;
+  std::vector<gr::GzWalkFile> got = gr::gzip_walk(files, span, max_bytes, gr::gzip_walk_sizes(), launch, &st);
+  for (uint32_t i = 0; i < n; ++i) {
+    out[i] = nullptr;
+    if (got[i].unreadable) {
+      continue;
+    }
+    out[i] = new gr_gzidx;
+    out[i]->n_text = got[i].index ? got[i].index->text_bytes : 0;
+    out[i]->idx = std::move(got[i].index);
+    out[i]->left = got[i].left;
+    out[i]->left_status = got[i].status;
+  }
+  if (stats) {
+    const uint64_t v[8] = { st.files, st.walked, st.left_to_zlib, st.rounds, st.text_bytes, st.launches, st.repeats, (uint64_t)(st.seconds * 1e6) };
+    std::memcpy(stats, v, sizeof v);
+  }
+  return 0;
+}
+
+gr_gzidx*
+gr_gzidx_build_device(const grp_engine_ext* ext, void* engine_ctx, const char* path, uint64_t span, uint64_t max_bytes)
+{
+  gr_gzidx* h = nullptr;
+  return gr_gzidx_build_device_many(ext, engine_ctx, &path, 1, span, max_bytes, &h, nullptr) == 0 ? h : nullptr;
+}
+
+long
+gr_gzip_header_bytes(const unsigned char* buf, size_t n)
+{
+  return gr::gzip_header_bytes(buf, n);
+}
+
+int
+gr_gzip_walk_switch(void)
+{
+  return gr::gzip_walk_switch();
+}
+
+const char*
+gr_gzidx_left(const gr_gzidx* h, uint32_t* status)
+{
+  if (status) {
+    *status = h ? h->left_status : 0;
+  }
+  return h ? h->left : nullptr;
 }
 
 void

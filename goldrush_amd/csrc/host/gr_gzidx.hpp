@@ -46,6 +46,7 @@ public:
 
 private:
   friend class GzIndexReader;
+  friend class GzWalker; // gr_gzwalk.hpp: the same index from steps of the engine's decoder
   static constexpr uint64_t kBlock = uint64_t(1) << 20; // histories are kept in blocks of this size, none across two
   std::vector<std::unique_ptr<uint8_t[]>> store_;
   uint64_t used_ = kBlock; // of the last block

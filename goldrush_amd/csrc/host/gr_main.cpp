@@ -118,5 +118,8 @@ main(int argc, char** argv)
     return grp_reads_gather(static_cast<grp_ctx*>(c), reinterpret_cast<const grp_reads* const*>(srcs), n_srcs, slices, n_slices, reinterpret_cast<grp_reads**>(out));
   };
   ext.rewind = [](void* c) { return grp_rewind(static_cast<grp_ctx*>(c)); };
+  ext.gzip_walk = [](void* c, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n, grp_gzip_walk_result* res, uint8_t* hist, char* text, uint64_t cap, uint32_t* bad) {
+    return grp_gzip_walk(static_cast<grp_ctx*>(c), comp, n_comp, dict, n_dict, steps, n, res, hist, text, cap, bad);
+  };
   return gr_path_main_ext(argc, argv, &vt, &ext);
 }

@@ -9,6 +9,7 @@
 #include "../../../include/grpath_host.h"
 #include "gr_fastq.hpp"
 #include "gr_golden.hpp"
+#include "gr_gzwalk.hpp"
 #include "gr_opts.hpp"
 #include "gr_params.hpp"
 #include "gr_passes.hpp"
@@ -148,6 +149,14 @@ read_options(PathRun& run, int argc, char** argv, Quiet& quiet)
     std::cerr << "goldrush-path: GRP_BAM_ALIGNED=" << e << ": the switch takes on or off" << std::endl;
     return 1;
   }
+  // GRP_GZIP_WALK=on: the restart points of the plain gzip inputs are found on the device in front of the first pass
+  // (gr_gzwalk.hpp).  Opt-in: it pays from some tens of files upward and loses on a single one
+  const int walk = gzip_walk_switch();
+  if (walk < 0) {
+    std::cerr << "goldrush-path: GRP_GZIP_WALK=" << getenv("GRP_GZIP_WALK") << ": the switch takes on or off" << std::endl;
+    return 1;
+  }
+  run.gzip_walk = walk == 1;
   return -1;
 }
 

@@ -3,6 +3,7 @@
 #include "gr_source.hpp"
 #include "gr_bgzf.hpp"
 #include "gr_fastq.hpp"
+#include "gr_gzwalk.hpp"
 #include "gr_params.hpp"
 
 #include <algorithm>
@@ -607,6 +608,67 @@ plan_feed(PathRun& run, size_t file, size_t chunk)
   return pl;
 }
 
+// GRP_GZIP_WALK=on, once per run, where the plans of the first pass's files are about to be made: every file that
+// plan_feed would read as text through GzIndexReader — gzip, not routed to the BGZF form, without an index, on an engine
+// that inflates segments — is walked on the device, all of them side by side (gr_gzwalk.hpp).  A file the walk completes
+// has its index in PathRun::gzidx and plan_feed chooses GzipSegFeed by itself; every other file is read as without the walk.
+void
+walk_gzip_files(PathRun& run)
+{
+  if (run.gzip_walked) {
+    return;
+  }
+  run.gzip_walked = true;
+  if (!run.gzip_walk || !run.ext.gzip_walk || !run.ext.gzip_inflate || !gzip_index_enabled()) {
+    return;
+  }
+  const char* e = getenv("GRP_BGZF");
+  const bool bgzf_routed = run.ext.bgzf_inflate && !(e && !strcmp(e, "off"));
+  std::vector<size_t> which;
+  std::vector<std::string> paths;
+  std::vector<unsigned char> head(BGZF_MAX_MEMBER);
+  for (size_t f = 0; f < run.files.size(); ++f) {
+    const FileProbe p = probe_file(run.files[f]);
+    if (!p.opened || !p.regular || p.magic != FileProbe::GZIP || run.gzidx[f]) {
+      continue;
+    }
+    if (bgzf_routed) { // (plan_feed's test: is the first member a complete BGZF member?)
+      const int fd = ::open(run.files[f].c_str(), O_RDONLY | O_CLOEXEC);
+      int err = 0;
+      const size_t k = pread_full(fd, head.data(), head.size(), 0, &err);
+      if (fd >= 0) {
+        ::close(fd);
+      }
+      grp_bgzf_block b;
+      if (k > 0 && bgzf_scan(head.data(), k, &b, 1, nullptr, nullptr) == 1) {
+        continue;
+      }
+    }
+    which.push_back(f);
+    paths.push_back(run.files[f]);
+  }
+  GzWalkStats st;
+  if (!paths.empty()) {
+    const auto launch = [&run](const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n, grp_gzip_walk_result* res, uint8_t* hist) {
+      return run.ext.gzip_walk(run.ctx, comp, n_comp, dict, n_dict, steps, n, res, hist, nullptr, 0, nullptr) == GRP_OK;
+    };
+    GzWalkBuffer pin, unpin;
+    if (run.vt.fastq_pin && run.vt.fastq_unpin) { // the windows of all files: one page-locked buffer (the source pins its own behind the walk)
+      pin = [&run](uint8_t* buf, size_t n) { (void)run.vt.fastq_pin(run.ctx, reinterpret_cast<const char*>(buf), n); };
+      unpin = [&run](uint8_t*, size_t) { (void)run.vt.fastq_unpin(run.ctx); };
+    }
+    std::vector<GzWalkFile> got = gzip_walk(paths, gzip_index_span(), gzip_index_max_bytes(), gzip_walk_sizes(), launch, &st, pin, unpin);
+    for (size_t i = 0; i < got.size(); ++i) {
+      if (got[i].index) {
+        run.gzidx[which[i]] = std::move(got[i].index);
+      }
+    }
+  }
+  if (getenv("GRP_TRACE_INGEST") && run.rank == 0) {
+    std::cerr << "GRP_TRACE_INGEST gzip walk: files=" << st.files << " walked=" << st.walked << " left_to_zlib=" << st.left_to_zlib << " rounds=" << st.rounds << " text=" << st.text_bytes << " seconds=" << st.seconds << std::endl;
+  }
+}
+
 std::unique_ptr<Feed>
 open_feed(PathRun& run, size_t file, const FilePlan& pl)
 {
@@ -656,6 +718,7 @@ public:
     chunk_ = std::max<size_t>(ingest_chunk_bytes(), 64);
     plan_.resize(n_files);
     feeds_.resize(n_files);
+    walk_gzip_files(run_);
     Feed::Sizes sz{ chunk_, 0, 0 };
     uint64_t largest = 0; // plain files, all of known size: the largest of them
     bool sized = true;

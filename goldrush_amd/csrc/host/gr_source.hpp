@@ -49,6 +49,9 @@ struct PathRun
   // a plain gzip input: the restart points the first pass that read that file to its end wrote down (gr_gzidx.hpp); the
   // passes behind it inflate its segments on the device.  One per file, each built, dropped and used on its own
   std::vector<std::shared_ptr<GzIndex>> gzidx;
+  // GRP_GZIP_WALK=on (read_options): in front of the first source of the run, the indexes of all its plain gzip files are
+  // built on the device, the files side by side (gr_gzwalk.hpp), so that the first pass reads them through segments too
+  bool gzip_walk = false, gzip_walked = false; // the switch; the walk has had its turn
   // a BGZF input: the members the last pass over that file walked, if it walked them to the file's end (BgzfFeed); a file
   // whose last pass did not go through the member feed, or left it for zlib at a member that is not BGZF, has none
   std::vector<std::shared_ptr<BgzfMap>> bgzf_map;

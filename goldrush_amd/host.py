@@ -123,9 +123,12 @@ READS_GATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.
 REWIND_FN = C.CFUNCTYPE(C.c_int, _vp)
 
 
+GZIP_WALK_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32))
+
+
 class grp_engine_ext(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bgzf_inflate", BGZF_INFLATE_FN), ("gzip_inflate", GZIP_INFLATE_FN), ("bam_parse", BAM_PARSE_FN), ("records_fetch", RECORDS_FETCH_FN),
-                ("bam_parse_ex", BAM_PARSE_EX_FN), ("reads_gather", READS_GATHER_FN), ("rewind", REWIND_FN)]
+                ("bam_parse_ex", BAM_PARSE_EX_FN), ("reads_gather", READS_GATHER_FN), ("rewind", REWIND_FN), ("gzip_walk", GZIP_WALK_FN)]
 
 
 class gr_bam_record(C.Structure):
@@ -188,6 +191,11 @@ SIGNATURES = {
     "gr_gzidx_segment": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "gr_gzidx_matches": (C.c_int, [_vp, C.c_char_p]),
     "gr_gzidx_free": (None, [_vp]),
+    "gr_gzidx_build_device_many": (C.c_int, [C.POINTER(grp_engine_ext), _vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(_vp), _vp]),
+    "gr_gzidx_build_device": (_vp, [C.POINTER(grp_engine_ext), _vp, C.c_char_p, C.c_uint64, C.c_uint64]),
+    "gr_gzidx_left": (C.c_char_p, [_vp, C.POINTER(C.c_uint32)]),
+    "gr_gzip_header_bytes": (C.c_long, [C.c_char_p, C.c_size_t]),
+    "gr_gzip_walk_switch": (C.c_int, []),
 }
 
 _lib = None
@@ -388,6 +396,48 @@ def gzip_index(path, span: int = 256 << 10, max_bytes: int = 16 << 30, stop_afte
         lib.gr_gzidx_free(h)
 
 
+def _gzidx_dict(lib, h, path) -> dict:
+    info = np.zeros(8, dtype=np.uint64)
+    lib.gr_gzidx_info(h, _p(info))
+    segs = []
+    seg = np.zeros(1, dtype=native.gzip_segment_dtype)
+    hist = np.zeros(32768, dtype=np.uint8)
+    for i in range(int(info[1])):
+        if lib.gr_gzidx_segment(h, i, _p(seg), _p(hist)) != 0:
+            raise RuntimeError("gr_gzidx_segment(%d) failed" % i)
+        g = seg[0]
+        segs.append(dict(comp_bit=int(g["comp_bit"]), n_bits=int(g["n_bits"]), dict=hist[:int(g["dict_len"])].tobytes(), text_len=int(g["text_len"]),
+                         crc32=int(g["crc32"]), flags=int(g["flags"])))
+    status = C.c_uint32()
+    left = lib.gr_gzidx_left(h, C.byref(status))
+    return dict(complete=bool(info[0]), segments=segs, n_text=int(info[2]), index_bytes=int(info[3]), dropped=bool(info[4]), failed=bool(info[5]),
+                max_text=int(info[6]), file_size=int(info[7]), matches=bool(lib.gr_gzidx_matches(h, os.fsencode(str(path)))),
+                left=left.decode() if left else None, status=status.value)
+
+
+def gzip_index_device(engine, paths, span: int = 256 << 10, max_bytes: int = 16 << 30):
+    """gr_gzidx_build_device_many: the index of every file of `paths` built by the engine's walk (grp_gzip_walk of `engine`, a
+    native.Engine), all files side by side.  Returns ([gzip_index's dict per file, with `left` (why the file was left to
+    zlib, or None) and `status`; None for a file that cannot be read], the walk's statistics)."""
+    lib = load()
+    ext = hip_engine_ext()
+    arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(str(p)) for p in paths])
+    hs = (_vp * max(len(paths), 1))()
+    stats = np.zeros(8, dtype=np.uint64)
+    if lib.gr_gzidx_build_device_many(C.byref(ext), engine._h, arr, len(paths), span, max_bytes, hs, _p(stats)) != 0:
+        raise RuntimeError("gr_gzidx_build_device_many failed")
+    out = []
+    try:
+        for h, path in zip(hs, paths):
+            out.append(_gzidx_dict(lib, h, path) if h else None)
+    finally:
+        for h in hs[:len(paths)]:
+            if h:
+                lib.gr_gzidx_free(h)
+    names = ("files", "walked", "left_to_zlib", "rounds", "text_bytes", "launches", "repeats", "microseconds")
+    return out, {k: int(v) for k, v in zip(names, stats)}
+
+
 def hip_engine_ext() -> grp_engine_ext:
     """The second table filled with the symbols of libgrpath_hip.so."""
     lib = native.load()
@@ -400,6 +450,7 @@ def hip_engine_ext() -> grp_engine_ext:
     ext.bam_parse_ex = C.cast(lib.grp_bam_parse_ex, BAM_PARSE_EX_FN)
     ext.reads_gather = C.cast(lib.grp_reads_gather, READS_GATHER_FN)
     ext.rewind = C.cast(lib.grp_rewind, REWIND_FN)
+    ext.gzip_walk = C.cast(lib.grp_gzip_walk, GZIP_WALK_FN)
     return ext
 
 

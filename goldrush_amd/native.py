@@ -134,6 +134,8 @@ SIGNATURES = {
     "grp_debug_bgzf_stats": (C.c_int, [_vp, _vp]),
     "grp_gzip_inflate": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
     "grp_debug_gzip_stats": (C.c_int, [_vp, _vp]),
+    "grp_gzip_walk": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "grp_gzip_status_text": (C.c_char_p, [C.c_uint32]),
     "grp_records_fetch": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "grp_reads_gather": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(_vp)]),
     "grp_reads_download": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),
@@ -167,6 +169,10 @@ fastq_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off
 bgzf_block_dtype = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 # grp_gzip_segment: a run of whole DEFLATE blocks out of a serial stream, from bit comp_bit on, with dict_len bytes of history
 gzip_segment_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_off", "<u8"), ("dict_len", "<u4"), ("text_len", "<u4"), ("crc32", "<u4"), ("flags", "<u4")])
+# grp_gzip_walk_step / grp_gzip_walk_result: one open step of grp_gzip_walk and its answer
+gzip_walk_step_dtype = np.dtype([("comp_bit", "<u8"), ("n_bits", "<u8"), ("dict_off", "<u8"), ("dict_len", "<u4"), ("min_text", "<u4"), ("room", "<u4"), ("reserved", "<u4")])
+gzip_walk_result_dtype = np.dtype([("bits", "<u8"), ("text_len", "<u4"), ("crc32", "<u4"), ("final", "<u4"), ("status", "<u4"), ("hist_len", "<u4"), ("reserved", "<u4")])
+GZIP_WALK_INPUT_ENDS, GZIP_WALK_NO_ROOM = 3, 19
 # grp_fetch_record: one record to format out of the units' text (offsets count in the concatenated text of the call's units)
 fetch_record_dtype = np.dtype([("id_off", "<u8"), ("seq_off", "<u8"), ("qual_off", "<u8"), ("out_off", "<u8"), ("id_len", "<u4"), ("seq_from", "<u4"), ("n_seq", "<u4"),
                               ("qual_from", "<u4"), ("n_qual", "<u4"), ("flags", "<u4")])
@@ -469,6 +475,36 @@ class Engine:
             e.bad_seg = None if bad.value == 0xFFFFFFFF else bad.value
             raise e
         return out[:total].tobytes()
+
+    # -- one open step in each of many gzip streams (include/grpath_ingest.h)
+    def gzip_walk(self, comp, dict_bytes, steps, want_text: bool = False, text_cap: "int | None" = None):
+        """grp_gzip_walk: steps = gzip_walk_step_dtype records (or (comp_bit, n_bits, dict_off, dict_len, min_text, room[,
+        reserved]) tuples).  Returns (gzip_walk_result_dtype records, [the new history of every step], [its text] if
+        want_text else None).  A table entry that is refused raises GrpError with .bad_step set; a step's status is its answer."""
+        buf = np.frombuffer(comp, dtype=np.uint8) if len(comp) else np.zeros(1, dtype=np.uint8)
+        dic = np.frombuffer(dict_bytes, dtype=np.uint8) if len(dict_bytes) else np.zeros(1, dtype=np.uint8)
+        if not isinstance(steps, np.ndarray):
+            steps = np.array([tuple(g) + (0,) * (7 - len(g)) for g in steps], dtype=gzip_walk_step_dtype)
+        steps = np.ascontiguousarray(steps, dtype=gzip_walk_step_dtype)
+        n = len(steps)
+        total = int(steps["room"].astype(np.uint64).sum())
+        cap = total if text_cap is None else text_cap
+        res = np.zeros(max(n, 1), dtype=gzip_walk_result_dtype)
+        hist = np.zeros(max(n, 1) * 32768, dtype=np.uint8)
+        text = np.zeros(max(cap, 1), dtype=np.uint8) if want_text else None
+        bad = C.c_uint32(0xFFFFFFFF)
+        rc = self.lib.grp_gzip_walk(self._h, _ptr(buf), len(comp), _ptr(dic), len(dict_bytes), _ptr(steps) if n else None, n, _ptr(res), _ptr(hist), _ptr(text), cap if want_text else 0, C.byref(bad))
+        if rc != GRP_OK:
+            e = GrpError(rc, (self.lib.grp_last_error(self._h) or b"").decode())
+            e.bad_step = None if bad.value == 0xFFFFFFFF else bad.value
+            raise e
+        res = res[:n]
+        hists = [hist[32768 * i:32768 * i + int(res[i]["hist_len"])].tobytes() for i in range(n)]
+        texts = None
+        if want_text:
+            offs = np.concatenate([[0], np.cumsum(steps["room"].astype(np.uint64))]).astype(np.int64)
+            texts = [text[offs[i]:offs[i] + int(res[i]["text_len"])].tobytes() for i in range(n)]
+        return res, hists, texts
 
     # -- records fetched out of members / segments and formatted on the device (include/grpath_ingest.h)
     def records_fetch(self, unit_kind: int, comp, dict_bytes, units, recs, out_flags: int, out: np.ndarray, out_cap: "int | None" = None):

@@ -636,6 +636,12 @@ int grp_debug_bgzf_stats(const grp_ctx* ctx, uint64_t out[4]);
 typedef struct grp_gzip_segment grp_gzip_segment;
 int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_segment* segs, uint32_t n_segs, char* text_out, uint64_t text_cap, uint32_t* bad_seg);
 int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
+/* ... whose restart points the device finds itself, one step in each of many files side by side (grpath_ingest.h) */
+typedef struct grp_gzip_walk_step grp_gzip_walk_step;
+typedef struct grp_gzip_walk_result grp_gzip_walk_result;
+int grp_gzip_walk(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n_steps, grp_gzip_walk_result* results, uint8_t* hist_out, char* text_out,
+                  uint64_t text_cap, uint32_t* bad_step);
+const char* grp_gzip_status_text(uint32_t status);
 /* ... and the records of an unaligned BAM stream, parsed where FASTQ text is (grpath_ingest.h) */
 typedef struct grp_fastq grp_fastq;
 int grp_bam_parse(grp_ctx* ctx, const char* bytes, uint64_t n_bytes, int final_chunk, grp_fastq** out, uint64_t* n_records, uint64_t* bytes_consumed, uint64_t* bad_offset);

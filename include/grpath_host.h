@@ -363,7 +363,28 @@ typedef struct
    * the silver files */
   int (*reads_gather)(void* ctx, const void* const* srcs, uint32_t n_srcs, const grp_read_slice* slices, uint32_t n_slices, void** out);
   int (*rewind)(void* ctx);
+  /* grp_gzip_walk: with it (and GRP_GZIP_WALK=on), the restart points of the run's plain gzip files are found on the
+   * device in front of the first pass, all files side by side (csrc/host/gr_gzwalk.hpp), and the first pass over them
+   * inflates their segments through gzip_inflate too; without it that pass reads them through zlib and builds the index */
+  int (*gzip_walk)(void* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n_steps, grp_gzip_walk_result* results, uint8_t* hist_out, char* text_out,
+                   uint64_t text_cap, uint32_t* bad_step);
 } grp_engine_ext;
+
+/* The same index built by the engine's walk (csrc/host/gr_gzwalk.hpp; ext->gzip_walk on engine_ctx), the n files side by
+ * side: out[i] is a handle like gr_gzidx_build's (_info: [2] the text the index describes, [4] the file was left to zlib,
+ * [5] 0; _segment / _matches as above) — NULL where the file cannot be read as a regular file.  The sizes come from
+ * GRP_GZIP_WALK_ROOM.  stats, if not NULL: files, walked, left to zlib, rounds, bytes of text decoded, launches, repeated
+ * steps, microseconds.  -1: no walk in the table, or a bad argument.  _build_device: one file; NULL also without a walk.
+ * _left: why the file was left to zlib (NULL: it was not), *status = the decoder's status where that was the reason. */
+int gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, gr_gzidx** out, uint64_t stats[8]);
+gr_gzidx* gr_gzidx_build_device(const grp_engine_ext* ext, void* engine_ctx, const char* path, uint64_t span, uint64_t max_bytes);
+const char* gr_gzidx_left(const gr_gzidx* h, uint32_t* status);
+/* The two pieces of the walk that need no engine.  _header_bytes: the gzip header at buf[0, n) as the walk parses it (FEXTRA,
+ * FNAME, FCOMMENT, FHCRC with its CRC16): its length; 0: it does not end inside the n bytes; -1: not a header zlib takes
+ * (magic, a method other than 8, a reserved flag, a header CRC that does not match).  _switch: GRP_GZIP_WALK as the host
+ * program reads it: 1 on, 0 off or unset, -1 any other value (the run ends with status 1 before its first pass). */
+long gr_gzip_header_bytes(const unsigned char* buf, size_t n);
+int gr_gzip_walk_switch(void);
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */
 int gr_path_main(int argc, char** argv, const grp_engine_vt* vt); /* = gr_path_main_ext(argc, argv, vt, NULL) */

@@ -149,6 +149,51 @@ int grp_gzip_inflate(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const u
 int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
 
 /*
+ * ---- plain gzip FASTQ, many files: the restart points found on the device ---------------------------------------------
+ * One gzip stream is serial, but every FILE's first member starts at a known bit behind its header, with no history, and
+ * where a block ends is known the moment the decoder gets there.  grp_gzip_walk takes one step in each of many streams
+ * side by side, one wave per step (csrc/grp_inflate.inc: the open form of the decoder): from a bit where a block begins,
+ * with the history in front of it, whole blocks until at least min_text bytes of text have come out or a final block has
+ * ended.  The host (csrc/host/gr_gzwalk.hpp) parses the headers and trailers, strings the steps of a file together and
+ * writes down the index GzIndexReader would have written.  Nothing is guessed: a step starts behind a header the host
+ * parsed or at a boundary the step in front of it reached.  The text is decoded to find the boundaries and thrown away.
+ */
+struct grp_gzip_walk_step
+{
+  uint64_t comp_bit;   /* the step's first bit inside `comp` (`comp` starts on a byte of the file: a stored block aligns to it) */
+  uint64_t n_bits;     /* the bits there are from comp_bit on: the step consumes what its blocks take of them */
+  uint64_t dict_off;   /* its history inside `dict` */
+  uint32_t dict_len;   /* 0 .. 32768 */
+  uint32_t min_text;   /* it stops behind the first block where at least this much text has come out (or behind a final block) */
+  uint32_t room;       /* ... and may produce this much */
+  uint32_t reserved;
+};
+struct grp_gzip_walk_result
+{
+  uint64_t bits;       /* consumed: comp_bit + bits is the block boundary the step ended at */
+  uint32_t text_len;   /* that came out */
+  uint32_t crc32;      /* of that text */
+  uint32_t final;      /* 1: the boundary lies behind a final block */
+  uint32_t status;     /* 0, or why the step did not end at a boundary (GRP_GZIP_WALK_*, else a damaged stream); then the other fields are 0 */
+  uint32_t hist_len;   /* min(32768, dict_len + text_len): the last bytes of history and text, the history of the next step */
+  uint32_t reserved;
+}; /* (the typedefs are in grpath.h) */
+#define GRP_GZIP_WALK_INPUT_ENDS 3u /* n_bits ended inside a block, or in front of the next one: the step needs more compressed bytes */
+#define GRP_GZIP_WALK_NO_ROOM 19u   /* the text of the step's blocks does not fit `room` */
+
+/* One step in each of n_steps streams.  results[i] is step i's answer; hist_out + 32768 * i receives its hist_len bytes of
+ * new history (host memory, 32768 * n_steps bytes); text_out, if not NULL, the text of step i at the sum of the ROOMS in
+ * front of it (tests; the product passes NULL).  Synchronous, on the side stream, with the threading rules of
+ * grp_gzip_inflate.  The whole table is checked before anything is launched (the bits inside comp, the history inside
+ * dict, dict_len <= 32768, a reserved field that is not 0, the sum of the rooms <= 2^34 and, with text_out, <= text_cap:
+ * GRP_ERR_INVALID, *bad_step = the entry).  A step that ends with a status is NOT a failed call: the status is that
+ * step's answer, and the other steps of the call are not touched by it.  grp_gzip_status_text: the words of a status.
+ * At most 4 GiB of compressed bytes, 4 GiB of histories and 2^22 steps per call. */
+int grp_gzip_walk(grp_ctx* ctx, const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n_steps, grp_gzip_walk_result* results, uint8_t* hist_out, char* text_out,
+                  uint64_t text_cap, uint32_t* bad_step);
+const char* grp_gzip_status_text(uint32_t status);
+
+/*
  * ---- unaligned BAM: records instead of four text lines ---------------------------------------------------------------
  * PacBio and Nanopore deliver long reads as unaligned BAM: a BGZF container (grp_bgzf_inflate turns its members into
  * bytes) around a header and records of 4-bit bases and raw Phred bytes.  The program reads a BAM file as its FASTQ twin

@@ -18,6 +18,13 @@
 //   /tmp/inflate_host_check /tmp/inflate_gen/members.bin
 //   /tmp/inflate_host_check --segments /tmp/inflate_gen/segments.bin
 //   /tmp/inflate_host_check --gzip /tmp/inflate_gen/gzip/*.gz
+// The open form (k_inflate<InfWalkEntry>) with the rounds that drive it (csrc/host/gr_gzwalk.cpp, compiled into this program): every
+// file is indexed through GzIndexReader and through gzip_walk over the host-compiled decoder, at spans 1, 4096 and 262144,
+// with the default sizes and with tiny ones (every step repeated until it fits); the two indexes must agree field by field.
+// Then one open step per segment of the reader's index and its damaged forms (a shorter history, fewer bits, a room one
+// byte short), and damaged copies of the file (flipped bits, cut short, bytes appended): each must be left to zlib or
+// indexed as the reader indexes it.
+//   /tmp/inflate_host_check --walk /tmp/gzip_cases/*.gz
 #define GRP_INFLATE_HOST
 #include <cstdint>
 #include <cstdio>
@@ -28,6 +35,8 @@
 #include <zlib.h>
 #include "../../include/grpath_ingest.h"
 #include "../../goldrush_amd/csrc/host/gr_gzidx.hpp"
+#include "../../goldrush_amd/csrc/host/gr_gzwalk.cpp" // (the rounds themselves: the command lines above stay as they are)
+#include <unistd.h>
 #include "../../goldrush_amd/csrc/host/gr_fastq.hpp"
 #include "../../goldrush_amd/csrc/grp_inflate.inc"
 // file: u32 n; per case: u32 comp_len, u32 text_len, u32 expect_ok, u32 crc, u32 pre (bytes in front of payload), payload(pre+comp_len), text
@@ -146,6 +155,197 @@ static int gzip_main(int argc, char** argv)
   return bad != 0;
 }
 
+// ---- --walk ------------------------------------------------------------------------------------------------------------
+static uint64_t g_walk_steps = 0, g_walk_overrun = 0;
+
+// grp_gzip_walk on the host: the engine's buffers (the bytes, 8 bytes of zero padding), a text buffer of exactly `room`
+static bool walk_launch(const uint8_t* comp, uint64_t n_comp, const uint8_t* dict, uint64_t n_dict, const grp_gzip_walk_step* steps, uint32_t n, grp_gzip_walk_result* res, uint8_t* hist)
+{
+  static uint32_t tabs[1056]; static bool have = false;
+  if (!have) { crc_tables(tabs); have = true; }
+  std::vector<uint32_t> cw((n_comp + 8 + 3) / 4 + 1, 0), dw((n_dict + 8 + 3) / 4 + 1, 0);
+  memcpy(cw.data(), comp, n_comp); memcpy(dw.data(), dict, n_dict);
+  for (uint32_t i = 0; i < n; ++i) {
+    ++g_walk_steps;
+    std::vector<char> out((size_t)steps[i].room + 1, 0x55);
+    std::vector<uint8_t> h(32768 + 1, 0x55);
+    const InfWalkEntry e{ steps[i], &res[i], h.data() };
+    memset(&g_s, 0xAA, sizeof g_s);
+    const uint32_t st = inf_entry(g_s, (const uint8_t*)cw.data(), (const uint8_t*)dw.data(), e, out.data());
+    if ((uint8_t)out[steps[i].room] != 0x55 || h[32768] != 0x55) ++g_walk_overrun;
+    if (st != 0) { res[i] = grp_gzip_walk_result{ 0, 0, 0, 0, st, 0, 0 }; continue; }
+    res[i].crc32 = crc_member(g_cs, tabs, out.data(), res[i].text_len);
+    memcpy(hist + (size_t)32768 * i, h.data(), res[i].hist_len);
+  }
+  return true;
+}
+
+static std::unique_ptr<gr::GzIndex> reader_index(const char* path, uint64_t span, bool* failed, std::vector<char>* text = nullptr)
+{
+  gr::GzIndexReader rd(path, span, uint64_t(1) << 32);
+  std::vector<char> piece(1 << 16);
+  size_t k;
+  while ((k = rd.read(piece.data(), piece.size())) > 0) { if (text) text->insert(text->end(), piece.data(), piece.data() + k); }
+  *failed = rd.failed();
+  return rd.take();
+}
+
+static bool same_index(const gr::GzIndex& a, const gr::GzIndex& b, const char* what)
+{
+  if (a.segs.size() != b.segs.size() || a.text_bytes != b.text_bytes || a.max_text != b.max_text || a.max_comp != b.max_comp || a.bytes() != b.bytes() || a.file_size != b.file_size) {
+    printf("%s: totals differ (segments %zu / %zu, text %llu / %llu, bytes %llu / %llu)\n", what, a.segs.size(), b.segs.size(), (unsigned long long)a.text_bytes, (unsigned long long)b.text_bytes, (unsigned long long)a.bytes(), (unsigned long long)b.bytes());
+    return false;
+  }
+  for (size_t i = 0; i < a.segs.size(); ++i) {
+    const gr::GzSegment &x = a.segs[i], &y = b.segs[i];
+    if (x.comp_bit != y.comp_bit || x.n_bits != y.n_bits || x.dict_at != y.dict_at || x.dict_len != y.dict_len || x.text_len != y.text_len || x.crc32 != y.crc32 || x.flags != y.flags || (x.dict_len != 0 && memcmp(a.dict(x), b.dict(y), x.dict_len) != 0)) {
+      printf("%s: segment %zu differs (bit %llu / %llu, bits %llu / %llu, dict %u / %u, text %u / %u, crc %08x / %08x, flags %u / %u)\n", what, i, (unsigned long long)x.comp_bit, (unsigned long long)y.comp_bit, (unsigned long long)x.n_bits,
+             (unsigned long long)y.n_bits, x.dict_len, y.dict_len, x.text_len, y.text_len, x.crc32, y.crc32, x.flags, y.flags);
+      return false;
+    }
+  }
+  return true;
+}
+
+// One open step per segment of the reader's index, asked for the segment's own text in a room of exactly that size: it must
+// end where the segment ends.  Then the damaged forms of the --gzip mode that carry over to a step, which has no given end:
+// the history shorter by a byte, by half, gone (refused, or the same text where no distance reaches that far), the bits cut
+// inside the segment (never the whole text: the input ends, or the step stops at an earlier boundary with a prefix of
+// it), a room one byte short (the status of its own) — and nothing written behind the room or the 32 KiB of history.
+static void walk_steps(const char* path, const std::vector<uint8_t>& raw, int* bad, uint64_t* n_steps, uint64_t* n_forms, uint64_t* n_refused, uint64_t* n_same)
+{
+  uint32_t tabs[1056]; crc_tables(tabs);
+  std::vector<uint32_t> compw((raw.size() + 8 + 3) / 4 + 1, 0);
+  uint8_t* comp = (uint8_t*)compw.data();
+  memcpy(comp, raw.data(), raw.size());
+  bool failed = false; std::vector<char> text;
+  std::unique_ptr<gr::GzIndex> ix = reader_index(path, 4096, &failed, &text);
+  if (!ix) return;
+  uint64_t off = 0;
+  for (size_t i = 0; i < ix->segs.size(); off += ix->segs[i].text_len, ++i) {
+    const gr::GzSegment& g = ix->segs[i];
+    if (ix->segs.size() > 40 && i % 7 != 0) continue;
+    std::vector<uint32_t> dictw((g.dict_len + 8 + 3) / 4 + 1, 0);
+    uint8_t* dict = (uint8_t*)dictw.data();
+    if (g.dict_len) memcpy(dict, ix->dict(g), g.dict_len);
+    struct Form { grp_gzip_walk_step s; int kind; }; // 0 the step itself, 1 a shorter history, 2 fewer bits, 3 a room one byte short
+    std::vector<Form> forms;
+    const grp_gzip_walk_step e{ g.comp_bit, raw.size() * 8 - g.comp_bit, 0, g.dict_len, g.text_len, g.text_len, 0 };
+    forms.push_back({ e, 0 });
+    if (g.dict_len) { grp_gzip_walk_step x = e; x.dict_off = 1; x.dict_len = g.dict_len - 1; forms.push_back({ x, 1 }); x.dict_len = g.dict_len / 2; x.dict_off = g.dict_len - x.dict_len; forms.push_back({ x, 1 }); x.dict_len = 0; x.dict_off = 0; forms.push_back({ x, 1 }); }
+    for (int64_t d : { 1ll, 3ll, 8ll, 17ll, 1000ll }) { if ((int64_t)g.n_bits > d) { grp_gzip_walk_step x = e; x.n_bits = g.n_bits - (uint64_t)d; forms.push_back({ x, 2 }); } }
+    { grp_gzip_walk_step x = e; x.n_bits = g.n_bits; forms.push_back({ x, 0 }); } // exactly the segment's bits: the same answer
+    { grp_gzip_walk_step x = e; x.room = g.text_len - 1; forms.push_back({ x, 3 }); }
+    for (size_t q = 0; q < forms.size(); ++q) {
+      const grp_gzip_walk_step& s = forms[q].s;
+      std::vector<char> out((size_t)s.room + 1, 0x55);
+      std::vector<uint8_t> h(32768 + 1, 0x55);
+      grp_gzip_walk_result r{};
+      const InfWalkEntry w{ s, &r, h.data() };
+      memset(&g_s, 0xAA, sizeof g_s);
+      const uint32_t st = inf_entry(g_s, comp, dict, w, out.data());
+      ++*n_steps;
+      if (forms[q].kind) ++*n_forms;
+      if ((uint8_t)out[s.room] != 0x55 || h[32768] != 0x55) { printf("%s seg %zu form %zu: wrote behind the room or the history\n", path, i, q); ++*bad; }
+      if (st != r.status) { printf("%s seg %zu form %zu: the status returned is not the status stored\n", path, i, q); ++*bad; }
+      // (a member's last segment may end with blocks without text, which the walk's NEXT step finds: the step then stops in
+      // front of them with all of the text, and a step of its own, from there, must end the member without a byte)
+      const bool all_text = st == 0 && r.text_len == g.text_len && memcmp(out.data(), text.data() + off, g.text_len) == 0 && crc_member(g_cs, tabs, out.data(), r.text_len) == g.crc32;
+      const bool in_front_of_empty_blocks = all_text && (g.flags & 1u) && !r.final && r.bits < g.n_bits && r.bits <= s.n_bits;
+      bool whole = all_text && ((r.bits == g.n_bits && r.final == (g.flags & 1u)) || in_front_of_empty_blocks);
+      if (whole && in_front_of_empty_blocks && forms[q].kind == 0) {
+        std::vector<uint32_t> d2w(32768 / 4 + 3, 0);
+        memcpy(d2w.data(), h.data(), r.hist_len);
+        std::vector<char> o2(2, 0x55);
+        std::vector<uint8_t> h2(32768 + 1, 0x55);
+        grp_gzip_walk_result r2{};
+        const InfWalkEntry w2{ grp_gzip_walk_step{ g.comp_bit + r.bits, raw.size() * 8 - g.comp_bit - r.bits, 0, r.hist_len, 1, 1, 0 }, &r2, h2.data() };
+        const uint32_t st2 = inf_entry(g_s, comp, (const uint8_t*)d2w.data(), w2, o2.data());
+        ++*n_steps;
+        whole = st2 == 0 && r2.final == 1 && r2.text_len == 0 && r.bits + r2.bits == g.n_bits && r2.hist_len == r.hist_len && memcmp(h2.data(), h.data(), r.hist_len) == 0;
+      }
+      switch (forms[q].kind) {
+        case 0:
+          if (!whole) { printf("%s seg %zu form %zu: status %u, the step does not end where the segment ends\n", path, i, q, st); ++*bad; }
+          else if (r.hist_len != std::min<uint64_t>(32768, (uint64_t)g.dict_len + g.text_len)) { printf("%s seg %zu: history of %u bytes\n", path, i, r.hist_len); ++*bad; }
+          break;
+        case 1:
+          if (st != 0) ++*n_refused; else if (whole) ++*n_same; else { printf("%s seg %zu form %zu: a shorter history gave another answer\n", path, i, q); ++*bad; }
+          break;
+        case 2:
+          if (st != 0) ++*n_refused;
+          else if (in_front_of_empty_blocks) ++*n_same; // (the cut lies in the blocks without text behind it)
+          else { printf("%s seg %zu form %zu: fewer bits than the segment has, and the step ended with status 0, %llu bits, %u bytes\n", path, i, q, (unsigned long long)r.bits, r.text_len); ++*bad; }
+          break;
+        default:
+          if (st != INF_NO_ROOM) { printf("%s seg %zu form %zu: a room one byte short gave status %u\n", path, i, q, st); ++*bad; } else ++*n_refused;
+      }
+    }
+  }
+}
+
+static int walk_main(int argc, char** argv)
+{
+  uint64_t n_step_checks = 0, n_step_forms = 0, n_step_refused = 0, n_step_same = 0;
+  int bad = 0; uint64_t n_same = 0, n_dmg = 0, n_dmg_left = 0, n_dmg_same = 0, n_repeats = 0;
+  gr::GzWalkSizes tiny; tiny.room = 64; tiny.window = 64; tiny.cap = uint64_t(1) << 26;
+  const gr::GzWalkSizes sizes[2] = { gr::GzWalkSizes(), tiny };
+  char tmp[] = "/tmp/inflate_walk_XXXXXX";
+  const int tfd = mkstemp(tmp);
+  if (tfd < 0) { printf("no temporary file\n"); return 2; }
+  close(tfd);
+  for (int a = 2; a < argc; ++a) {
+    FILE* f = fopen(argv[a], "rb");
+    if (!f) { printf("%s: cannot open\n", argv[a]); return 2; }
+    std::vector<uint8_t> raw; uint8_t buf[65536]; size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) raw.insert(raw.end(), buf, buf + k);
+    fclose(f);
+    for (uint64_t span : { uint64_t(1), uint64_t(4096), uint64_t(262144) }) {
+      bool failed = false;
+      std::unique_ptr<gr::GzIndex> want = reader_index(argv[a], span, &failed);
+      if (!want) { printf("%s span %llu: the reader has no index\n", argv[a], (unsigned long long)span); ++bad; continue; }
+      for (int z = 0; z < 2; ++z) {
+        gr::GzWalkStats st;
+        std::vector<gr::GzWalkFile> got = gr::gzip_walk({ argv[a] }, span, uint64_t(1) << 32, sizes[z], walk_launch, &st);
+        n_repeats += st.repeats;
+        char what[512]; snprintf(what, sizeof what, "%s span %llu sizes %d", argv[a], (unsigned long long)span, z);
+        if (!got[0].index) { printf("%s: left to zlib: %s (status %u)\n", what, got[0].left, got[0].status); ++bad; continue; }
+        if (!same_index(*want, *got[0].index, what)) { ++bad; continue; }
+        ++n_same;
+      }
+    }
+    walk_steps(argv[a], raw, &bad, &n_step_checks, &n_step_forms, &n_step_refused, &n_step_same);
+    // damaged copies, at span 4096
+    uint64_t r = 0x9e3779b97f4a7c15ull * (uint64_t)(a + 1);
+    for (int t = 0; t < 40; ++t) {
+      std::vector<uint8_t> d = raw;
+      r = r * 6364136223846793005ull + 1442695040888963407ull;
+      if (t < 28) { const uint64_t bit = (r >> 20) % (raw.size() * 8); d[bit >> 3] ^= (uint8_t)(1u << (bit & 7)); }
+      else if (t < 36) { d.resize((size_t)((r >> 20) % raw.size())); }
+      else { d.insert(d.end(), (size_t)(t - 35), (uint8_t)(t == 39 ? 0x1f : 0)); }
+      FILE* o = fopen(tmp, "wb");
+      if (!o || fwrite(d.data(), 1, d.size(), o) != d.size()) { printf("cannot write %s\n", tmp); return 2; }
+      fclose(o);
+      ++n_dmg;
+      bool failed = false;
+      std::unique_ptr<gr::GzIndex> want = reader_index(tmp, 4096, &failed);
+      std::vector<gr::GzWalkFile> got = gr::gzip_walk({ tmp }, 4096, uint64_t(1) << 32, sizes[t & 1], walk_launch, nullptr);
+      if (!got[0].index) { ++n_dmg_left; continue; }
+      char what[512]; snprintf(what, sizeof what, "%s damaged form %d", argv[a], t);
+      if (!want || failed) { printf("%s: the walk indexed what the reader %s\n", what, failed ? "refused" : "dropped"); ++bad; continue; }
+      if (!same_index(*want, *got[0].index, what)) { ++bad; continue; }
+      ++n_dmg_same;
+    }
+  }
+  unlink(tmp);
+  if (g_walk_overrun) { printf("%llu steps wrote behind their room or their history\n", (unsigned long long)g_walk_overrun); ++bad; }
+  printf("steps: %llu open steps over the reader's segments, %llu damaged forms: %llu refused, %llu gave the segment's text\n", (unsigned long long)n_step_checks, (unsigned long long)n_step_forms, (unsigned long long)n_step_refused,
+         (unsigned long long)n_step_same);
+  printf("walk: %llu indexes equal the reader's; %llu steps, %llu repeated; %llu damaged files: %llu left to zlib, %llu indexed as the reader does; %d bad\n", (unsigned long long)n_same, (unsigned long long)g_walk_steps,
+         (unsigned long long)n_repeats, (unsigned long long)n_dmg, (unsigned long long)n_dmg_left, (unsigned long long)n_dmg_same, bad);
+  return bad != 0;
+}
+
 // hand-made segments (inflate_host_cases.py: write_segments): each with its own file and a history at a given alignment
 static int segments_main(const char* path)
 {
@@ -186,6 +386,9 @@ int main(int argc, char** argv)
 {
   if (argc >= 3 && !strcmp(argv[1], "--gzip")) {
     return gzip_main(argc, argv);
+  }
+  if (argc >= 3 && !strcmp(argv[1], "--walk")) {
+    return walk_main(argc, argv);
   }
   if (argc >= 3 && !strcmp(argv[1], "--segments")) {
     return segments_main(argv[2]);
