@@ -400,8 +400,10 @@ gr_gzidx_matches(const gr_gzidx* h, const char* path)
   return ix && path && ix->matches(path) ? 1 : 0;
 }
 
+namespace {
+
 int
-gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, gr_gzidx** out, uint64_t stats[8])
+gzidx_build_device(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, const gr::GzWalkMembers& members, gr_gzidx** out, uint64_t* stats, size_t n_stats)
 {
   if (!ext || ext->struct_size < offsetof(grp_engine_ext, gzip_walk) + sizeof(ext->gzip_walk) || !ext->gzip_walk || (n && (!paths || !out))) {
     return -1;
@@ -414,7 +416,7 @@ gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const ch
     return ext->gzip_walk(engine_ctx, comp, n_comp, dict, n_dict, steps, n_steps, res, hist, nullptr, 0, nullptr) == GRP_OK;
   };
   gr::GzWalkStats st;
-  std::vector<gr::GzWalkFile> got = gr::gzip_walk(files, span, max_bytes, gr::gzip_walk_sizes(), launch, &st);
+  std::vector<gr::GzWalkFile> got = gr::gzip_walk(files, span, max_bytes, gr::gzip_walk_sizes(), launch, &st, nullptr, nullptr, members);
   for (uint32_t i = 0; i < n; ++i) {
     out[i] = nullptr;
     if (got[i].unreadable) {
@@ -427,10 +429,27 @@ gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const ch
     out[i]->left_status = got[i].status;
   }
   if (stats) {
-    const uint64_t v[8] = { st.files, st.walked, st.left_to_zlib, st.rounds, st.text_bytes, st.launches, st.repeats, (uint64_t)(st.seconds * 1e6) };
-    std::memcpy(stats, v, sizeof v);
+    const uint64_t v[16] = { st.files, st.walked, st.left_to_zlib, st.rounds, st.text_bytes, st.launches, st.repeats, (uint64_t)(st.seconds * 1e6),
+                             st.candidates, st.streams, st.adopted, st.dropped, st.max_in_flight, st.wasted_text, (uint64_t)(st.scan_seconds * 1e6), 0 };
+    std::memcpy(stats, v, n_stats * sizeof(uint64_t));
   }
   return 0;
+}
+
+} // namespace
+
+int
+gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, gr_gzidx** out, uint64_t stats[8])
+{
+  return gzidx_build_device(ext, engine_ctx, paths, n, span, max_bytes, gr::GzWalkMembers(), out, stats, 8);
+}
+
+int
+gr_gzidx_build_device_many_ex(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, int members, gr_gzidx** out, uint64_t stats[16])
+{
+  gr::GzWalkMembers m = gr::gzip_walk_members(); // (the budget: GRP_GZIP_WALK_STREAMS)
+  m.on = members != 0;
+  return gzidx_build_device(ext, engine_ctx, paths, n, span, max_bytes, m, out, stats, 16);
 }
 
 gr_gzidx*
@@ -450,6 +469,12 @@ int
 gr_gzip_walk_switch(void)
 {
   return gr::gzip_walk_switch();
+}
+
+int
+gr_gzip_walk_members_switch(void)
+{
+  return gr::gzip_walk_members_switch();
 }
 
 const char*

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
+#include <map>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -18,6 +19,25 @@ gzip_walk_switch()
 {
   const char* e = getenv("GRP_GZIP_WALK");
   return !e || !strcmp(e, "off") ? 0 : !strcmp(e, "on") ? 1 : -1;
+}
+
+int
+gzip_walk_members_switch()
+{
+  const char* e = getenv("GRP_GZIP_WALK_MEMBERS");
+  return !e || !strcmp(e, "off") ? 0 : !strcmp(e, "on") ? 1 : -1;
+}
+
+GzWalkMembers
+gzip_walk_members()
+{
+  GzWalkMembers m;
+  m.on = gzip_walk_members_switch() == 1;
+  if (const char* e = getenv("GRP_GZIP_WALK_STREAMS")) {
+    unsigned long long v = 0;
+    m.streams = sscanf(e, "%llu", &v) == 1 && v ? v : m.streams;
+  }
+  return m;
 }
 
 GzWalkSizes
@@ -123,18 +143,16 @@ read_at(const std::string& path, uint8_t* to, size_t n, uint64_t off, int* err)
 class GzWalker
 {
 public:
-  GzWalker(const std::vector<std::string>& paths, uint64_t span, uint64_t max_bytes, const GzWalkSizes& sizes)
+  GzWalker(const std::vector<std::string>& paths, uint64_t span, uint64_t max_bytes, const GzWalkSizes& sizes, const GzWalkMembers& members, GzWalkStats& stats)
     : span_(std::max<uint64_t>(span, 1))
     , max_bytes_(max_bytes)
     , sizes_(sizes)
+    , members_(members)
     , files_(paths.size())
   {
     for (size_t i = 0; i < paths.size(); ++i) {
       File& f = files_[i];
       f.path = paths[i];
-      f.room = sizes_.room;
-      f.window = sizes_.window;
-      f.hist.resize(32768);
       struct stat st;
       if (stat(f.path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
         f.left = "it cannot be read as a regular file";
@@ -146,45 +164,72 @@ public:
       f.ix->file_size = f.size;
       f.ix->mtime_s = (int64_t)st.st_mtim.tv_sec;
       f.ix->mtime_ns = (int64_t)st.st_mtim.tv_nsec;
-      begin_member(f, 0);
+      f.head = new_stream(f, false);
+      begin_member(*f.head, 0);
+      if (f.head->left) {
+        f.left = f.head->left;
+      } else if (members_.on) {
+        scan(f, stats);
+      }
     }
   }
 
   void run(const GzWalkLaunch& launch, GzWalkStats& stats, const GzWalkBuffer& pin, const GzWalkBuffer& unpin)
   {
-    std::vector<File*> active;
-    for (File& f : files_) {
-      if (!f.left && !f.done) {
-        active.push_back(&f);
+    // the window buffer once, for the first windows of all streams there can be at a time; it grows only where a step is
+    // repeated with more
+    size_t cap = 0, ahead = 0;
+    for (const File& f : files_) {
+      if (live(f)) {
+        cap += (size_t)((f.head->window + 7) & ~uint64_t(7));
+        ahead += f.cand.size();
       }
     }
-    // the window buffer once, for the first windows of all files; it grows only where a step is repeated with more
-    size_t cap = 0;
-    for (const File* f : active) {
-      cap += (size_t)((f->window + 7) & ~uint64_t(7));
-    }
+    const bool any = cap != 0;
+    cap += (size_t)std::min<uint64_t>(ahead, members_.streams) * (size_t)((sizes_.window + 7) & ~uint64_t(7));
     buf_.resize(cap + 8);
-    if (pin && !active.empty()) {
+    if (pin && any) {
       pin(buf_.data(), buf_.size());
     }
-    bool pinned = pin && !active.empty();
+    const bool pinned = pin && any;
+    std::vector<Stream*> active;
     std::vector<grp_gzip_walk_step> steps;
     std::vector<grp_gzip_walk_result> res;
     std::vector<uint8_t> dict, hist_out;
-    while (!active.empty()) {
+    for (bool failed = false; !failed;) {
+      if (members_.on) {
+        admit(stats);
+      }
+      active.clear();
+      for (File& f : files_) {
+        if (live(f)) {
+          active.push_back(f.head.get());
+          for (auto& s : f.ahead) {
+            if (s.second->stepping()) {
+              active.push_back(s.second.get());
+            }
+          }
+        }
+      }
+      if (active.empty()) {
+        break;
+      }
       ++stats.rounds;
+      if (members_.on) {
+        stats.max_in_flight = std::max<uint64_t>(stats.max_in_flight, active.size());
+      }
       for (size_t first = 0; first < active.size();) {
-        // one launch: the files from `first` on that fit its limits (all of them, but for very many or very large windows):
+        // one launch: the streams from `first` on that fit its limits (all of them, but for very many or very large windows):
         // 4 GiB of histories at 32 KiB a step are 2^17 steps, the compressed bytes and the rooms as the engine bounds them
         size_t n = 0;
         uint64_t n_comp = 0, rooms = 0;
         for (; first + n < active.size() && n < (size_t(1) << 17); ++n) {
-          const File& f = *active[first + n];
-          if (n != 0 && (n_comp + f.window > (uint64_t(1) << 31) || rooms + f.room > (uint64_t(1) << 33))) {
+          const Stream& s = *active[first + n];
+          if (n != 0 && (n_comp + s.window > (uint64_t(1) << 31) || rooms + s.room > (uint64_t(1) << 33))) {
             break;
           }
-          n_comp += (f.window + 7) & ~uint64_t(7);
-          rooms += f.room;
+          n_comp += (s.window + 7) & ~uint64_t(7);
+          rooms += s.room;
         }
         if (n_comp + 8 > buf_.size()) {
           if (pinned && unpin) {
@@ -201,24 +246,28 @@ public:
         hist_out.resize(n * 32768);
         uint64_t slot = 0;
         for (size_t k = 0; k < n; ++k) {
-          File& f = *active[first + k];
-          const uint64_t byte0 = f.bit >> 3, phase = f.bit & 7;
-          const uint64_t want = byte0 < f.size ? std::min(f.window, f.size - byte0) : 0;
+          Stream& s = *active[first + k];
+          const File& f = *s.file;
+          const uint64_t byte0 = s.bit >> 3, phase = s.bit & 7;
+          const uint64_t want = byte0 < f.size ? std::min(s.window, f.size - byte0) : 0;
           int err = 0;
           const uint64_t got = want ? read_at(f.path, buf_.data() + slot, (size_t)want, byte0, &err) : 0;
-          f.at_eof = err == 0 && byte0 + got >= f.size; // (a read that failed: the step runs out of bytes in front of the end)
-          f.read_failed = err != 0;
+          s.at_eof = err == 0 && byte0 + got >= f.size; // (a read that failed: the step runs out of bytes in front of the end)
+          s.read_failed = err != 0;
           const uint64_t n_bits = got * 8 > phase ? got * 8 - phase : 0;
-          memcpy(dict.data() + k * 32768, f.hist.data(), f.hist_len);
-          const uint64_t target = std::max<uint64_t>(1, std::min(span_ - f.seg_text, std::min(sizes_.room / 2, f.room)));
-          steps[k] = grp_gzip_walk_step{ slot * 8 + (n_bits ? phase : 0), n_bits, (uint64_t)k * 32768, f.hist_len, (uint32_t)target, (uint32_t)f.room, 0 };
-          slot += (f.window + 7) & ~uint64_t(7);
+          memcpy(dict.data() + k * 32768, s.hist.data(), s.hist_len);
+          const uint64_t target = std::max<uint64_t>(1, std::min(span_ - s.seg_text, std::min(sizes_.room / 2, s.room)));
+          steps[k] = grp_gzip_walk_step{ slot * 8 + (n_bits ? phase : 0), n_bits, (uint64_t)k * 32768, s.hist_len, (uint32_t)target, (uint32_t)s.room, 0 };
+          slot += (s.window + 7) & ~uint64_t(7);
         }
         ++stats.launches;
         if (!launch(buf_.data(), slot, dict.data(), dict.size(), steps.data(), (uint32_t)n, res.data(), hist_out.data())) {
-          for (File* f : active) {
-            f->left = "a launch of the walk failed";
+          for (File& f : files_) {
+            if (live(f)) {
+              f.left = "a launch of the walk failed";
+            }
           }
+          failed = true;
           break;
         }
         for (size_t k = 0; k < n; ++k) {
@@ -226,7 +275,12 @@ public:
         }
         first += n;
       }
-      active.erase(std::remove_if(active.begin(), active.end(), [](const File* f) { return f->left || f->done; }), active.end());
+      // behind the answers of ALL the round's steps: a stream that ended in this round is there for the chain that arrives at it
+      for (File& f : files_) {
+        if (f.head) {
+          settle(f, stats);
+        }
+      }
     }
     if (pinned && unpin) {
       unpin(buf_.data(), buf_.size());
@@ -250,15 +304,27 @@ public:
   }
 
 private:
-  struct File
+  struct File;
+
+  // a finished segment of a stream ahead of its file's chain, with the history at its point
+  struct Kept
   {
-    std::string path;
-    uint64_t size = 0;
-    std::unique_ptr<GzIndex> ix;
-    const char* left = nullptr; // why the file is left to zlib
+    GzSegment g;
+    std::vector<uint8_t> dict;
+  };
+
+  // One walk through members from a header on.  A file's chain head (ahead false) writes its segments into the file's
+  // index and goes from member to member; a stream begun at a candidate (ahead true) keeps them, walks one member and
+  // stops behind its trailer, until the chain arrives at its first byte and adopts it — or passes it, and it is dropped
+  struct Stream
+  {
+    File* file = nullptr;
+    bool ahead = false;
+    uint64_t start = 0;         // the byte the member's header stands at
+    const char* left = nullptr; // why the walk through this member stopped (the file's reason, once the chain is here)
     uint32_t status = 0;
-    bool unreadable = false;    // ... because it is no regular file that can be looked at
-    bool done = false;          // the last member's trailer ended the file
+    bool ended = false;         // the member's trailer matched ...
+    uint64_t end = 0;           // ... and this is the byte behind it
     uint64_t bit = 0;           // the block boundary the next step starts at, in the file
     uint64_t room = 0, window = 0;
     bool at_eof = false, read_failed = false; // of the window of the step under way
@@ -272,11 +338,215 @@ private:
     uint32_t seg_crc = 0;
     std::vector<uint8_t> seg_dict, hist;
     uint32_t hist_len = 0;
+    // ahead: the segments so far, the text decoded, the bytes they will take in the index (roughly: a history takes 32 KiB or less)
+    std::vector<Kept> kept;
+    uint64_t text = 0, kept_bytes = 0;
+    bool stepping() const { return !left && !ended; }
   };
 
-  // the header of the member at byte `at`: the point behind it
-  void begin_member(File& f, uint64_t at)
+  struct File
   {
+    std::string path;
+    uint64_t size = 0;
+    std::unique_ptr<GzIndex> ix;
+    const char* left = nullptr; // why the file is left to zlib
+    uint32_t status = 0;
+    bool unreadable = false;    // ... because it is no regular file that can be looked at
+    bool done = false;          // the last member's trailer ended the file
+    std::unique_ptr<Stream> head; // the chain: it began at byte 0
+    // the members switch: the candidates (ascending), the first one not looked at yet, the streams ahead of the chain by
+    // their first byte; no_ahead: the index and the streams ahead together went over the cap, the chain goes on alone
+    std::vector<uint64_t> cand;
+    size_t next_cand = 0;
+    std::map<uint64_t, std::unique_ptr<Stream>> ahead;
+    bool no_ahead = false;
+  };
+
+  static bool live(const File& f) { return f.head && !f.left && !f.done; }
+
+  std::unique_ptr<Stream> new_stream(File& f, bool ahead) const
+  {
+    std::unique_ptr<Stream> s(new Stream);
+    s->file = &f;
+    s->ahead = ahead;
+    s->room = sizes_.room;
+    s->window = sizes_.window;
+    s->hist.resize(32768);
+    return s;
+  }
+
+  // The candidates of a file: the bytes behind byte 0 where 1f 8b 08 stands with no reserved flag bit, in one sequential
+  // read.  (What is a header is decided by gzip_header_bytes when a stream is begun there.)
+  void scan(File& f, GzWalkStats& stats)
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int fd = ::open(f.path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd < 0) {
+      return;
+    }
+    constexpr size_t chunk = size_t(4) << 20;
+    std::vector<uint8_t> b(chunk + 3); // a chunk and the three bytes behind it: a candidate may lie across two chunks
+    for (uint64_t off = 0; off < f.size; off += chunk) {
+      size_t got = 0;
+      while (got < b.size()) {
+        const ssize_t r = ::pread(fd, b.data() + got, b.size() - got, (off_t)(off + got));
+        if (r < 0 && errno == EINTR) {
+          continue;
+        }
+        if (r <= 0) {
+          break;
+        }
+        got += (size_t)r;
+      }
+      if (got < 4) {
+        break;
+      }
+      const size_t last = std::min(chunk, got - 3); // candidates at [0, last) of this chunk
+      for (size_t i = 0; i < last;) {
+        const void* m = memchr(b.data() + i, 0x1f, last - i);
+        if (!m) {
+          break;
+        }
+        i = (size_t)(static_cast<const uint8_t*>(m) - b.data());
+        if (b[i + 1] == 0x8b && b[i + 2] == 8 && !(b[i + 3] & 0xe0) && off + i != 0) {
+          f.cand.push_back(off + i);
+        }
+        ++i;
+      }
+      if (got < b.size()) {
+        break;
+      }
+    }
+    ::close(fd);
+    stats.candidates += f.cand.size();
+    stats.scan_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+
+  // Streams are begun at candidates while fewer than the budget take steps: in file order, then offset order.  A candidate
+  // the chain has passed is forgotten, one whose header does not parse too
+  void admit(GzWalkStats& stats)
+  {
+    uint64_t in_flight = 0;
+    for (const File& f : files_) {
+      if (live(f)) {
+        ++in_flight;
+        for (const auto& s : f.ahead) {
+          in_flight += s.second->stepping();
+        }
+      }
+    }
+    for (File& f : files_) {
+      if (!live(f) || f.no_ahead) {
+        continue;
+      }
+      const uint64_t pos = f.head->bit >> 3;
+      while (f.next_cand < f.cand.size()) {
+        const uint64_t q = f.cand[f.next_cand];
+        if (q >= pos && in_flight >= members_.streams) {
+          return;
+        }
+        ++f.next_cand;
+        if (q < pos) {
+          continue;
+        }
+        std::unique_ptr<Stream> s = new_stream(f, true);
+        begin_member(*s, q);
+        if (s->left) {
+          continue;
+        }
+        ++stats.streams;
+        ++in_flight;
+        f.ahead[q] = std::move(s);
+      }
+    }
+  }
+
+  void drop(File& f, std::map<uint64_t, std::unique_ptr<Stream>>::iterator last, GzWalkStats& stats)
+  {
+    for (auto it = f.ahead.begin(); it != last; ++it) {
+      ++stats.dropped;
+      stats.wasted_text += it->second->text;
+    }
+    f.ahead.erase(f.ahead.begin(), last);
+  }
+
+  // Behind a round: the chain.  The head's failure is the file's.  Where the head's member has ended, the chain arrives at the
+  // byte behind its trailer: the end of the file, bytes that are no member, a stream begun there (adopted: its segments
+  // enter the index in order; ended too, its end is the next arrival) or none (the head begins the member itself, as
+  // without the switch).  Then the streams the chain has passed are dropped
+  void settle(File& f, GzWalkStats& stats)
+  {
+    if (!f.left && !f.done && f.head->left) {
+      f.left = f.head->left;
+      f.status = f.head->status;
+    }
+    while (!f.left && !f.done && f.head->ended) {
+      const uint64_t p = f.head->end;
+      if (p == f.size) {
+        f.done = true;
+        break;
+      }
+      uint8_t t[2];
+      int err = 0;
+      if (read_at(f.path, t, (size_t)std::min<uint64_t>(2, f.size - p), p, &err) != 2 || t[0] != 0x1f || t[1] != 0x8b) {
+        f.left = "bytes behind the last member that are no member"; // (gzread ignores them; every pass over such a file stays with zlib)
+        break;
+      }
+      const auto it = f.ahead.find(p);
+      if (it == f.ahead.end()) {
+        f.head->ended = false;
+        begin_member(*f.head, p);
+      } else {
+        std::unique_ptr<Stream> s = std::move(it->second);
+        f.ahead.erase(it);
+        ++stats.adopted;
+        stats.text_bytes += s->text;
+        // in the order the serial walk meets them: the segments (the cap), then what stopped the stream
+        const char* const noted = s->left;
+        s->left = nullptr;
+        s->ahead = false;
+        for (const Kept& k : s->kept) {
+          append(*s, k.g, k.dict.data());
+          if (s->left) {
+            break;
+          }
+        }
+        s->kept.clear();
+        s->kept.shrink_to_fit();
+        if (!s->left) {
+          s->left = noted;
+        } else {
+          s->status = 0;
+        }
+        f.head = std::move(s);
+      }
+      if (f.head->left) {
+        f.left = f.head->left;
+        f.status = f.head->status;
+      }
+    }
+    if (f.ahead.empty()) {
+      return;
+    }
+    if (f.left || f.done) {
+      drop(f, f.ahead.end(), stats);
+      return;
+    }
+    drop(f, f.ahead.lower_bound(f.head->bit >> 3), stats); // (behind the last consumed bit a member may begin, in front of it none)
+    uint64_t bytes = f.ix->bytes();
+    for (const auto& s : f.ahead) {
+      bytes += s.second->kept_bytes;
+    }
+    if (bytes > max_bytes_) { // the cap holds for the index and the streams ahead together: the chain goes on alone
+      drop(f, f.ahead.end(), stats);
+      f.no_ahead = true;
+    }
+  }
+
+  // the header of the member at byte `at`: the point behind it
+  void begin_member(Stream& s, uint64_t at)
+  {
+    const File& f = *s.file;
     std::vector<uint8_t> head;
     long h = 0;
     for (size_t n = size_t(1) << 12; h == 0; n *= 16) {
@@ -289,143 +559,155 @@ private:
       }
     }
     if (h < 0) {
-      f.left = "a member's header is not one zlib takes";
+      s.left = "a member's header is not one zlib takes";
       return;
     }
-    f.bit = (at + (uint64_t)h) * 8;
-    f.member_text = 0;
-    f.member_crc = 0;
-    f.member_segs = 0;
-    f.hist_len = 0;
-    point(f);
+    s.start = at;
+    s.bit = (at + (uint64_t)h) * 8;
+    s.member_text = 0;
+    s.member_crc = 0;
+    s.member_segs = 0;
+    s.hist_len = 0;
+    point(s);
   }
 
-  // a restart point at f.bit, with the history there
-  void point(File& f)
+  // a restart point at s.bit, with the history there
+  void point(Stream& s)
   {
-    f.cur = GzSegment{ f.bit, 0, 0, f.hist_len, 0, 0, 0 };
-    f.seg_dict.assign(f.hist.begin(), f.hist.begin() + f.hist_len);
-    f.seg_text = 0;
-    f.seg_crc = 0;
+    s.cur = GzSegment{ s.bit, 0, 0, s.hist_len, 0, 0, 0 };
+    s.seg_dict.assign(s.hist.begin(), s.hist.begin() + s.hist_len);
+    s.seg_text = 0;
+    s.seg_crc = 0;
   }
 
-  // the open segment ends at f.bit (GzIndexReader::commit)
-  void commit(File& f, uint32_t flags)
+  // a finished segment enters the file's index (GzIndexReader::commit)
+  void append(Stream& s, GzSegment g, const uint8_t* dict)
   {
-    GzIndex& ix = *f.ix;
-    if (f.seg_text == 0 || f.seg_text > 0xffff0000ull) { // (never empty; the engine takes 32-bit lengths)
-      f.left = "a segment of more than 4 GiB - 64 KiB of text";
-      return;
+    GzIndex& ix = *s.file->ix;
+    if (g.dict_len) {
+      uint8_t* d = ix.reserve(32768, &g.dict_at);
+      memcpy(d, dict, g.dict_len);
+      ix.used_ += g.dict_len;
     }
-    f.cur.n_bits = f.bit - f.cur.comp_bit;
-    f.cur.text_len = (uint32_t)f.seg_text;
-    f.cur.crc32 = f.seg_crc;
-    f.cur.flags = flags;
-    if (f.cur.dict_len) {
-      uint8_t* d = ix.reserve(32768, &f.cur.dict_at);
-      memcpy(d, f.seg_dict.data(), f.cur.dict_len);
-      ix.used_ += f.cur.dict_len;
-    }
-    ix.segs.push_back(f.cur);
-    ix.text_bytes += f.seg_text;
-    ix.max_text = std::max(ix.max_text, f.seg_text);
-    ix.max_comp = std::max(ix.max_comp, f.cur.end_byte() - f.cur.first_byte());
-    ++f.member_segs;
+    ix.segs.push_back(g);
+    ix.text_bytes += g.text_len;
+    ix.max_text = std::max<uint64_t>(ix.max_text, g.text_len);
+    ix.max_comp = std::max(ix.max_comp, g.end_byte() - g.first_byte());
     if (ix.bytes() > max_bytes_) {
-      f.left = "the index grew beyond its cap";
+      s.left = "the index grew beyond its cap";
     }
   }
 
-  // behind the final block at f.bit: the trailer, then another member, the end of the file, or bytes that are no member
-  void end_member(File& f)
+  // the open segment ends at s.bit
+  void commit(Stream& s, uint32_t flags)
   {
-    const uint64_t at = (f.bit + 7) >> 3;
-    uint8_t t[10];
+    if (s.seg_text == 0 || s.seg_text > 0xffff0000ull) { // (never empty; the engine takes 32-bit lengths)
+      s.left = "a segment of more than 4 GiB - 64 KiB of text";
+      return;
+    }
+    s.cur.n_bits = s.bit - s.cur.comp_bit;
+    s.cur.text_len = (uint32_t)s.seg_text;
+    s.cur.crc32 = s.seg_crc;
+    s.cur.flags = flags;
+    if (s.ahead) {
+      s.kept.push_back(Kept{ s.cur, std::vector<uint8_t>(s.seg_dict.begin(), s.seg_dict.begin() + s.cur.dict_len) });
+      s.kept_bytes += sizeof(GzSegment) + s.cur.dict_len;
+    } else {
+      append(s, s.cur, s.seg_dict.data());
+    }
+    ++s.member_segs;
+  }
+
+  // behind the final block at s.bit: the trailer.  What stands behind it is the chain's to look at (settle)
+  void end_member(Stream& s)
+  {
+    const File& f = *s.file;
+    const uint64_t at = (s.bit + 7) >> 3;
+    uint8_t t[8];
     int err = 0;
-    const size_t got = at + 8 <= f.size ? read_at(f.path, t, (size_t)std::min<uint64_t>(10, f.size - at), at, &err) : 0;
+    const size_t got = at + 8 <= f.size ? read_at(f.path, t, 8, at, &err) : 0;
     if (got < 8 || err) {
-      f.left = "the file ends inside a member's trailer";
+      s.left = "the file ends inside a member's trailer";
       return;
     }
     const uint32_t crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
     const uint32_t isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
-    if (crc != f.member_crc || isize != (uint32_t)f.member_text) {
-      f.left = "a member's trailer does not match its text";
+    if (crc != s.member_crc || isize != (uint32_t)s.member_text) {
+      s.left = "a member's trailer does not match its text";
       return;
     }
-    if (at + 8 == f.size) {
-      f.done = true;
-    } else if (got == 10 && t[8] == 0x1f && t[9] == 0x8b) {
-      begin_member(f, at + 8);
-    } else {
-      f.left = "bytes behind the last member that are no member"; // (gzread ignores them; every pass over such a file stays with zlib)
-    }
+    s.ended = true;
+    s.end = at + 8;
   }
 
-  void answer(File& f, const grp_gzip_walk_result& r, const uint8_t* hist, GzWalkStats& stats)
+  void answer(Stream& s, const grp_gzip_walk_result& r, const uint8_t* hist, GzWalkStats& stats)
   {
-    if (r.status == GRP_GZIP_WALK_NO_ROOM || (r.status == GRP_GZIP_WALK_INPUT_ENDS && !f.at_eof && !f.read_failed)) {
+    if (r.status == GRP_GZIP_WALK_NO_ROOM || (r.status == GRP_GZIP_WALK_INPUT_ENDS && !s.at_eof && !s.read_failed)) {
       // the step is repeated with both doubled
-      if ((r.status == GRP_GZIP_WALK_NO_ROOM ? f.room : f.window) >= sizes_.cap) {
-        f.left = "a block needs more room or more compressed bytes than the cap";
-        f.status = r.status;
+      if ((r.status == GRP_GZIP_WALK_NO_ROOM ? s.room : s.window) >= sizes_.cap) {
+        s.left = "a block needs more room or more compressed bytes than the cap";
+        s.status = r.status;
         return;
       }
-      f.room = std::min(2 * f.room, sizes_.cap);
-      f.window = std::min(2 * f.window, sizes_.cap);
+      s.room = std::min(2 * s.room, sizes_.cap);
+      s.window = std::min(2 * s.window, sizes_.cap);
       ++stats.repeats;
       return;
     }
     if (r.status != 0) {
-      f.left = f.read_failed ? "the file could not be read" : r.status == GRP_GZIP_WALK_INPUT_ENDS ? "the stream ends inside a block at the end of the file" : "the decoder refused the stream";
-      f.status = r.status;
+      s.left = s.read_failed ? "the file could not be read" : r.status == GRP_GZIP_WALK_INPUT_ENDS ? "the stream ends inside a block at the end of the file" : "the decoder refused the stream";
+      s.status = r.status;
       return;
     }
     if (r.bits == 0 || r.hist_len > 32768 || (!r.final && r.text_len == 0)) {
-      f.left = "a step that made no progress"; // (not what the engine is known to do)
+      s.left = "a step that made no progress"; // (not what the engine is known to do)
       return;
     }
-    f.bit += r.bits;
-    f.seg_text += r.text_len;
-    f.member_text += r.text_len;
-    f.seg_crc = (uint32_t)crc32_combine(f.seg_crc, r.crc32, (z_off_t)r.text_len);
-    f.member_crc = (uint32_t)crc32_combine(f.member_crc, r.crc32, (z_off_t)r.text_len);
-    memcpy(f.hist.data(), hist, r.hist_len);
-    f.hist_len = r.hist_len;
-    stats.text_bytes += r.text_len;
+    s.bit += r.bits;
+    s.seg_text += r.text_len;
+    s.member_text += r.text_len;
+    s.seg_crc = (uint32_t)crc32_combine(s.seg_crc, r.crc32, (z_off_t)r.text_len);
+    s.member_crc = (uint32_t)crc32_combine(s.member_crc, r.crc32, (z_off_t)r.text_len);
+    memcpy(s.hist.data(), hist, r.hist_len);
+    s.hist_len = r.hist_len;
+    (s.ahead ? s.text : stats.text_bytes) += r.text_len; // (a stream's text is counted where the chain takes or passes it)
     if (r.final) { // the member's end closes the segment
-      if (f.seg_text != 0) {
-        commit(f, GRP_GZIP_SEG_FINAL);
-      } else if (f.member_segs != 0) {
+      if (s.seg_text != 0) {
+        commit(s, GRP_GZIP_SEG_FINAL);
+      } else if (s.member_segs != 0) {
         // blocks without text behind the last point: they belong to the segment in front of it, the point is forgotten
-        GzSegment& g = f.ix->segs.back();
-        g.n_bits = f.bit - g.comp_bit;
+        GzSegment& g = s.ahead ? s.kept.back().g : s.file->ix->segs.back();
+        g.n_bits = s.bit - g.comp_bit;
         g.flags = GRP_GZIP_SEG_FINAL;
-        f.ix->max_comp = std::max(f.ix->max_comp, g.end_byte() - g.first_byte());
+        if (!s.ahead) {
+          s.file->ix->max_comp = std::max(s.file->ix->max_comp, g.end_byte() - g.first_byte());
+        }
       } // (else: a member without text has no segment)
-      if (!f.left) {
-        end_member(f);
+      if (!s.left) {
+        end_member(s);
       }
-    } else if (f.seg_text >= span_) {
-      commit(f, 0);
-      if (!f.left) {
-        point(f);
+    } else if (s.seg_text >= span_) {
+      commit(s, 0);
+      if (!s.left) {
+        point(s);
       }
     }
   }
 
   const uint64_t span_, max_bytes_;
   const GzWalkSizes sizes_;
+  const GzWalkMembers members_;
   std::vector<File> files_;
   std::vector<uint8_t> buf_;
 };
 
 std::vector<GzWalkFile>
-gzip_walk(const std::vector<std::string>& paths, uint64_t span, uint64_t max_bytes, const GzWalkSizes& sizes, const GzWalkLaunch& launch, GzWalkStats* stats, const GzWalkBuffer& pin, const GzWalkBuffer& unpin)
+gzip_walk(const std::vector<std::string>& paths, uint64_t span, uint64_t max_bytes, const GzWalkSizes& sizes, const GzWalkLaunch& launch, GzWalkStats* stats, const GzWalkBuffer& pin, const GzWalkBuffer& unpin,
+          const GzWalkMembers& members)
 {
   const auto t0 = std::chrono::steady_clock::now();
   GzWalkStats st;
-  GzWalker w(paths, span, max_bytes, sizes);
+  GzWalker w(paths, span, max_bytes, sizes, members, st);
   w.run(launch, st, pin, unpin);
   std::vector<GzWalkFile> out = w.take();
   st.files = paths.size();

@@ -9,7 +9,22 @@
 //   text since the last point; none behind a final block: the member's end closes the segment (flag 1); a round without
 //   text that ends a member goes to the segment in front of it; a member without text has no segment.
 // The text is decoded to find the boundaries and thrown away: a pass that then reads the file inflates it a second time,
-// through its segments.  The parallelism is the number of files: a single file gains nothing over zlib.
+// through its segments.  The parallelism is the number of files: a single-member file gains nothing over zlib.
+//
+// The members of one file (GzWalkMembers, GRP_GZIP_WALK_MEMBERS=on): `cat a.gz b.gz ... > reads.gz` is one file of many
+// members, and a member depends on nothing in front of it: it starts on a byte, behind a header, with no history, and the
+// index rule starts anew there.  With the switch on, every byte behind byte 0 where `1f 8b 08` stands with no reserved flag
+// bit is a candidate (one sequential read of the file), and a stream is begun at a candidate whose header parses: it walks
+// ONE member, in the same rounds and launches as every other step, keeps its segments to itself, checks the trailer, notes
+// where the member ended and stops.  Per file the serial logic stays the authority (the chain): it starts at byte 0, and
+// when it arrives behind a trailer at byte p it adopts the stream that was begun at p, if there is one — its segments go
+// into the file's index in order, its end is the next arrival, an unfinished one goes on as the chain's head, a failure
+// it noted is the file's.  Nothing guessed enters the index: a stream's segments are taken only if the chain of members
+// from byte 0 arrives at exactly its first byte, and then the serial walk would have begun there too, with the same empty
+// state and the same decoder — the same index by construction, not by a checksum.  A stream the chain never arrives at (a
+// `1f 8b 08` inside a header field, inside stored text, in a trailer) is dropped, the moment the chain has passed its
+// first byte: guessing costs work, never correctness.  Where the chain arrives at a byte without a stream it does what it
+// does without the switch, so every file that is left to zlib is left for the same reason in the same words.
 //
 // A file is left to zlib (it gets no index, its reader does and says what it does without the walk) when its bytes behind
 // the last member are no member, a header is not what zlib takes, a trailer does not match, the stream ends inside a
@@ -17,7 +32,7 @@
 // more compressed bytes than the cap: a step that runs out of either is repeated with both doubled up to there.
 //
 // The steps go through a callback, so that the same rounds run over the engine (gr_source.cpp, gr_capi.cpp) and over the
-// decoder compiled for the host (tools/dev/inflate_host_check.cpp --walk).
+// decoder compiled for the host (tools/dev/inflate_host_check.cpp --walk, --members).
 #pragma once
 #include "gr_gzidx.hpp"
 
@@ -44,10 +59,30 @@ using GzWalkLaunch = std::function<bool(const uint8_t* comp, uint64_t n_comp, co
 // the window buffer is about to be read by launches / about to go away (page-locking); either may be empty
 using GzWalkBuffer = std::function<void(uint8_t* buf, size_t n)>;
 
+// GRP_GZIP_WALK_MEMBERS: 1 on, 0 off or unset, -1 any other value.  It has no effect without GRP_GZIP_WALK=on
+int gzip_walk_members_switch();
+
+// The members of a file side by side (above).  `streams`, GRP_GZIP_WALK_STREAMS: the most streams that take steps at the
+// same time, over all files.  Every file's chain head is one of them whatever the number (they are the walk without the
+// switch), streams ahead of a chain are begun only while there are fewer: in file order, then offset order.  1024 is a
+// bound on memory, not a measured optimum: a stream holds a window (512 KiB) and two histories (32 KiB each) on the host,
+// about 0.6 GB for 1024, and its room (1 MiB) on the device.
+struct GzWalkMembers
+{
+  bool on = false;
+  uint64_t streams = 1024;
+};
+GzWalkMembers gzip_walk_members(); // from the two variables (a bad value of the switch reads as off here: the caller has refused it)
+
 struct GzWalkStats
 {
   uint64_t files = 0, walked = 0, left_to_zlib = 0, rounds = 0, text_bytes = 0, launches = 0, repeats = 0;
   double seconds = 0.0;
+  // GzWalkMembers::on: candidates found, streams begun ahead of a chain, of them adopted by one and dropped, the most streams
+  // that took a step in one round (heads included), the text dropped streams had decoded.  text_bytes is text that
+  // entered an index or was decoded by a chain's head
+  uint64_t candidates = 0, streams = 0, adopted = 0, dropped = 0, max_in_flight = 0, wasted_text = 0;
+  double scan_seconds = 0.0;
 };
 
 // why a file was left to zlib (tests); nullptr for a file that was walked
@@ -60,7 +95,7 @@ struct GzWalkFile
 };
 
 std::vector<GzWalkFile> gzip_walk(const std::vector<std::string>& paths, uint64_t span, uint64_t max_bytes, const GzWalkSizes& sizes, const GzWalkLaunch& launch, GzWalkStats* stats = nullptr, const GzWalkBuffer& pin = nullptr,
-                                  const GzWalkBuffer& unpin = nullptr);
+                                  const GzWalkBuffer& unpin = nullptr, const GzWalkMembers& members = GzWalkMembers());
 
 // The gzip header at buf[0, n): its length; 0: more bytes are needed (n < the header's end); -1: not a header zlib takes.
 long gzip_header_bytes(const uint8_t* buf, size_t n);

@@ -157,6 +157,13 @@ read_options(PathRun& run, int argc, char** argv, Quiet& quiet)
     return 1;
   }
   run.gzip_walk = walk == 1;
+  // GRP_GZIP_WALK_MEMBERS=on, beside it: the members of one file side by side too (cat *.fastq.gz > reads.fq.gz).  Off by
+  // default, and without effect where the walk is off
+  if (gzip_walk_members_switch() < 0) {
+    std::cerr << "goldrush-path: GRP_GZIP_WALK_MEMBERS=" << getenv("GRP_GZIP_WALK_MEMBERS") << ": the switch takes on or off" << std::endl;
+    return 1;
+  }
+  run.gzip_walk_members = gzip_walk_members();
   return -1;
 }
 

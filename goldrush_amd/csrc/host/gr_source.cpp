@@ -612,6 +612,7 @@ plan_feed(PathRun& run, size_t file, size_t chunk)
 // plan_feed would read as text through GzIndexReader — gzip, not routed to the BGZF form, without an index, on an engine
 // that inflates segments — is walked on the device, all of them side by side (gr_gzwalk.hpp).  A file the walk completes
 // has its index in PathRun::gzidx and plan_feed chooses GzipSegFeed by itself; every other file is read as without the walk.
+// With GRP_GZIP_WALK_MEMBERS=on the members of a file are walked side by side too (GzWalkMembers): the indexes are the same.
 void
 walk_gzip_files(PathRun& run)
 {
@@ -657,7 +658,7 @@ walk_gzip_files(PathRun& run)
       pin = [&run](uint8_t* buf, size_t n) { (void)run.vt.fastq_pin(run.ctx, reinterpret_cast<const char*>(buf), n); };
       unpin = [&run](uint8_t*, size_t) { (void)run.vt.fastq_unpin(run.ctx); };
     }
-    std::vector<GzWalkFile> got = gzip_walk(paths, gzip_index_span(), gzip_index_max_bytes(), gzip_walk_sizes(), launch, &st, pin, unpin);
+    std::vector<GzWalkFile> got = gzip_walk(paths, gzip_index_span(), gzip_index_max_bytes(), gzip_walk_sizes(), launch, &st, pin, unpin, run.gzip_walk_members);
     for (size_t i = 0; i < got.size(); ++i) {
       if (got[i].index) {
         run.gzidx[which[i]] = std::move(got[i].index);
@@ -666,6 +667,10 @@ walk_gzip_files(PathRun& run)
   }
   if (getenv("GRP_TRACE_INGEST") && run.rank == 0) {
     std::cerr << "GRP_TRACE_INGEST gzip walk: files=" << st.files << " walked=" << st.walked << " left_to_zlib=" << st.left_to_zlib << " rounds=" << st.rounds << " text=" << st.text_bytes << " seconds=" << st.seconds << std::endl;
+    if (run.gzip_walk_members.on) {
+      std::cerr << "GRP_TRACE_INGEST gzip walk members: candidates=" << st.candidates << " streams=" << st.streams << " adopted=" << st.adopted << " dropped=" << st.dropped << " max_in_flight=" << st.max_in_flight
+                << " wasted_text=" << st.wasted_text << " scan_seconds=" << st.scan_seconds << std::endl;
+    }
   }
 }
 

@@ -10,6 +10,7 @@
 #include "../../../include/grpath_host.h"
 #include "gr_bam.hpp"
 #include "gr_gzidx.hpp"
+#include "gr_gzwalk.hpp"
 #include "gr_opts.hpp"
 #include "gr_units.hpp"
 
@@ -52,6 +53,9 @@ struct PathRun
   // GRP_GZIP_WALK=on (read_options): in front of the first source of the run, the indexes of all its plain gzip files are
   // built on the device, the files side by side (gr_gzwalk.hpp), so that the first pass reads them through segments too
   bool gzip_walk = false, gzip_walked = false; // the switch; the walk has had its turn
+  // GRP_GZIP_WALK_MEMBERS=on, GRP_GZIP_WALK_STREAMS (read_options): the walk also begins streams at the members behind a
+  // file's first, so that a file of many members (cat *.fastq.gz) is walked side by side like many files
+  GzWalkMembers gzip_walk_members;
   // a BGZF input: the members the last pass over that file walked, if it walked them to the file's end (BgzfFeed); a file
   // whose last pass did not go through the member feed, or left it for zlib at a member that is not BGZF, has none
   std::vector<std::shared_ptr<BgzfMap>> bgzf_map;

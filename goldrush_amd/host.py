@@ -192,10 +192,12 @@ SIGNATURES = {
     "gr_gzidx_matches": (C.c_int, [_vp, C.c_char_p]),
     "gr_gzidx_free": (None, [_vp]),
     "gr_gzidx_build_device_many": (C.c_int, [C.POINTER(grp_engine_ext), _vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(_vp), _vp]),
+    "gr_gzidx_build_device_many_ex": (C.c_int, [C.POINTER(grp_engine_ext), _vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(_vp), _vp]),
     "gr_gzidx_build_device": (_vp, [C.POINTER(grp_engine_ext), _vp, C.c_char_p, C.c_uint64, C.c_uint64]),
     "gr_gzidx_left": (C.c_char_p, [_vp, C.POINTER(C.c_uint32)]),
     "gr_gzip_header_bytes": (C.c_long, [C.c_char_p, C.c_size_t]),
     "gr_gzip_walk_switch": (C.c_int, []),
+    "gr_gzip_walk_members_switch": (C.c_int, []),
 }
 
 _lib = None
@@ -415,17 +417,25 @@ def _gzidx_dict(lib, h, path) -> dict:
                 left=left.decode() if left else None, status=status.value)
 
 
-def gzip_index_device(engine, paths, span: int = 256 << 10, max_bytes: int = 16 << 30):
+def gzip_index_device(engine, paths, span: int = 256 << 10, max_bytes: int = 16 << 30, members: bool = False, ext=None):
     """gr_gzidx_build_device_many: the index of every file of `paths` built by the engine's walk (grp_gzip_walk of `engine`, a
     native.Engine), all files side by side.  Returns ([gzip_index's dict per file, with `left` (why the file was left to
-    zlib, or None) and `status`; None for a file that cannot be read], the walk's statistics)."""
+    zlib, or None) and `status`; None for a file that cannot be read], the walk's statistics).
+    members=True: gr_gzidx_build_device_many_ex with its flag set — the members of a file side by side too, at most
+    GRP_GZIP_WALK_STREAMS streams at a time; the statistics then carry candidates, streams, adopted, dropped,
+    max_in_flight, wasted_text and scan_microseconds as well.  ext: another second table than the HIP engine's (tests)."""
     lib = load()
-    ext = hip_engine_ext()
+    ext = hip_engine_ext() if ext is None else ext
     arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(str(p)) for p in paths])
     hs = (_vp * max(len(paths), 1))()
-    stats = np.zeros(8, dtype=np.uint64)
-    if lib.gr_gzidx_build_device_many(C.byref(ext), engine._h, arr, len(paths), span, max_bytes, hs, _p(stats)) != 0:
-        raise RuntimeError("gr_gzidx_build_device_many failed")
+    stats = np.zeros(16 if members else 8, dtype=np.uint64)
+    handle = engine._h if engine is not None else None
+    if members:
+        rc = lib.gr_gzidx_build_device_many_ex(C.byref(ext), handle, arr, len(paths), span, max_bytes, 1, hs, _p(stats))
+    else:
+        rc = lib.gr_gzidx_build_device_many(C.byref(ext), handle, arr, len(paths), span, max_bytes, hs, _p(stats))
+    if rc != 0:
+        raise RuntimeError("gr_gzidx_build_device_many%s failed" % ("_ex" if members else ""))
     out = []
     try:
         for h, path in zip(hs, paths):
@@ -434,7 +444,8 @@ def gzip_index_device(engine, paths, span: int = 256 << 10, max_bytes: int = 16 
         for h in hs[:len(paths)]:
             if h:
                 lib.gr_gzidx_free(h)
-    names = ("files", "walked", "left_to_zlib", "rounds", "text_bytes", "launches", "repeats", "microseconds")
+    names = ("files", "walked", "left_to_zlib", "rounds", "text_bytes", "launches", "repeats", "microseconds",
+             "candidates", "streams", "adopted", "dropped", "max_in_flight", "wasted_text", "scan_microseconds")
     return out, {k: int(v) for k, v in zip(names, stats)}
 
 

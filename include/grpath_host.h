@@ -378,6 +378,13 @@ typedef struct
  * _left: why the file was left to zlib (NULL: it was not), *status = the decoder's status where that was the reason. */
 int gr_gzidx_build_device_many(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, gr_gzidx** out, uint64_t stats[8]);
 gr_gzidx* gr_gzidx_build_device(const grp_engine_ext* ext, void* engine_ctx, const char* path, uint64_t span, uint64_t max_bytes);
+/* _many with the members of a file side by side (csrc/host/gr_gzwalk.hpp: GzWalkMembers; what GRP_GZIP_WALK_MEMBERS=on does in
+ * the host program): members != 0 begins a stream at every gzip header found behind byte 0 of a file, ahead of the chain of
+ * members from byte 0, which adopts the streams it arrives at and drops the others; at most GRP_GZIP_WALK_STREAMS (1024)
+ * streams take steps at a time.  The indexes are those of _many, word for word.  members == 0 is _many.  stats: the eight
+ * of _many, then candidates, streams begun, adopted, dropped, the most streams that took a step in one round, the bytes of
+ * text dropped streams had decoded, the microseconds of the scan for candidates, 0.  _many itself reads neither variable. */
+int gr_gzidx_build_device_many_ex(const grp_engine_ext* ext, void* engine_ctx, const char* const* paths, uint32_t n, uint64_t span, uint64_t max_bytes, int members, gr_gzidx** out, uint64_t stats[16]);
 const char* gr_gzidx_left(const gr_gzidx* h, uint32_t* status);
 /* The two pieces of the walk that need no engine.  _header_bytes: the gzip header at buf[0, n) as the walk parses it (FEXTRA,
  * FNAME, FCOMMENT, FHCRC with its CRC16): its length; 0: it does not end inside the n bytes; -1: not a header zlib takes
@@ -385,6 +392,7 @@ const char* gr_gzidx_left(const gr_gzidx* h, uint32_t* status);
  * program reads it: 1 on, 0 off or unset, -1 any other value (the run ends with status 1 before its first pass). */
 long gr_gzip_header_bytes(const unsigned char* buf, size_t n);
 int gr_gzip_walk_switch(void);
+int gr_gzip_walk_members_switch(void); /* GRP_GZIP_WALK_MEMBERS, read the same way; without GRP_GZIP_WALK=on it has no effect */
 
 /* ---- the CLI as a function (main of goldrush_path.cpp:1096-1275) ----------- */
 int gr_path_main(int argc, char** argv, const grp_engine_vt* vt); /* = gr_path_main_ext(argc, argv, vt, NULL) */

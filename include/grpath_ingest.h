@@ -155,8 +155,13 @@ int grp_debug_gzip_stats(const grp_ctx* ctx, uint64_t out[4]);
  * side by side, one wave per step (csrc/grp_inflate.inc: the open form of the decoder): from a bit where a block begins,
  * with the history in front of it, whole blocks until at least min_text bytes of text have come out or a final block has
  * ended.  The host (csrc/host/gr_gzwalk.hpp) parses the headers and trailers, strings the steps of a file together and
- * writes down the index GzIndexReader would have written.  Nothing is guessed: a step starts behind a header the host
- * parsed or at a boundary the step in front of it reached.  The text is decoded to find the boundaries and thrown away.
+ * writes down the index GzIndexReader would have written.  Nothing guessed enters the index: a step starts behind a header
+ * the host parsed or at a boundary the step in front of it reached, and what the steps of a stream produced is taken only
+ * if the chain of members from byte 0 of the file arrives at exactly that header — where the serial walk would have begun
+ * too, with the same empty state and the same decoder.  With GRP_GZIP_WALK_MEMBERS=on the host also begins streams at gzip
+ * headers it finds behind a file's first member, ahead of that chain; one the chain never arrives at is thrown away, so a
+ * step may start at bits that begin no DEFLATE stream: it ends with a status and touches nothing outside its buffers.
+ * The text is decoded to find the boundaries and thrown away.
  */
 struct grp_gzip_walk_step
 {

@@ -25,6 +25,10 @@
 // byte short), and damaged copies of the file (flipped bits, cut short, bytes appended): each must be left to zlib or
 // indexed as the reader indexes it.
 //   /tmp/inflate_host_check --walk /tmp/gzip_cases/*.gz
+// The members of a file side by side (GRP_GZIP_WALK_MEMBERS: gr_gzwalk.hpp), on the files tests/gzip_member_cases.py writes: all of
+// them in one walk with the switch and without it, against the reader's index; then 10 000 open steps from pseudo-random
+// bits of the first file, every buffer in a heap block of exactly its size:
+//   python tests/gzip_member_cases.py /tmp/gzip_members && /tmp/inflate_host_check --members /tmp/gzip_members/*.gz
 #define GRP_INFLATE_HOST
 #include <cstdint>
 #include <cstdio>
@@ -346,6 +350,94 @@ static int walk_main(int argc, char** argv)
   return bad != 0;
 }
 
+// ---- --members ---------------------------------------------------------------------------------------------------------
+// The open form from pseudo-random bits of a compressed buffer — what a stream begun at a false candidate gives the decoder.
+// The bytes lie in a heap block of exactly their number (a multiple of 4: the decoder loads the words its bits lie in), the
+// text goes to a block of exactly `room` bytes, the history comes from and goes to blocks of exactly their sizes: under
+// -fsanitize=address a load or store outside any of them ends the program.
+static int random_steps(const std::vector<uint8_t>& raw, uint64_t* counts)
+{
+  const size_t n = raw.size() & ~size_t(3);
+  if (n < 64) return 0;
+  uint8_t* comp = (uint8_t*)malloc(n);
+  memcpy(comp, raw.data(), n);
+  int bad = 0;
+  uint64_t r = 0x2545f4914f6cdd1dull;
+  for (int t = 0; t < 10000; ++t) {
+    r = r * 6364136223846793005ull + 1442695040888963407ull;
+    const uint64_t bit = (r >> 16) % (n * 8);
+    r = r * 6364136223846793005ull + 1442695040888963407ull;
+    const uint64_t left = n * 8 - bit;
+    const uint64_t n_bits = (t & 3) == 0 ? (r >> 16) % (left + 1) : left; // to the end of the buffer, or to any bit in front of it
+    const uint32_t room = (t & 7) < 3 ? 512u : 1u << 16, dict_len = (t & 1) ? 0u : (uint32_t)((r >> 40) % 32769);
+    const uint32_t min_text = (t & 16) ? room / 2 : 1;
+    uint8_t* dict = (uint8_t*)malloc(dict_len ? dict_len : 1);
+    memset(dict, 'A', dict_len ? dict_len : 1);
+    char* out = (char*)malloc(room);
+    uint8_t* hist = (uint8_t*)malloc(32768);
+    grp_gzip_walk_result res{};
+    const InfWalkEntry e{ grp_gzip_walk_step{ bit, n_bits, 0, dict_len, min_text, room, 0 }, &res, hist };
+    memset(&g_s, 0xAA, sizeof g_s);
+    const uint32_t st = inf_entry(g_s, comp, dict, e, out);
+    ++counts[st == 0 ? 0 : st == INF_INPUT_ENDS ? 1 : st == INF_NO_ROOM ? 2 : 3];
+    if (st != res.status || (st == 0 && (res.bits == 0 || res.bits > n_bits || res.text_len > room || res.hist_len > 32768 || res.hist_len != std::min<uint64_t>(32768, (uint64_t)dict_len + res.text_len)))) {
+      printf("random step %d (bit %llu, %llu bits): status %u, %llu bits, %u bytes, history %u\n", t, (unsigned long long)bit, (unsigned long long)n_bits, st, (unsigned long long)res.bits, res.text_len, res.hist_len);
+      ++bad;
+    }
+    free(hist); free(out); free(dict);
+  }
+  free(comp);
+  return bad;
+}
+
+// The members switch of the rounds (csrc/host/gr_gzwalk.hpp: GzWalkMembers) over the host-compiled decoder: all the files in ONE walk,
+// with the switch and without it, at spans 1, 50 000 and 10^9; the sizes of a step and the budget of streams come from
+// GRP_GZIP_WALK_ROOM and GRP_GZIP_WALK_STREAMS.  A file the serial walk indexes must get the reader's index from both; a file
+// it leaves to zlib must be left by both, for the same reason with the same status.  One line of statistics per span (tests/
+// test_gzip_members_cpu.py reads them), then the random steps over the first file's bytes.
+static int members_main(int argc, char** argv)
+{
+  int bad = 0;
+  gr::GzWalkMembers on = gr::gzip_walk_members();
+  on.on = true;
+  std::vector<std::string> paths(argv + 2, argv + argc);
+  for (uint64_t span : { uint64_t(1), uint64_t(50000), uint64_t(1000000000) }) {
+    gr::GzWalkStats s0, s1;
+    std::vector<gr::GzWalkFile> off = gr::gzip_walk(paths, span, uint64_t(1) << 32, gr::gzip_walk_sizes(), walk_launch, &s0);
+    std::vector<gr::GzWalkFile> got = gr::gzip_walk(paths, span, uint64_t(1) << 32, gr::gzip_walk_sizes(), walk_launch, &s1, nullptr, nullptr, on);
+    int span_bad = 0;
+    for (size_t i = 0; i < paths.size(); ++i) {
+      char what[600]; snprintf(what, sizeof what, "%s span %llu", paths[i].c_str(), (unsigned long long)span);
+      if (off[i].index) {
+        bool failed = false;
+        std::unique_ptr<gr::GzIndex> want = reader_index(paths[i].c_str(), span, &failed);
+        if (!want || failed || !same_index(*want, *off[i].index, what)) { printf("%s: the serial walk's index is not the reader's\n", what); ++span_bad; continue; }
+        if (!got[i].index) { printf("%s: with the members switch the file is left to zlib: %s (status %u)\n", what, got[i].left, got[i].status); ++span_bad; continue; }
+        if (!same_index(*want, *got[i].index, what)) ++span_bad;
+      } else if (got[i].index || strcmp(got[i].left, off[i].left) != 0 || got[i].status != off[i].status) {
+        printf("%s: left to zlib without the switch (%s, status %u), with it: %s, status %u\n", what, off[i].left, off[i].status, got[i].index ? "indexed" : got[i].left, got[i].status);
+        ++span_bad;
+      }
+    }
+    if (s0.candidates || s0.streams || s0.adopted || s0.dropped || s0.max_in_flight || s0.wasted_text) { printf("span %llu: the walk without the switch counts streams\n", (unsigned long long)span); ++span_bad; }
+    printf("members: span=%llu files=%llu walked=%llu left_to_zlib=%llu rounds=%llu serial_rounds=%llu text=%llu serial_text=%llu candidates=%llu streams=%llu adopted=%llu dropped=%llu max_in_flight=%llu wasted_text=%llu bad=%d\n",
+           (unsigned long long)span, (unsigned long long)s1.files, (unsigned long long)s1.walked, (unsigned long long)s1.left_to_zlib, (unsigned long long)s1.rounds, (unsigned long long)s0.rounds, (unsigned long long)s1.text_bytes,
+           (unsigned long long)s0.text_bytes, (unsigned long long)s1.candidates, (unsigned long long)s1.streams, (unsigned long long)s1.adopted, (unsigned long long)s1.dropped, (unsigned long long)s1.max_in_flight,
+           (unsigned long long)s1.wasted_text, span_bad);
+    bad += span_bad;
+  }
+  FILE* f = fopen(argv[2], "rb");
+  if (!f) { printf("%s: cannot open\n", argv[2]); return 2; }
+  std::vector<uint8_t> raw; uint8_t buf[65536]; size_t k;
+  while ((k = fread(buf, 1, sizeof buf, f)) > 0) raw.insert(raw.end(), buf, buf + k);
+  fclose(f);
+  uint64_t counts[4] = { 0, 0, 0, 0 };
+  bad += random_steps(raw, counts);
+  if (g_walk_overrun) { printf("%llu steps wrote behind their room or their history\n", (unsigned long long)g_walk_overrun); ++bad; }
+  printf("random: %llu steps ended at a boundary, %llu ran out of input, %llu out of room, %llu were refused; %d bad\n", (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3], bad);
+  return bad != 0;
+}
+
 // hand-made segments (inflate_host_cases.py: write_segments): each with its own file and a history at a given alignment
 static int segments_main(const char* path)
 {
@@ -389,6 +481,9 @@ int main(int argc, char** argv)
   }
   if (argc >= 3 && !strcmp(argv[1], "--walk")) {
     return walk_main(argc, argv);
+  }
+  if (argc >= 3 && !strcmp(argv[1], "--members")) {
+    return members_main(argc, argv);
   }
   if (argc >= 3 && !strcmp(argv[1], "--segments")) {
     return segments_main(argv[2]);
